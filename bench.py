@@ -19,7 +19,9 @@ detector's `binary` output.  The whole chain (D2H, contours, unclip, rectangles,
 the timed region.  Images shard across ranks with no data-path collective (weak scaling); RCCL is used once, to broadcast the packed
 weight blobs from rank 0.
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for the roofline / cpu_baseline / parity definitions).
+Prints ONE JSON line on rank 0.  A plain run measures the headline mode only; `--full` adds the further modes (--also), the per-kernel
+roofline pass, the parity re-run and the CPU baseline (see DESIGN.md "Measurement" for their definitions).  `--dump-outputs DIR` writes
+the last timed step's outputs as .npy files (write_outputs below), so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -41,6 +43,7 @@ PEAK_TFLOPS = {"bf16": 2500.0, "f16": 2500.0, "f32": 157.3, "f16x2": 2500.0 / 3}
 PEAK_HBM_GBS = 8000.0
 PROFILE_ROUND = "r04"
 PARITY_MODES = ("f16x2", "f32")       # modes whose CTC strings equal the CPU reference's (tests/test_gpu_parity_modes.py)
+DUMP_MAP_SAMPLES = 1 << 22            # --dump-outputs: seeded pixel sample of the last step's probability maps (16 MB of the 315 MB at 64 pages)
 
 
 def parse():
@@ -50,10 +53,15 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--dtype", default=None, choices=["bf16", "f16", "f32", "f16x2"],
                     help="operand type of both models for the headline.  Default: f16x2 (fp32-equivalent operands as two fp16 halves on the 16-bit "
-                         "matrix pipe: CTC strings equal the CPU reference's), followed by the --also modes; giving --dtype runs that one mode only")
+                         "matrix pipe: CTC strings equal the CPU reference's), followed with --full by the --also modes; giving --dtype runs that one mode only")
+    ap.add_argument("--full", action="store_true",
+                    help="measure beyond the headline: the --also modes, the per-kernel HIP-event pass (roofline), the fp32-mode parity re-run "
+                         "and the CPU baseline with its CER against the oracle (each of them can be left out with its --no-* / --also option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the headline mode's outputs of the last step to DIR/<name>.npy (write_outputs)")
     ap.add_argument("--also", default="f32,f16",
-                    help="comma list of further modes measured after the headline in the same process on the same inputs (f32 = exact fp32 MFMA, "
-                         "reported as `exact_fp32_mode`; f16 / bf16 = 16-bit throughput mode, reported as `throughput_mode`), or `none`")
+                    help="with --full: comma list of further modes measured after the headline in the same process on the same inputs (f32 = "
+                         "exact fp32 MFMA, reported as `exact_fp32_mode`; f16 / bf16 = 16-bit throughput mode, reported as `throughput_mode`), or `none`")
     ap.add_argument("--workload", default="e2e", choices=["e2e", "det", "rec"])
     ap.add_argument("--batch", type=int, default=64, help="invoices per rank per step (BASELINE.json configs[3])")
     ap.add_argument("--lines", type=int, default=30)
@@ -84,7 +92,10 @@ def parse():
     ap.add_argument("--no-overlap", action="store_true",
                     help="one stream, one step at a time: every kernel runs alone on the chip (the variant the rocprofv3 --stats summary under "
                          "profiles/ is taken from, so that its per-kernel averages can be compared with the HIP-event figures)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:            # a plain run times the headline mode and nothing else
+        args.also, args.no_prof, args.no_parity_check, args.no_cpu_baseline = "none", True, True, True
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ launcher
@@ -548,8 +559,9 @@ def cpu_baseline(args, det_sd, rec_sd, image_u8, crops_f32, gpu_texts, prob_page
             "det_s": round(t_det, 3), "post_s": round(t_post, 4), "crop_prep_s": round(t_pre, 4), "rec_s": round(t_rec, 3)}, cer_cpu
 
 
-def run_mode(args, dtype, dev, cdev, det_blob, rec_blob, images_u8, boxes, local_world, dist, lib):
-    """Warm-up + the timed region + one profiled eager pass for one compute dtype.  Returns a dict of raw results."""
+def run_mode(args, dtype, dev, cdev, det_blob, rec_blob, images_u8, boxes, local_world, dist, lib, sample_maps=False):
+    """Warm-up + the timed region + one profiled eager pass for one compute dtype.  Returns a dict of raw results; with sample_maps also
+    the seeded sample of the last timed step's probability maps that --dump-outputs writes."""
     import copy
     import torch
     from ocr_vi_invoice_amd import _lib
@@ -602,6 +614,15 @@ def run_mode(args, dtype, dev, cdev, det_blob, rec_blob, images_u8, boxes, local
         dt = max_over_ranks(dt, cdev, dist)
     assert len(done) == a.steps, (len(done), a.steps)
     last_rects, texts, counts = done[-1]
+    map_sample = None
+    if sample_maps and pipe.detected:    # before the eager pass below rewrites the maps
+        import numpy as np
+        flat = torch.cat([p.reshape(-1) for p in pipe.prob])
+        if flat.numel() > DUMP_MAP_SAMPLES:
+            idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), size=DUMP_MAP_SAMPLES))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        map_sample = flat.cpu().numpy()
+        del flat
     prof = {}
     if not a.no_prof:
         # graph nodes cannot carry per-kernel events, and under the two-stream pipeline a kernel's duration depends on what shares the
@@ -612,7 +633,7 @@ def run_mode(args, dtype, dev, cdev, det_blob, rec_blob, images_u8, boxes, local
         _lib.check(lib.ocrvi_prof_enable(0))
         prof = _lib.prof_report()
     out = {"dt": dt, "rank_dt": rank_dt, "rects": last_rects, "texts": texts, "counts": counts, "prof": prof, "detected": pipe.detected,
-           "post_threads": pipe.post_threads, "images": pipe.images}
+           "post_threads": pipe.post_threads, "images": pipe.images, "map_sample": map_sample}
     if queue_mode:
         mine = float(sum(len(r[2]) for r in done))           # pages this rank processed over the timed steps
         stolen = float(getattr(pipe, "stolen", 0))
@@ -634,6 +655,29 @@ def run_mode(args, dtype, dev, cdev, det_blob, rec_blob, images_u8, boxes, local
     gc.collect()
     torch.cuda.empty_cache()
     return out
+
+
+def write_outputs(out_dir, m):
+    """--dump-outputs: what the timed path handed its caller in the last timed step (rank 0's shard), as float arrays.
+      det_map_sample   float32 [<= DUMP_MAP_SAMPLES]  the probability maps post-processing ran on (pages x H x W, flattened): all of them,
+                                                   or, when larger, DUMP_MAP_SAMPLES pixel indices drawn with numpy's default_rng(0), sorted
+      rects            float64 [n, 5]              crop rectangles (page, x, y, w, h), in the order the recogniser consumed them
+      boxes_per_page   float64 [pages]             boxes DB post-processing found on each page
+      texts            float64 [n, L]              the recognised strings as Unicode code points, -1 padded (L = longest string, >= 1)
+    Arrays a workload does not produce (no maps with --boxes synthetic-gt, no strings with --workload det) are not written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"det_map_sample": None if m["map_sample"] is None else m["map_sample"].astype(np.float32),
+              "rects": None if m["rects"] is None else np.asarray(m["rects"], np.float64),
+              "boxes_per_page": np.asarray(m["counts"], np.float64) if m["counts"] else None, "texts": None}
+    if m["texts"] is not None:
+        t = np.full((len(m["texts"]), max([1] + [len(s) for s in m["texts"]])), -1.0)
+        for i, s in enumerate(m["texts"]):
+            t[i, :len(s)] = [ord(ch) for ch in s]
+        arrays["texts"] = t
+    for name, arr in arrays.items():
+        if arr is not None:
+            np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def roofline_of(prof, dtype):
@@ -750,7 +794,10 @@ def main():
     boxes = np.ascontiguousarray(np.concatenate(boxes, 0), dtype=np.int32)
     lib = _lib.load()
 
-    m1 = run_mode(args, primary, dev, cdev, det_blob, rec_blob, images_u8, boxes, local_world, dist, lib)
+    m1 = run_mode(args, primary, dev, cdev, det_blob, rec_blob, images_u8, boxes, local_world, dist, lib,
+                  sample_maps=args.dump_outputs is not None)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, m1)
     extra = [(m, run_mode(args, m, dev, cdev, det_blob, rec_blob, images_u8, boxes, local_world, dist, lib)) for m in others]
 
     if rank == 0:

@@ -195,3 +195,34 @@ def test_bench_page_queue_two_ranks_process_every_page_once():
     assert q["n_gpus"] == 2 and q["config"]["global_batch"] == 16 and q["value"] > 0
     assert sum(q["page_queue"]["pages_by_rank"]) == 2 * 16                 # 2 timed steps x 16 pages: none dropped, none twice
     assert "page queue" in q["config"]["parallelism"] and "page_queue" not in out["static"]
+
+
+def test_bench_plain_run_dumps_the_same_outputs_twice(tmp_path):
+    """A plain `bench.py --dump-outputs DIR` at reduced size: the line carries the headline only with `steps` timed steps, the dump holds
+    float arrays of the last step that agree with each other (a rectangle and a string per box), and a second run with the same arguments
+    writes the same outputs (seeded inputs)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B, H, W = 4, 320, 480
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", str(B), "--det-chunk", "2",
+            "--lines", "4", "--height", str(H), "--width", str(W), "--rec-batch", "16"]
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    dumps = []
+    for run in ("a", "b"):
+        r = subprocess.run(base + ["--dump-outputs", str(tmp_path / run)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert res["steps"] == 3 and res["ms_per_step"] > 0 and res["dtype"] == "f16x2" and res["higher_is_better"] is True
+        assert not {"roofline", "cpu_baseline", "exact_fp32_mode", "throughput_mode", "cer_vs_f32_mode"} & set(res)
+        d = {f[:-4]: np.load(tmp_path / run / f) for f in os.listdir(tmp_path / run)}
+        assert sorted(d) == ["boxes_per_page", "det_map_sample", "rects", "texts"]
+        assert all(v.dtype in (np.float32, np.float64) for v in d.values()) and sum(v.nbytes for v in d.values()) <= 64 << 20
+        assert d["det_map_sample"].shape == (B * H * W,) and 0.0 <= d["det_map_sample"].min() and d["det_map_sample"].max() <= 1.0
+        assert d["boxes_per_page"].shape == (B,) and len(d["rects"]) == d["boxes_per_page"].sum() == len(d["texts"]) > 0
+        dumps.append(d)
+    for k in ("rects", "boxes_per_page", "texts"):
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+    np.testing.assert_allclose(dumps[0]["det_map_sample"], dumps[1]["det_map_sample"], rtol=0, atol=1e-6)

@@ -98,7 +98,7 @@ if __name__ == "__main__":
         kernels[t] = {"mangled": a["mangled"], "dispatches": a["dispatches"], "fetch_bytes_per_launch": round(a["fetch"] / a["dispatches"]),
                       "write_bytes_per_launch": round(a["write"] / a["dispatches"]),
                       "traffic_bytes_per_launch": round((a["fetch"] + a["write"]) / a["dispatches"])}
-    json.dump({"_method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in two separate passes (with --kernel-trace only) over `python3 bench.py "
+    json.dump({"_method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in two separate passes (with --kernel-trace only) over `python3 bench.py --full "
                           "--steps 1 --warmup 1 --no-graph --no-prof --no-cpu-baseline --no-parity-check` (every mode of the default run); per-launch averages over all dispatches of the kernels that share a "
                           "tag; bytes = FETCH_SIZE*1024*2 (gfx950 counts 64 B per 128-B request on wide coalesced reads: MI355X_MICROARCH.md, HBM) + "
                           "WRITE_SIZE*1024.  Infinity-Cache hits are included in these fabric-side counters.  Made by tools/pmc_traffic.py.",
