@@ -12,6 +12,7 @@
 #include "gconv32.h"
 #include "dcn_pipe.h"
 #include "offs_conv.h"
+#include "conv3_halo.h"
 
 namespace ocrvi {
 
@@ -230,6 +231,9 @@ int launch_conv(const ConvParams& p_in, int amode, hipStream_t stream) {
         if (gconv32_eligible(p, amode, 2)) return launch_gconv32<T>(p, stream);
     }
     if (offs_conv_eligible(p, amode, TypeInfo<T>::dtype)) return launch_offs_conv<T>(p, stream);
+    if constexpr (IsSplit<T>::value) {
+        if (conv3_halo_eligible(p, amode, TypeInfo<T>::dtype)) return launch_conv3_halo<T>(p, stream);
+    }
     if constexpr (IsSplit<T>::value) {
         if (gemm_duo_eligible(p, amode, TypeInfo<T>::dtype)) return launch_gemm_duo<T>(p, stream);
     }

@@ -265,6 +265,18 @@ bool gemm_ring_eligible(const ConvParams& p, int amode, int dtype) {
     return true;
 }
 
+// The direct halo-tile 3x3 convolution (conv3_halo.h): f16x2, dense, stride 1, pad 1, whole 32-channel blocks, 64 / 128 / 256 columns, plain NHWC
+// output with bias + ReLU / none.  Independent of M and n_img (a page alone and inside a batch take the same kernel and the same K order).
+bool conv3_halo_eligible(const ConvParams& p, int amode, int dtype) {
+    static const bool on = !(getenv("OCRVI_CONV3_HALO") && atoi(getenv("OCRVI_CONV3_HALO")) == 0);   // A/B switch (0: conv_gemm)
+    if (!on || dtype != OCRVI_F16X2 || amode != AM_CONV3 || p.groups != 1 || p.store_mode != ST_NHWC || p.res_mode != RES_NONE || p.out_f32) return false;
+    if (p.KH != 3 || p.SH != 1 || p.SW != 1 || p.PH != 1 || p.PW != 1 || p.H != p.OH || p.W != p.OW) return false;
+    if (p.Cin_g % 32 != 0 || p.Kp != 9 * p.Cin_g || !(p.Np == 64 || p.Np == 128 || p.Np == 256) || p.N_g > p.Np) return false;
+    if (p.act != ACT_NONE && p.act != ACT_RELU) return false;
+    if (p.Cin % 4 != 0 || p.cin_off % 4 != 0 || p.N_g % 4 != 0 || p.ldo % 4 != 0 || p.out_coff % 4 != 0) return false;
+    return ((uintptr_t)p.x & 15) == 0 && ((uintptr_t)p.w & 15) == 0 && ((uintptr_t)p.out & 15) == 0;
+}
+
 // The duo ring GEMM (gemm_duo.h): f16x2 1x1 convolutions / Linears that gemm_ring would take, whose column count tiles by 256 or 192,
 // with at least four K-steps (below that the layers sit on their HBM roof in either kernel) and an epilogue variant that is built
 // (duo_f16x2.hip: launch_duo_ni).  The choice depends on the layer only (N, K, epilogue), never on M, so a page alone and the same page
@@ -427,7 +439,12 @@ int launch_conv_dt(int dtype, const ConvParams& p, int amode, hipStream_t stream
         const bool pipe = amode == AM_DCN && dcn_pipe_eligible(q, dtype);
         static const bool detail = getenv("OCRVI_PROF_DETAIL") != nullptr;
         const bool duo = gemm_duo_eligible(q, amode, dtype);
-        if (duo && !detail)
+        const bool halo = conv3_halo_eligible(q, amode, dtype);
+        if (halo && !detail)
+            snprintf(tag, sizeof(tag), "conv3x3_halo_%s", dtype_name(dtype));
+        else if (halo)
+            snprintf(tag, sizeof(tag), "conv3x3_halo_%s M%d N%d K%d g%d s%d", dtype_name(dtype), p.M, p.N_g, (int)kvalid, p.groups, p.SH);
+        else if (duo && !detail)
             snprintf(tag, sizeof(tag), "gemm_duo_%s", dtype_name(dtype));
         else if (ring && !detail)
             snprintf(tag, sizeof(tag), "gemm_ring_%s", dtype_name(dtype));
