@@ -145,6 +145,23 @@ int ocrvi_resize_u8(int device, const uint8_t* src, int src_h, int src_w, uint8_
 int ocrvi_crop_resize_normalize(int device, const uint8_t* images, int n_img, int H, int W, const int32_t* boxes, int B,
                                 int out_h, int out_w, float* out, void* stream);
 
+/* Page table of the two *_pages entries below: int64 [n][OCRVI_PAGE_ENTRY] in DEVICE memory, entry i = (device address of page i, a
+ * uint8 HWC [h,w,3] image, h, w, 0).  The kernels read it when they run, not when they are enqueued: a graph captured over these calls
+ * stays valid when the pages are moved and only the table's contents are rewritten.  An entry with a null address or a side <= 0 is
+ * invalid (it is never dereferenced). */
+#define OCRVI_PAGE_ENTRY 4
+/* Replaces the per-image resize_image_for_det (src/pipeline/pipeline2.py:33-40) + normalisation (:312-314) for n pages of their own
+ * sizes that map to one H x W detector shape: out float32 NCHW [n,3,H,W] (16-byte aligned, W % 4 == 0), element for element equal to
+ * ocrvi_resize_u8(page i -> H x W) followed by ocrvi_normalize_u8 on page i alone (an invalid entry gives the normalised zero pixel).
+ * Enqueue-only on `stream`. */
+int ocrvi_resize_normalize_pages(int device, const int64_t* pages, int n, int H, int W, float* out, void* stream);
+/* ocrvi_crop_resize_normalize (crop_image, src/det/test.py:123-130 + preprocess_for_recognition, pipeline2.py:92-128) for crops of
+ * pages of different sizes: boxes int32 [B,5] = (page table index, x, y, w, h); each output equals ocrvi_crop_resize_normalize on that
+ * crop's page alone.  w<=0, h<=0, an index outside [0, n_pages) or an invalid entry yields the all-zero tensor (pipeline2.py:154-156).
+ * Enqueue-only on `stream`. */
+int ocrvi_crop_resize_normalize_pages(int device, const int64_t* pages, int n_pages, const int32_t* boxes, int B, int out_h, int out_w,
+                                      float* out, void* stream);
+
 /* Replaces DBPostProcessor(thresh, box_thresh, max_candidates, unclip_ratio).__call__ with .min_area (src/det/test.py:46-106) on a HOST
  * probability map prob[H*W] (the reference also runs this stage on the CPU after `.cpu().numpy()`, pipeline2.py:320-321).
  * Output: the unclipped polygons as int32 (x, y) pairs in points[2*cap_points]; box i owns points box_offsets[i] .. box_offsets[i+1]
@@ -166,6 +183,21 @@ int ocrvi_unclip_polygon(const int32_t* pts, int n_pts, double distance, int32_t
 int ocrvi_db_boxes_batch(const float* prob, int n_pages, int H, int W, float thresh, float box_thresh, int max_candidates,
                          float unclip_ratio, float min_area, double scale_w, double scale_h, int orig_h, int orig_w, int page_base,
                          int32_t* rects, float* scores, int cap_per_page, int32_t* counts, int threads);
+
+/* ocrvi_db_boxes_batch for pages of different original sizes that share one detector shape (the per-image loop of pipeline2.py:306-343
+ * over a bucket of pages): page p's boxes are divided by (scale_w[p], scale_h[p]) = (new_w/w, new_h/h) with the int64 truncation of
+ * pipeline2.py:324-328 and clamped to its orig_h[p] x orig_w[p] page.  Per page p, besides rects (first column = page_ids[p]), scores and
+ * counts as ocrvi_db_boxes_batch writes them:
+ *   points      int32 [n_pages][cap_points][2]      the rescaled polygons (what rescale_boxes returns), box after box
+ *   box_offsets int32 [n_pages][cap_per_page + 1]   box i of page p owns points box_offsets[p][i] .. box_offsets[p][i+1] of its page row
+ *   overflow    int32 [n_pages]                     0, or the number of polygon points page p needs when that exceeds cap_points: its
+ *                                                   points and offsets are then not written (rects, scores and counts are) and the
+ *                                                   caller redoes the page alone with room for them.  No page is truncated.
+ * Runs on the same host thread pool as ocrvi_db_boxes_batch. */
+int ocrvi_db_boxes_pages(const float* prob, int n_pages, int H, int W, float thresh, float box_thresh, int max_candidates, float unclip_ratio,
+                         float min_area, const double* scale_w, const double* scale_h, const int32_t* orig_h, const int32_t* orig_w,
+                         const int32_t* page_ids, int32_t* points, int cap_points, int32_t* box_offsets, int32_t* rects, float* scores,
+                         int cap_per_page, int32_t* counts, int32_t* overflow, int threads);
 
 /* Device half of the same stage (the reference thresholds on the host, `pred[0] > self.thresh`, src/det/test.py:57,
  * after copying the whole map, pipeline2.py:320).  prob: DEVICE float32 [n_pages,H,W] (W % 32 == 0).  Outputs, all DEVICE buffers:

@@ -1,6 +1,6 @@
 """MI355X-native (gfx950) inference engine for the DBNet++ -> SVTRv2 -> CTC invoice OCR hot path.
 
-Importing the package is cheap and CPU-safe; ``DBNetPP`` / ``SVTRv2`` load ``lib/libocrvi.so`` on first use and
+Importing the package is cheap and CPU-safe; ``DBNetPP`` / ``SVTRv2`` / ``Engine`` (batched OCR over pages of mixed sizes) load ``lib/libocrvi.so`` on first use and
 raise if it is missing (there is no CPU fallback)."""
 from .vocab import VOCAB, Tokenizer  # noqa: F401
 
@@ -12,4 +12,7 @@ def __getattr__(name):
     if name == "SVTRv2":
         from .rec import SVTRv2
         return SVTRv2
+    if name == "Engine":
+        from .engine import Engine
+        return Engine
     raise AttributeError(name)

@@ -26,7 +26,9 @@ EXPORTS = [
     "ocrvi_test_deform_conv", "ocrvi_test_offset_conv", "ocrvi_test_conv", "ocrvi_test_gemm", "ocrvi_test_attention", "ocrvi_test_mlp", "ocrvi_test_stem_pool", "ocrvi_test_pack_f16x2",
     "ocrvi_prof_enable", "ocrvi_prof_reset", "ocrvi_prof_report",
     "ocrvi_det_status", "ocrvi_rec_status", "ocrvi_range_reset", "ocrvi_range_flag",
+    "ocrvi_resize_normalize_pages", "ocrvi_crop_resize_normalize_pages", "ocrvi_db_boxes_pages",
 ]
+PAGE_ENTRY = 4          # int64 fields of one page-table entry: (device address, height, width, 0) -- OCRVI_PAGE_ENTRY
 
 
 class DetCfg(C.Structure):
@@ -82,6 +84,10 @@ def load() -> C.CDLL:
     lib.ocrvi_unclip_polygon.argtypes = [vp, i32, C.c_double, vp, i32, C.POINTER(i32)]
     lib.ocrvi_db_boxes_batch.argtypes = [vp, i32, i32, i32, C.c_float, C.c_float, i32, C.c_float, C.c_float, C.c_double, C.c_double, i32, i32, i32,
                                          vp, vp, i32, vp, i32]
+    lib.ocrvi_resize_normalize_pages.argtypes = [i32, vp, i32, i32, i32, f32p, vp]
+    lib.ocrvi_crop_resize_normalize_pages.argtypes = [i32, vp, i32, i32p, i32, i32, i32, f32p, vp]
+    lib.ocrvi_db_boxes_pages.argtypes = [vp, i32, i32, i32, C.c_float, C.c_float, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp,
+                                         vp, i32, vp, vp, vp, i32, vp, vp, i32]
     lib.ocrvi_test_deform_conv.argtypes = [i32, i32, f32p, f32p, f32p, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32p, i32,
                                            C.POINTER(C.c_float)]
     lib.ocrvi_test_offset_conv.argtypes = [i32, i32, f32p, vp, vp, i32, i32, i32, i32, i32, f32p, i32, C.POINTER(C.c_float)]

@@ -425,12 +425,18 @@ extern "C" int ocrvi_db_postprocess(const float* prob, int H, int W, float thres
 // handles one page at a time in Python); everything stays in C so no interpreter lock is held.
 namespace {
 struct PageView { const float* prob; const uint32_t* bits; bool ok; };
+// Where page pg's boxes go in its original image: divide by (scale_w, scale_h), clamp to orig_h x orig_w, tag the rectangles with page_id
+struct PageGeom { double scale_w, scale_h; int orig_h, orig_w, page_id; };
+// Optional sink of the rescaled polygons: page pg's points at points + pg * cap_points * 2, its box offsets at offsets + pg * (cap_per_page
+// + 1); overflow[pg] = points needed when they do not fit (nothing of the polygons is written then)
+struct PolySink { int32_t* points; int cap_points; int32_t* offsets; int32_t* overflow; };
 
-// Shared body of the batch entries: page(pg, slot) hands over the map (and optionally its bit mask) of page pg for host thread `slot`.
-template <typename PageFn>
-int boxes_batch_impl(PageFn page, int n_pages, int H, int W, float thresh, float box_thresh, int max_candidates, float unclip_ratio,
-                     float min_area, double scale_w, double scale_h, int orig_h, int orig_w, int page_base, int32_t* rects, float* scores,
-                     int cap_per_page, int32_t* counts, int threads, int32_t* skipped) {
+// Shared body of the batch entries: page(pg, slot) hands over the map (and optionally its bit mask) of page pg for host thread `slot`,
+// geom(pg) its rescaling and clamping.
+template <typename PageFn, typename GeomFn>
+int boxes_batch_impl(PageFn page, GeomFn geom, int n_pages, int H, int W, float thresh, float box_thresh, int max_candidates, float unclip_ratio,
+                     float min_area, int32_t* rects, float* scores, int cap_per_page, int32_t* counts, int threads, int32_t* skipped,
+                     const PolySink* poly = nullptr) {
     using namespace ocrvi;
     std::atomic<int> next(0), failed(0);
     static std::vector<std::vector<signed char>> label_pool;    // padded label images, kept across calls (page faults cost more than the scan)
@@ -457,19 +463,27 @@ int boxes_batch_impl(PageFn page, int n_pages, int H, int W, float thresh, float
                 cap_pts *= 4;
             }
             if (rc != OCRVI_OK) { failed.store(rc); counts[pg] = 0; continue; }
+            const PageGeom g = geom(pg);
             int32_t* out = rects + (size_t)pg * cap_per_page * 5;
+            const bool keep_poly = poly && offs[nb] <= poly->cap_points;
+            int32_t* ppts = keep_poly ? poly->points + (size_t)pg * poly->cap_points * 2 : nullptr;
+            if (poly) {
+                poly->overflow[pg] = keep_poly ? 0 : offs[nb];
+                if (keep_poly) memcpy(poly->offsets + (size_t)pg * (cap_per_page + 1), offs.data(), sizeof(int32_t) * (nb + 1));
+            }
             for (int b = 0; b < nb; ++b) {
                 long long x0 = 0, x1 = 0, y0 = 0, y1 = 0;
                 for (int i = offs[b]; i < offs[b + 1]; ++i) {
                     // rescaled_box[:, 0] = rescaled_box[:, 0] / scale_w into an integer array: C truncation toward zero; then astype(int32)
-                    const long long x = (long long)((double)pts[2 * i] / scale_w), y = (long long)((double)pts[2 * i + 1] / scale_h);
+                    const long long x = (long long)((double)pts[2 * i] / g.scale_w), y = (long long)((double)pts[2 * i + 1] / g.scale_h);
+                    if (ppts) { ppts[2 * i] = (int32_t)x; ppts[2 * i + 1] = (int32_t)y; }
                     if (i == offs[b]) { x0 = x1 = x; y0 = y1 = y; }
                     x0 = std::min(x0, x); x1 = std::max(x1, x); y0 = std::min(y0, y); y1 = std::max(y1, y);
                 }
                 const long long bw = x1 - x0 + 1, bh = y1 - y0 + 1;          // cv2.boundingRect of integer points is inclusive
                 const long long cx = std::max(0LL, x0), cy = std::max(0LL, y0);
-                const long long cw = std::max(0LL, std::min(bw, (long long)orig_w - cx)), ch = std::max(0LL, std::min(bh, (long long)orig_h - cy));
-                out[5 * b] = page_base + pg; out[5 * b + 1] = (int32_t)cx; out[5 * b + 2] = (int32_t)cy; out[5 * b + 3] = (int32_t)cw; out[5 * b + 4] = (int32_t)ch;
+                const long long cw = std::max(0LL, std::min(bw, (long long)g.orig_w - cx)), ch = std::max(0LL, std::min(bh, (long long)g.orig_h - cy));
+                out[5 * b] = g.page_id; out[5 * b + 1] = (int32_t)cx; out[5 * b + 2] = (int32_t)cy; out[5 * b + 3] = (int32_t)cw; out[5 * b + 4] = (int32_t)ch;
                 if (scores) scores[(size_t)pg * cap_per_page + b] = sc[b];
             }
             counts[pg] = nb;
@@ -495,8 +509,30 @@ extern "C" int ocrvi_db_boxes_batch(const float* prob, int n_pages, int H, int W
                 OCRVI_EINVAL, "db_boxes_batch: bad argument");
     std::lock_guard<std::mutex> lk(g_batch_mu);
     auto page = [&](int pg, int) { return PageView{prob + (size_t)pg * H * W, nullptr, true}; };
-    return boxes_batch_impl(page, n_pages, H, W, thresh, box_thresh, max_candidates, unclip_ratio, min_area, scale_w, scale_h, orig_h, orig_w,
-                            page_base, rects, scores, cap_per_page, counts, threads, nullptr);
+    auto geom = [&](int pg) { return PageGeom{scale_w, scale_h, orig_h, orig_w, page_base + pg}; };
+    return boxes_batch_impl(page, geom, n_pages, H, W, thresh, box_thresh, max_candidates, unclip_ratio, min_area, rects, scores, cap_per_page,
+                            counts, threads, nullptr);
+}
+
+// ocrvi_db_boxes_batch with each page's own rescaling, original size and id, plus the rescaled polygons themselves (what the per-image
+// loop's rescale_boxes hands on, pipeline2.py:324-328): the pages of one detector shape usually come from originals of different sizes.
+extern "C" int ocrvi_db_boxes_pages(const float* prob, int n_pages, int H, int W, float thresh, float box_thresh, int max_candidates, float unclip_ratio,
+                                    float min_area, const double* scale_w, const double* scale_h, const int32_t* orig_h, const int32_t* orig_w,
+                                    const int32_t* page_ids, int32_t* points, int cap_points, int32_t* box_offsets, int32_t* rects, float* scores,
+                                    int cap_per_page, int32_t* counts, int32_t* overflow, int threads) {
+    using namespace ocrvi;
+    OCRVI_CHECK(prob && scale_w && scale_h && orig_h && orig_w && page_ids && points && box_offsets && rects && counts && overflow && n_pages > 0 &&
+                    H > 0 && W > 0 && cap_points >= 0 && cap_per_page > 0,
+                OCRVI_EINVAL, "db_boxes_pages: bad argument");
+    for (int pg = 0; pg < n_pages; ++pg)
+        OCRVI_CHECK(scale_w[pg] > 0 && scale_h[pg] > 0 && orig_h[pg] > 0 && orig_w[pg] > 0, OCRVI_EINVAL,
+                    "db_boxes_pages: page %d has a non-positive scale or size", pg);
+    std::lock_guard<std::mutex> lk(g_batch_mu);
+    auto page = [&](int pg, int) { return PageView{prob + (size_t)pg * H * W, nullptr, true}; };
+    auto geom = [&](int pg) { return PageGeom{scale_w[pg], scale_h[pg], orig_h[pg], orig_w[pg], page_ids[pg]}; };
+    const PolySink sink{points, cap_points, box_offsets, overflow};
+    return boxes_batch_impl(page, geom, n_pages, H, W, thresh, box_thresh, max_candidates, unclip_ratio, min_area, rects, scores, cap_per_page,
+                            counts, threads, nullptr, &sink);
 }
 
 // The same stage fed by the device half (ocrvi_db_components, dbcomp.hip): per page the 1-bit thresholded mask, the component table
@@ -533,6 +569,7 @@ extern "C" int ocrvi_db_boxes_batch_sparse(const uint32_t* mask_bits, const int3
         }
         return PageView{m.data(), mask_bits + (size_t)pg * H * (W >> 5), true};
     };
-    return boxes_batch_impl(page, n_pages, H, W, 0.f, box_thresh, max_candidates, unclip_ratio, min_area, scale_w, scale_h, orig_h, orig_w, page_base,
-                            rects, scores, cap_per_page, counts, threads, skipped);
+    auto geom = [&](int pg) { return PageGeom{scale_w, scale_h, orig_h, orig_w, page_base + pg}; };
+    return boxes_batch_impl(page, geom, n_pages, H, W, 0.f, box_thresh, max_candidates, unclip_ratio, min_area, rects, scores, cap_per_page, counts,
+                            threads, skipped);
 }

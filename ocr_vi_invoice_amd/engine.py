@@ -1,0 +1,382 @@
+"""Batched OCR over pages of mixed sizes: the reference's per-image loop (src/pipeline/pipeline2.py:279-352) for a whole folder of
+invoices at once, on the graph-replayed, two-stream path.
+
+Pages are grouped into **buckets**: the pages that ``resize_image_for_det`` (pipeline2.py:33-40) maps to the same x32 detector shape.
+A page is never padded into a larger shape (that would change the detector's output near its edges).  Each bucket runs through the
+detector in chunks of up to ``det_chunk`` pages; the crops of every page of every bucket then share recogniser batches.
+
+Per detector chunk, on the detector stream: the chunk's page table -> device, ``ocrvi_resize_normalize_pages`` + ``ocrvi_det_forward``
+(binary map only; one captured graph per (H, W, n), kept in an LRU of ``graph_cache``), the optional ``prob_hook``, the map -> a pinned
+host slot of two, an event.  The host post-processes chunk c (``ocrvi_db_boxes_pages``) while the device runs chunk c + 1.  Rectangles
+accumulate across chunks and buckets; each full ``rec_batch`` goes out on the recogniser stream: rectangles -> device,
+``ocrvi_crop_resize_normalize_pages`` + ``ocrvi_rec_forward`` (one captured graph), ids / lens -> a pinned host slot, an event.
+
+Every result equals ``pipeline.detect_and_recognize`` run on that page alone in the f32 and f16x2 modes ("Batched engine":
+in bf16 / f16 a kernel choice depends on the batch's row count, so a page inside a chunk may be computed differently from alone).
+"""
+from __future__ import annotations
+
+import collections
+import ctypes as C
+import math
+import os
+import time
+from typing import Dict, List, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from .pipeline import DBPostProcessor, db_boxes_pages
+
+_ARENA_ALIGN = 256
+_STREAMS: Dict[int, Tuple[torch.cuda.Stream, torch.cuda.Stream]] = {}
+
+
+def plan_buckets(sizes: Sequence[Tuple[int, int]], det_size: int):
+    """The detector shape of every page, with the reference's arithmetic (pipeline2.py:36-39): float64 ``scale = det_size / max(h, w)``,
+    ``new = int(np.round(side * scale / 32) * 32)`` (round half to even: a 960 x 1280 page at det_size 960 gives 704 x 960).
+    ``sizes``: (h, w) per page.  Returns (shapes [(new_h, new_w)], scales [(scale_h, scale_w)] = (new_h / h, new_w / w), buckets
+    {(new_h, new_w): [page indices, in input order]} in order of first appearance).  A page whose side rounds to 0 raises ValueError
+    naming it (cv2.resize raises there in the reference)."""
+    shapes, scales, buckets = [], [], {}
+    for i, hw in enumerate(sizes):
+        h, w = int(hw[0]), int(hw[1])
+        if h <= 0 or w <= 0:
+            raise ValueError(f"page {i}: empty image ({h}x{w})")
+        scale = det_size / max(h, w)
+        new_h = int(np.round(h * scale / 32) * 32)
+        new_w = int(np.round(w * scale / 32) * 32)
+        if new_h <= 0 or new_w <= 0:
+            raise ValueError(f"page {i}: {h}x{w} resizes to {new_h}x{new_w} at det_size {det_size} (a side rounds to 0; the reference's "
+                             "cv2.resize rejects it)")
+        shapes.append((new_h, new_w))
+        scales.append((new_h / h, new_w / w))
+        buckets.setdefault((new_h, new_w), []).append(i)
+    return shapes, scales, buckets
+
+
+def _usable_cores(cap: int = 16) -> int:
+    try:
+        n = len(os.sched_getaffinity(0))
+    except AttributeError:
+        n = os.cpu_count() or 1
+    return max(1, min(n, cap))
+
+
+class Engine:
+    """``run(pages)`` -> [(boxes, scores, texts) per page, in input order], each exactly what ``pipeline.detect_and_recognize(page,
+    det_model, rec_model, post_processor, det_size=det_size, rec_size=rec_size)`` returns for that page alone.
+
+    ``det_model`` / ``rec_model``: the library's ``DBNetPP`` / ``SVTRv2`` (same device).  Defaults follow pipeline2's CLI (:212-220).
+    ``max_pages`` pages are resident at a time in one device arena (a wave); ``graphs=False`` launches eagerly (same bits).
+    ``prob_hook(prob, page_indices)``: called on the detector stream after each chunk's forward with the device map [n,1,H,W] (edit it in
+    place) and the input indices of its pages -- how random-weight runs get a map with text structure.  It runs eagerly, outside the
+    captured graphs.  ``post_threads``: host threads of the box stage (0 = the cores this process may use, at most 16).
+    The captured graphs hold the models' weights as they were: after reloading a model's weights, build a new Engine."""
+
+    def __init__(self, det_model, rec_model, post_processor: DBPostProcessor, det_size: int = 960, rec_size: Tuple[int, int] = (32, 256),
+                 det_chunk: int = 16, rec_batch: int = 256, max_pages: int = 256, graphs: bool = True, graph_cache: int = 16,
+                 post_threads: int = 0, prob_hook=None):
+        rh, rw = int(rec_size[0]), int(rec_size[1])
+        if rh <= 0 or rw <= 0 or rh % 16 or rw % 4:
+            raise ValueError(f"rec_size {rec_size}: the height must be a multiple of 16 and the width of 4")
+        if det_size <= 0 or det_chunk <= 0 or rec_batch <= 0 or max_pages <= 0 or graph_cache <= 0:
+            raise ValueError("det_size, det_chunk, rec_batch, max_pages and graph_cache must be positive")
+        self.det, self.rec, self.pp = det_model, rec_model, post_processor
+        self.dev = det_model.device if det_model.device.index is not None else torch.device("cuda", det_model._dev_index())
+        self.devi = det_model._dev_index()
+        if rec_model._dev_index() != self.devi:
+            raise ValueError(f"det_model is on cuda:{self.devi}, rec_model on cuda:{rec_model._dev_index()}")
+        self.det_size, self.rec_size = int(det_size), (rh, rw)
+        self.det_chunk, self.rec_batch, self.max_pages = int(det_chunk), int(rec_batch), int(max_pages)
+        self.graphs, self.graph_cache, self.prob_hook = bool(graphs), int(graph_cache), prob_hook
+        self.post_threads = int(post_threads) or _usable_cores()
+        self.lib = _lib.load()
+        # every bucket det_size can produce fits in L x L (the longer side rounds to 32 round(det_size / 32); ceil covers a tie)
+        self.L = L = 32 * int(math.ceil(det_size / 32))
+        # the strided 1x1 layers and the 32-bit epilogue offsets of the ring GEMM switch kernels at n H W 64 bytes >= 2^32 (the widest
+        # tensor: 256 fp32 / f16x2 channels at H/4 x W/4): a chunk past that would not compute what a page alone computes
+        if self.det_chunk * L * L * 64 >= (1 << 32) - (1 << 20):
+            raise ValueError(f"det_chunk {det_chunk} at det_size {det_size}: a {det_chunk}-page {L}x{L} chunk leaves the kernels a page alone "
+                             "takes (n * L * L * 64 bytes must stay below 2^32); use a smaller det_chunk")
+        d = dict(device=self.dev)
+        # ---- detector: one workspace for every bucket shape at det_chunk (never the facade's per-shape cache, which frees the previous
+        #      shape's buffer: a graph captured for one bucket would replay into freed memory)
+        need = 0
+        for s in range(32, L + 1, 32):
+            for (h, w) in ((L, s), (s, L)):
+                need = max(need, self._det_ws_bytes(self.det_chunk, h, w))
+        self.det_ws = torch.empty(max(need, 1), dtype=torch.uint8, **d)
+        self.d_x = torch.empty(self.det_chunk * 3 * L * L, dtype=torch.float32, **d)
+        self.d_bin = torch.empty(self.det_chunk * L * L, dtype=torch.float32, **d)
+        self.d_det_table = torch.zeros((self.det_chunk, _lib.PAGE_ENTRY), dtype=torch.int64, **d)
+        self.h_map = [torch.empty(self.det_chunk * L * L, dtype=torch.float32).pin_memory() for _ in range(2)]
+        self.ev_map = [torch.cuda.Event() for _ in range(2)]
+        # ---- recogniser: one batch shape, one workspace, one graph
+        n = C.c_size_t()
+        _lib.check(self.lib.ocrvi_rec_workspace_bytes(rec_model._handle, self.rec_batch, rh, rw, C.byref(n)))
+        self.rec_ws = torch.empty(max(n.value, 1), dtype=torch.uint8, **d)
+        T = rw // 4
+        self.d_rects = torch.zeros((self.rec_batch, 5), dtype=torch.int32, **d)
+        self.d_crops = torch.empty((self.rec_batch, 3, rh, rw), dtype=torch.float32, **d)
+        self.d_am = torch.empty((self.rec_batch, T), dtype=torch.int32, **d)
+        self.d_ids = torch.empty((self.rec_batch, T), dtype=torch.int32, **d)
+        self.d_lens = torch.empty((self.rec_batch,), dtype=torch.int32, **d)
+        self.d_rec_table = torch.zeros((self.max_pages, _lib.PAGE_ENTRY), dtype=torch.int64, **d)
+        nslots = 4
+        self.h_rects = [torch.zeros((self.rec_batch, 5), dtype=torch.int32).pin_memory() for _ in range(nslots)]
+        self.h_ids = [torch.empty((self.rec_batch, T), dtype=torch.int32).pin_memory() for _ in range(nslots)]
+        self.h_lens = [torch.empty((self.rec_batch,), dtype=torch.int32).pin_memory() for _ in range(nslots)]
+        self.ev_rec = [torch.cuda.Event() for _ in range(nslots)]
+        # ---- pages: one device arena per wave, filled through pinned staging; the wave's page table (pinned, arena order)
+        self.arena = torch.empty(0, dtype=torch.uint8, **d)
+        self.h_stage = torch.empty(0, dtype=torch.uint8)
+        self.h_table = torch.zeros((self.max_pages, _lib.PAGE_ENTRY), dtype=torch.int64).pin_memory()
+        # one stream pair per device for every engine of the process: each new HIP stream takes the next hardware queue round-robin
+        if self.devi not in _STREAMS:
+            _STREAMS[self.devi] = (torch.cuda.Stream(self.dev), torch.cuda.Stream(self.dev))
+        self.s_det, self.s_rec = _STREAMS[self.devi]
+        self._det_graphs: "collections.OrderedDict[tuple, torch.cuda.CUDAGraph]" = collections.OrderedDict()
+        self._rec_graph = None
+        self._rec_warm = False
+        self.stats = {}
+
+    # ------------------------------------------------------------------------------------------------ device work (enqueue-only)
+    def _det_ws_bytes(self, n, h, w) -> int:
+        b = C.c_size_t()
+        _lib.check(self.lib.ocrvi_det_workspace_bytes(self.det._handle, n, h, w, C.byref(b)))
+        return b.value
+
+    def _det_calls(self, n, H, W):
+        st = self.s_det.cuda_stream
+        _lib.check(self.lib.ocrvi_resize_normalize_pages(self.devi, self.d_det_table.data_ptr(), n, H, W, self.d_x.data_ptr(), st))
+        _lib.check(self.lib.ocrvi_det_forward(self.det._handle, self.d_x.data_ptr(), n, H, W, self.d_bin.data_ptr(), None, None, None, None,
+                                              self.det_ws.data_ptr(), self.det_ws.numel(), st))
+
+    def _rec_calls(self):
+        st = self.s_rec.cuda_stream
+        rh, rw = self.rec_size
+        _lib.check(self.lib.ocrvi_crop_resize_normalize_pages(self.devi, self.d_rec_table.data_ptr(), self.max_pages, self.d_rects.data_ptr(),
+                                                              self.rec_batch, rh, rw, self.d_crops.data_ptr(), st))
+        _lib.check(self.lib.ocrvi_rec_forward(self.rec._handle, self.d_crops.data_ptr(), self.rec_batch, rh, rw, None, self.d_am.data_ptr(),
+                                              self.d_ids.data_ptr(), self.d_lens.data_ptr(), self.rec_ws.data_ptr(), self.rec_ws.numel(), st))
+
+    def _run_det(self, n, H, W):
+        """Steps 2 and 3 of a chunk on the detector stream: the cached graph of (H, W, n), or an eager launch that is captured after it."""
+        if not self.graphs:
+            self._det_calls(n, H, W)
+            return
+        key = (H, W, n)
+        g = self._det_graphs.get(key)
+        if g is not None:
+            self._det_graphs.move_to_end(key)
+            g.replay()
+            return
+        self._det_calls(n, H, W)                  # first use: the real launch (also warms up what a capture must not do)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=self.s_det):   # (synchronises the device first: no evicted graph is still running below)
+            self._det_calls(n, H, W)
+        self._det_graphs[key] = g
+        while len(self._det_graphs) > self.graph_cache:
+            self._det_graphs.popitem(last=False)
+
+    def _run_rec(self):
+        if not self.graphs:
+            self._rec_calls()
+        elif self._rec_graph is not None:
+            self._rec_graph.replay()
+        else:
+            self._rec_calls()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=self.s_rec):
+                self._rec_calls()
+            self._rec_graph = g
+
+    # ------------------------------------------------------------------------------------------------ input
+    @staticmethod
+    def _check_page(i, p):
+        if isinstance(p, np.ndarray):
+            ok = p.dtype == np.uint8
+        elif isinstance(p, torch.Tensor):
+            ok = p.dtype == torch.uint8
+        else:
+            raise ValueError(f"page {i}: expected an RGB uint8 HxWx3 numpy array or tensor, got {type(p).__name__}")
+        if not ok or p.ndim != 3 or p.shape[2] != 3:
+            raise ValueError(f"page {i}: expected an RGB uint8 HxWx3 array, got dtype {p.dtype} shape {tuple(p.shape)}")
+        return int(p.shape[0]), int(p.shape[1])
+
+    def _stage(self, pages, wave, lo, hi):
+        """Pages wave[lo:hi] (consecutive arena slots) -> the arena, on the detector stream."""
+        for slot in range(lo, hi):
+            i = wave[slot]
+            p, off, nb = pages[i], self._offs[slot], self._nbytes[slot]
+            dst = self.arena[off:off + nb]
+            if isinstance(p, torch.Tensor) and p.is_cuda:
+                dst.copy_(p.contiguous().view(-1), non_blocking=True)
+            else:
+                src = p.numpy() if isinstance(p, torch.Tensor) else p
+                stage = self.h_stage[off:off + nb].numpy()
+                np.copyto(stage.reshape(src.shape), src)
+                dst.copy_(self.h_stage[off:off + nb], non_blocking=True)
+
+    # ------------------------------------------------------------------------------------------------ recogniser batches
+    def _launch_rec(self, rows, tags):
+        if len(self._rec_inflight) == len(self.h_rects):
+            self._decode_oldest()
+        k = self._rec_slot
+        self._rec_slot = (k + 1) % len(self.h_rects)
+        hr = self.h_rects[k].numpy()
+        hr[:len(rows)] = rows
+        hr[len(rows):] = 0                        # w = h = 0: the all-zero tensor; its string is dropped
+        with torch.cuda.stream(self.s_rec):
+            self.d_rects.copy_(self.h_rects[k], non_blocking=True)
+            self._run_rec()
+            self.h_ids[k].copy_(self.d_ids, non_blocking=True)
+            self.h_lens[k].copy_(self.d_lens, non_blocking=True)
+            self.ev_rec[k].record(self.s_rec)
+        self._rec_inflight.append((k, tags))
+        self.stats["rec_batches"] += 1
+
+    def _decode_oldest(self):
+        k, tags = self._rec_inflight.popleft()
+        t0 = time.perf_counter()
+        self.ev_rec[k].synchronize()
+        self.stats["rec_wait_s"] += time.perf_counter() - t0
+        n = len(tags)
+        ids, lens = self.h_ids[k][:n].tolist(), self.h_lens[k][:n].tolist()
+        texts = self.rec.tokenizer.decode([row[:m] for row, m in zip(ids, lens)])
+        for (pg, b), t in zip(tags, texts):
+            self._texts[pg][b] = t
+
+    def _feed(self, rects, tags):
+        self._pend_rects.extend(rects)
+        self._pend_tags.extend(tags)
+        rb = self.rec_batch
+        while len(self._pend_rects) >= rb:
+            self._launch_rec(self._pend_rects[:rb], self._pend_tags[:rb])
+            del self._pend_rects[:rb], self._pend_tags[:rb]
+
+    # ------------------------------------------------------------------------------------------------ detector chunks
+    def _post(self, job):
+        """Host stage of a launched chunk: wait for its map, ocrvi_db_boxes_pages, rectangles -> the recogniser queue."""
+        idx, slots, (H, W), s = job
+        n = len(idx)
+        t0 = time.perf_counter()
+        self.ev_map[s].synchronize()
+        t1 = time.perf_counter()
+        maps = self.h_map[s][:n * H * W].view(n, H, W)
+        res = db_boxes_pages(maps, self.pp, [self._scales[i] for i in idx], [self._sizes[i] for i in idx], slots, threads=self.post_threads)
+        self.stats["det_wait_s"] += t1 - t0
+        self.stats["post_s"] += time.perf_counter() - t1
+        rects, tags = [], []
+        for i, (polys, r, sc) in zip(idx, res):
+            self._boxes[i], self._scores[i] = polys, [float(v) for v in sc]
+            self._texts[i] = [None] * len(polys)
+            rects.extend(r.tolist())
+            tags.extend((i, b) for b in range(len(polys)))
+        self.stats["crops"] += len(rects)
+        self._feed(rects, tags)
+
+    def _launch_det(self, pages, wave, lo, hi, shape, s):
+        H, W = shape
+        n = hi - lo
+        idx = wave[lo:hi]
+        t0 = time.perf_counter()
+        with torch.cuda.stream(self.s_det):
+            self._stage(pages, wave, lo, hi)
+            self.d_det_table[:n].copy_(self.h_table[lo:hi], non_blocking=True)
+            self._run_det(n, H, W)
+            if self.prob_hook is not None:
+                self.prob_hook(self.d_bin[:n * H * W].view(n, 1, H, W), list(idx))
+            self.h_map[s][:n * H * W].copy_(self.d_bin[:n * H * W], non_blocking=True)
+            self.ev_map[s].record(self.s_det)
+        self.stats["launch_s"] += time.perf_counter() - t0
+        return (idx, list(range(lo, hi)), shape, s)
+
+    def _run_wave(self, pages, wave):
+        # arena layout and page table of the wave (slots in bucket order, so every chunk is a run of consecutive slots)
+        offs, nbytes, off = [], [], 0
+        for i in wave:
+            h, w = self._sizes[i]
+            offs.append(off)
+            nbytes.append(h * w * 3)
+            off += (h * w * 3 + _ARENA_ALIGN - 1) // _ARENA_ALIGN * _ARENA_ALIGN
+        self._offs, self._nbytes = offs, nbytes
+        if self.arena.numel() < off:               # (the previous wave has drained: nothing reads the old arena any more)
+            self.arena = torch.empty(off, dtype=torch.uint8, device=self.dev)
+        if any(not (isinstance(pages[i], torch.Tensor) and pages[i].is_cuda) for i in wave) and self.h_stage.numel() < off:
+            self.h_stage = torch.empty(off, dtype=torch.uint8).pin_memory()
+        tab = self.h_table.numpy()
+        tab[:] = 0
+        base = self.arena.data_ptr()
+        for slot, i in enumerate(wave):
+            tab[slot] = (base + offs[slot], self._sizes[i][0], self._sizes[i][1], 0)
+        with torch.cuda.stream(self.s_rec):
+            self.d_rec_table.copy_(self.h_table, non_blocking=True)
+        # chunks: consecutive slots of one shape, at most det_chunk of them
+        chunks, lo = [], 0
+        while lo < len(wave):
+            shape = self._shapes[wave[lo]]
+            hi = lo + 1
+            while hi < len(wave) and hi - lo < self.det_chunk and self._shapes[wave[hi]] == shape:
+                hi += 1
+            chunks.append((lo, hi, shape))
+            lo = hi
+        pending = collections.deque()
+        for c, (lo, hi, shape) in enumerate(chunks):
+            if len(pending) == 2:                  # its pinned map slot is the one chunk c reuses
+                self._post(pending.popleft())
+            pending.append(self._launch_det(pages, wave, lo, hi, shape, c & 1))
+        while pending:
+            self._post(pending.popleft())
+        # drain the wave: the last partial recogniser batch goes out padded, every string is decoded
+        if self._pend_rects:
+            self._launch_rec(self._pend_rects, self._pend_tags)
+            self._pend_rects, self._pend_tags = [], []
+        while self._rec_inflight:
+            self._decode_oldest()
+        self.s_det.synchronize()
+        self.s_rec.synchronize()                   # (the table upload, even when the wave produced no crop)
+
+    # ------------------------------------------------------------------------------------------------ public
+    def run(self, pages: Sequence) -> List[Tuple[list, list, list]]:
+        pages = list(pages)
+        sizes = [self._check_page(i, p) for i, p in enumerate(pages)]
+        shapes, scales, buckets = plan_buckets(sizes, self.det_size)     # raises before any GPU work
+        for i, (h, w) in enumerate(shapes):
+            if h > self.L or w > self.L:
+                raise RuntimeError(f"page {i}: bucket {h}x{w} exceeds the {self.L}x{self.L} the workspace was sized for")
+        self.stats = {"pages": len(pages), "buckets": {f"{h}x{w}": len(v) for (h, w), v in buckets.items()}, "crops": 0, "rec_batches": 0,
+                      "launch_s": 0.0, "det_wait_s": 0.0, "post_s": 0.0, "rec_wait_s": 0.0}
+        if not pages:
+            return []
+        t_start = time.perf_counter()
+        self._sizes, self._shapes, self._scales = sizes, shapes, scales
+        self._boxes, self._scores, self._texts = [None] * len(pages), [None] * len(pages), [None] * len(pages)
+        self._pend_rects, self._pend_tags = [], []
+        self._rec_inflight, self._rec_slot = collections.deque(), 0
+        order = [i for v in buckets.values() for i in v]
+        cur = torch.cuda.current_stream(self.dev)
+        self.s_det.wait_stream(cur)                # device pages the caller just produced
+        self.s_rec.wait_stream(cur)
+        _lib.check(self.lib.ocrvi_range_reset(self.devi, self.s_det.cuda_stream))
+        self.s_rec.wait_stream(self.s_det)
+        try:
+            for w0 in range(0, len(order), self.max_pages):
+                self._run_wave(pages, order[w0:w0 + self.max_pages])
+        finally:
+            self.s_det.synchronize()
+            self.s_rec.synchronize()
+        rc = self.lib.ocrvi_det_status(self.det._handle)
+        if rc == 0:
+            rc = self.lib.ocrvi_rec_status(self.rec._handle)
+        if rc != 0:
+            msg = _lib.last_error()
+            _lib.check(self.lib.ocrvi_range_reset(self.devi, self.s_det.cuda_stream))
+            self.s_det.synchronize()
+            if rc == -5:
+                raise OverflowError(msg)
+            _lib.check(rc)
+        self.stats["total_s"] = time.perf_counter() - t_start
+        return [(self._boxes[i], self._scores[i], self._texts[i]) for i in range(len(pages))]

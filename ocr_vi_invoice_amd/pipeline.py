@@ -163,6 +163,61 @@ def db_boxes_batch(prob_maps, post_processor: "DBPostProcessor", scale_w: float 
         np.concatenate([scores[i, :counts[i]] for i in range(n)], 0)
 
 
+
+def db_boxes_pages(prob_maps, post_processor: "DBPostProcessor", scales, orig_sizes, page_ids=None, threads: int = 8, cap_points: int = None,
+                   cap_per_page: int = None):
+    """``db_boxes_batch`` for maps of one shape whose pages have their own scale and original size (``ocrvi_db_boxes_pages``): for page p,
+    ``post_processor`` on its map -> ``rescale_boxes`` with ``scales[p] = (scale_h, scale_w)`` -> ``crop_rect`` in ``orig_sizes[p] = (h, w)``.
+    ``prob_maps``: float32 [n,H,W] host array (numpy, or a CPU/pinned torch tensor).  ``cap_points``: polygon points room per page (default
+    4 (H + W) + 4096); a page that needs more is redone alone with the room it reported.  Returns, per page, (rescaled polygons [int32 (k, 2)],
+    rects int32 [k,5] = (page_ids[p], x, y, w, h), scores float32 [k])."""
+    if isinstance(prob_maps, torch.Tensor):
+        assert not prob_maps.is_cuda and prob_maps.dtype == torch.float32 and prob_maps.is_contiguous()
+        n, H, W = prob_maps.shape[-3:] if prob_maps.dim() >= 3 else (1,) + tuple(prob_maps.shape)
+        ptr = prob_maps.data_ptr()
+    else:
+        prob_maps = np.ascontiguousarray(prob_maps, dtype=np.float32)
+        if prob_maps.ndim == 2:
+            prob_maps = prob_maps[None]
+        n, H, W = prob_maps.shape
+        ptr = prob_maps.ctypes.data
+    sh = np.ascontiguousarray([s[0] for s in scales], np.float64)
+    sw = np.ascontiguousarray([s[1] for s in scales], np.float64)
+    oh = np.ascontiguousarray([o[0] for o in orig_sizes], np.int32)
+    ow = np.ascontiguousarray([o[1] for o in orig_sizes], np.int32)
+    ids = np.ascontiguousarray(np.arange(n) if page_ids is None else page_ids, np.int32)
+    assert len(sh) == len(sw) == len(oh) == len(ow) == len(ids) == n
+    cap = int(cap_per_page or max(int(post_processor.max_candidates), 1))
+    cap_pts = int(4 * (H + W) + 4096 if cap_points is None else cap_points)
+    lib = _lib.load()
+
+    def call(i0, i1, cap_pts):
+        m = i1 - i0
+        pts = np.empty((m, max(cap_pts, 1), 2), np.int32)
+        offs = np.empty((m, cap + 1), np.int32)
+        rects = np.empty((m, cap, 5), np.int32)
+        scores = np.empty((m, cap), np.float32)
+        counts, over = np.empty(m, np.int32), np.empty(m, np.int32)
+        _lib.check(lib.ocrvi_db_boxes_pages(ptr + i0 * H * W * 4, m, H, W, float(post_processor.thresh), float(post_processor.box_thresh),
+                                            int(post_processor.max_candidates), float(post_processor.unclip_ratio), float(post_processor.min_area),
+                                            sw[i0:].ctypes.data, sh[i0:].ctypes.data, oh[i0:].ctypes.data, ow[i0:].ctypes.data, ids[i0:].ctypes.data,
+                                            pts.ctypes.data, cap_pts, offs.ctypes.data, rects.ctypes.data, scores.ctypes.data, cap,
+                                            counts.ctypes.data, over.ctypes.data, int(threads)))
+        out = []
+        for j in range(m):
+            k = int(counts[j])
+            if over[j]:
+                out.append(None)
+                continue
+            o = offs[j]
+            out.append(([pts[j, o[b]:o[b + 1]].copy() for b in range(k)], rects[j, :k].copy(), scores[j, :k].copy()))
+        return out, over
+
+    res, over = call(0, n, cap_pts)
+    for j in np.nonzero(over)[0]:          # the page's polygons did not fit: redo it alone with the room it asked for
+        res[j] = call(int(j), int(j) + 1, int(over[j]))[0][0]
+    return res
+
 class DBComponents:
     """Device half of DB post-processing for a fixed page geometry: ``run(prob)`` thresholds DEVICE maps [n,H,W] and labels their
     8-connected components (``ocrvi_db_components``), leaving in HBM the 1-bit mask, the component table and the probability values
@@ -366,3 +421,15 @@ def detect_and_recognize(original_image, det_model, rec_model, post_processor: D
             batch[idx] = preprocess_crops(page[None], live, rec_size)
         texts.extend(rec_model.decode_greedy(batch))
     return rescaled, scores, texts
+
+
+def detect_and_recognize_pages(images, det_model, rec_model, post_processor: DBPostProcessor, device: str = "cuda:0", det_size: int = 640,
+                               rec_size: Tuple[int, int] = (32, 256), rec_batch_size: int = 64):
+    """``detect_and_recognize`` for a list of pages of any sizes in one call: a one-shot ``engine.Engine`` (pages bucketed by detector
+    shape, detector chunks and recogniser batches across pages).  ``det_model`` / ``rec_model`` are the library's DBNetPP / SVTRv2 on
+    ``device``.  Returns [(rescaled_boxes, scores, texts) per page, in input order], each what ``detect_and_recognize`` returns for that
+    page alone."""
+    from .engine import Engine
+    if torch.device(device).type != "cuda" or _dev_index(device) != det_model._dev_index():
+        raise ValueError(f"models live on cuda:{det_model._dev_index()}, not {device}")
+    return Engine(det_model, rec_model, post_processor, det_size=det_size, rec_size=rec_size, rec_batch=rec_batch_size).run(images)

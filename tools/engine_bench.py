@@ -1,0 +1,156 @@
+#!/usr/bin/env python3
+"""Throughput of the batched engine (ocr_vi_invoice_amd.engine.Engine) on bench.py's synthetic invoices, and the fused page-table
+pre-processing kernel against the two-kernel path it replaces.  Prints ONE JSON line.
+
+  uniform   64 pages of 960x1280 at det_size 1280: the identity resize, bench.py's headline shape
+  mixed     64 pages drawn from five aspect ratios (A4 portrait, landscape, tall receipt, square, wide strip) at det_size 960
+  preproc   one 16-page chunk: ocrvi_resize_normalize_pages against ocrvi_resize_u8 per page + ocrvi_normalize_u8 (HIP events)
+
+Both runs use SVTRv2-base and DBNet++ with bench.py's seeded weights in f16x2, crops of 48x320 in batches of 256, det_chunk 16, and
+bench.py's map blend through ``prob_hook``: every page's ground-truth line boxes, scaled to its bucket and shrunk by the DB shrink rule,
+at 0.75 + 0.25 binary (elsewhere 0.25 binary).  Each ``run`` drains at its end (bench.py's timed region carries the recogniser's last
+partial batch over into the next step instead)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+MIXED = [(1754, 1240), (960, 1280), (1600, 600), (1000, 1000), (700, 1400)]
+
+
+def make_set(sizes, lines, det_size):
+    import numpy as np
+    import torch
+    from bench import shrink_box
+    from ocr_vi_invoice_amd import synth
+    from ocr_vi_invoice_amd.engine import plan_buckets
+    shapes, scales, _ = plan_buckets(sizes, det_size)
+    pages, kern = [], []
+    for i, ((h, w), (H, W), (sh, sw)) in enumerate(zip(sizes, shapes, scales)):
+        img, boxes = synth.make_invoice(i, h, w, lines)
+        pages.append(img)
+        k = np.zeros((1, H, W), np.float32)
+        for x, y, bw, bh in boxes:
+            x0, y0 = int(x * sw), int(y * sh)
+            bw, bh = int((x + bw) * sw) - x0, int((y + bh) * sh) - y0
+            if bw >= 4 and bh >= 4:
+                sx, sy, sw_, sh_ = shrink_box(x0, y0, bw, bh)
+                k[0, sy:sy + sh_, sx:sx + sw_] = 0.75
+        kern.append(torch.from_numpy(k).cuda())
+    return pages, kern
+
+
+def run_set(name, engine_kw, sizes, det_size, args, det, rec, pp):
+    import torch
+    from ocr_vi_invoice_amd import Engine
+    pages, kern = make_set(sizes, args.lines, det_size)
+
+    def hook(prob, idx):
+        torch.add(torch.stack([kern[i] for i in idx]), prob, alpha=0.25, out=prob)
+
+    eng = Engine(det, rec, pp, det_size=det_size, prob_hook=hook, **engine_kw)
+    for _ in range(args.warmup):
+        eng.run(pages)
+    ts, stats = [], []
+    for _ in range(args.steps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = eng.run(pages)
+        ts.append(time.perf_counter() - t0)
+        stats.append(dict(eng.stats))
+    ts.sort()
+    med = ts[len(ts) // 2]
+    st = stats[0]
+    per_stage = {k: round(sum(s[k] for s in stats) / len(stats) * 1e3, 2) for k in ("launch_s", "det_wait_s", "post_s", "rec_wait_s", "total_s")}
+    del eng
+    torch.cuda.empty_cache()
+    return {"set": name, "det_size": det_size, "pages": len(pages), "pages_per_s": round(len(pages) / med, 3), "ms_per_run_median": round(med * 1e3, 2),
+            "ms_per_run_min_max": [round(ts[0] * 1e3, 2), round(ts[-1] * 1e3, 2)], "buckets": st["buckets"], "crops": st["crops"],
+            "rec_batches": st["rec_batches"], "boxes_per_page_min_max": [min(len(o[0]) for o in out), max(len(o[0]) for o in out)],
+            "host_ms_per_run": {k.replace("_s", ""): v for k, v in per_stage.items()},
+            "host_stage_note": "launch = staging (host copy into pinned memory) + enqueue; det_wait / rec_wait = host blocked on the device; "
+                               "post = ocrvi_db_boxes_pages"}
+
+
+def time_preproc(iters=50):
+    """16-page chunk: the fused kernel against resize_u8 per page + normalize_u8 on the chunk, for three source sizes."""
+    import numpy as np
+    import torch
+    from ocr_vi_invoice_amd import _lib, synth
+    lib = _lib.load()
+    H, W, n = 960, 1280, 16
+    out = []
+    for src_h, src_w, dst_w in ((960, 1280, 1280), (1920, 2560, 1280), (1754, 1240, 672)):
+        img = torch.from_numpy(synth.make_invoice(1, src_h, src_w, 30)[0]).cuda()
+        pages = [img.clone() for _ in range(n)]
+        tab = torch.from_numpy(np.asarray([(p.data_ptr(), src_h, src_w, 0) for p in pages], np.int64)).cuda()
+        x = torch.empty((n, 3, H, dst_w), device="cuda")
+        u8 = torch.empty((n, H, dst_w, 3), dtype=torch.uint8, device="cuda")
+        st = torch.cuda.current_stream().cuda_stream
+
+        def fused():
+            _lib.check(lib.ocrvi_resize_normalize_pages(0, tab.data_ptr(), n, H, dst_w, x.data_ptr(), st))
+
+        def two():
+            for i, p in enumerate(pages):
+                _lib.check(lib.ocrvi_resize_u8(0, p.data_ptr(), src_h, src_w, u8[i].data_ptr(), H, dst_w, st))
+            _lib.check(lib.ocrvi_normalize_u8(0, u8.data_ptr(), n, H, dst_w, x.data_ptr(), st))
+
+        res = {"src": f"{src_h}x{src_w}", "dst": f"{H}x{dst_w}", "pages": n}
+        for name, fn in (("fused", fused), ("two_kernel", two)):
+            for _ in range(3):
+                fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            e1.synchronize()
+            ms = e0.elapsed_time(e1) / iters
+            res[name + "_ms"] = round(ms, 4)
+        wbytes = n * H * dst_w * 12                            # fp32 planes: what dominates
+        res["fused_write_gbs"] = round(wbytes / (res["fused_ms"] / 1e3) / 1e9, 1)
+        res["speedup"] = round(res["two_kernel_ms"] / res["fused_ms"], 3)
+        out.append(res)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--pages", type=int, default=64)
+    ap.add_argument("--lines", type=int, default=30)
+    ap.add_argument("--dtype", default="f16x2", choices=["f32", "f16x2", "bf16", "f16"])
+    ap.add_argument("--sets", default="uniform,mixed,preproc")
+    args = ap.parse_args()
+    import torch
+    from ocr_vi_invoice_amd import DBNetPP, SVTRv2, weights
+    from ocr_vi_invoice_amd.pipeline import DBPostProcessor
+    assert torch.cuda.is_available(), "engine_bench needs a GPU"
+    torch.cuda.set_device(0)
+    sets = args.sets.split(",")
+    res = {"tool": "engine_bench", "dtype": args.dtype, "steps": args.steps, "warmup": args.warmup}
+    if "preproc" in sets:
+        res["preproc"] = time_preproc()
+    if "uniform" in sets or "mixed" in sets:
+        det = DBNetPP(pretrained=False, state_dict=weights.make_det_state_dict(seed=1234), dtype=args.dtype)
+        rec = SVTRv2("base", state_dict=weights.make_rec_state_dict("base", seed=1234), dtype=args.dtype)
+        pp = DBPostProcessor(thresh=0.3, box_thresh=0.5, max_candidates=1000, unclip_ratio=1.6)
+        kw = dict(rec_size=(48, 320), det_chunk=16, rec_batch=256)
+        runs = []
+        if "uniform" in sets:
+            runs.append(run_set("uniform 960x1280", kw, [(960, 1280)] * args.pages, 1280, args, det, rec, pp))
+        if "mixed" in sets:
+            sizes = [MIXED[i % len(MIXED)] for i in range(args.pages)]
+            runs.append(run_set("mixed " + ",".join(f"{h}x{w}" for h, w in MIXED), kw, sizes, 960, args, det, rec, pp))
+        res["runs"] = runs
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()
