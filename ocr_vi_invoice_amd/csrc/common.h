@@ -284,9 +284,7 @@ template <> struct Mma<f16x2_t> {   // operands are chunks [4 hi | 4 lo]: hh + l
         // (register vectors, not uint4 structs: with the structs hipcc kept fragment arrays in scratch memory to form the swapped operand)
         const u4v av = {a.x, a.y, a.z, a.w}, bv = {b.x, b.y, b.z, b.w};
         const u4v as = __builtin_shufflevector(av, av, 2, 3, 0, 1);
-#ifndef OCRVI_TIMING_HALF_MFMA   /* timing experiment only (results are wrong): what the kernels would cost with half the matrix work */
         c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, as), __builtin_bit_cast(f16x8, bv), c, 0, 0, 0);
-#endif
         c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, av), __builtin_bit_cast(f16x8, bv), c, 0, 0, 0);
     }
     __device__ static inline void run(const uint4 (&a)[2], const uint4 (&b)[2], f32x4& c) {

@@ -54,7 +54,6 @@ struct ConvParams {
     int res_in_store = 0;  // fp32 out + fp32 residual, no activation: add the residual in the coalesced store phase
     int patch_lw = 7;      // dcn_pipe: a tile is a (128 >> patch_lw) x (1 << patch_lw) patch of output pixels
     unsigned out_bytes = 0;   // gemm_ring: bytes of the output tensor the stores may touch (buffer descriptor range; filled by launch_gemm_ring)
-    int nt_out = 0;        // gemm_ring / gemm_duo: non-temporal output stores (set by the launcher for N >= 2 K)
     float wscale = 1.f;    // f16x2: the weights are stored multiplied by 2^s (one power of two per layer, chosen by the packer so that their
                            // lo halves are normal fp16 numbers); every epilogue multiplies the accumulator by wscale = 2^-s (exact)
 };
@@ -539,9 +538,7 @@ __global__ __launch_bounds__(256, (ConvOccT<T, AMODE, BM, BN>::value)) void conv
 
 // Tile choice shared by the packer (host) and the launcher.
 static inline int conv_bn_for(int n_g) {
-    static const int cap = getenv("OCRVI_CONV_BN") ? atoi(getenv("OCRVI_CONV_BN")) : 128;  // experiment knob (packing + launch agree)
-    const int bn = n_g > 64 ? 128 : (n_g > 32 ? 64 : 32);
-    return bn > cap ? cap : bn;
+    return n_g > 64 ? 128 : (n_g > 32 ? 64 : 32);
 }
 static inline int conv_bke(int dtype) { return dtype_size(dtype) == 4 ? 32 : 64; }   // elements per 128-byte K-step
 

@@ -8,7 +8,6 @@
 
 #include "conv_gemm.h"
 #include "gemm_ring.h"
-#include "gemm_duo.h"
 #include "gconv32.h"
 #include "dcn_pipe.h"
 #include "offs_conv.h"
@@ -96,14 +95,6 @@ int launch_gemm_ring(const ConvParams& p_in, int amode, hipStream_t stream) {
         const size_t osz = (sizeof(T) == 4 || p.out_f32) ? 4 : 2;
         p.out_bytes = (unsigned)(((size_t)(p.M - 1) * p.ldo + p.out_coff + p.N_g) * osz);
     }
-    {   // non-temporal output stores (OCRVI_RING_NT=1; off by default).  Alone on the chip a GEMM whose output outweighs its operands
-        // (N >= 2 K) runs 3-23 % faster with them (K 128 N 512 244 -> 188 us, K 256 N 1024 181 -> 153, K 384 N 1152 226 -> 208: the output
-        // no longer displaces the activation rows the other column tiles want from L2) -- but inside the models the next layer then
-        // misses what it would have found in L2 / the Infinity Cache, and the ring total of a bench step does not move (131.8 vs 131.7 ms;
-        // profiles/r04_duo.md section 3)
-        static const int force = getenv("OCRVI_RING_NT") ? atoi(getenv("OCRVI_RING_NT")) : 0;
-        p.nt_out = (force == 1 && sizeof(T) == 4 && p.N_g >= 2 * p.Kp && p.Kp >= 128) ? 1 : (force == 2 ? 1 : 0);
-    }
     int n_cu = 0;
     OCRVI_TRY(device_cus(&n_cu));
     const int bn = p.Np % 128 == 0 ? 128 : 64;  // 64-channel layers: a 256x64 tile (16-bit types only, checked by gemm_ring_eligible)
@@ -111,18 +102,15 @@ int launch_gemm_ring(const ConvParams& p_in, int amode, hipStream_t stream) {
     OCRVI_CHECK(ntiles >= 1 && ntiles <= n_cu && nk >= 1, OCRVI_EINVAL, "gemm_ring: Np=%d Kp=%d out of range", p.Np, p.Kp);
     // 256-row tiles (4 slice groups riding on the next tile's first 4 K-steps) when K is deep enough for that and M still gives every
     // CU work; otherwise 128-row tiles (one group)
-    static const bool mid = !(getenv("OCRVI_RING_MID") && atoi(getenv("OCRVI_RING_MID")) == 0);  // experiment knob
     const bool big_m = amode == AM_CONV3 || cdiv(p.M, 256) * ntiles >= 192;
     const bool f32o = sizeof(T) == 4 || p.out_f32;
     // nk = 2..3 with a 16-bit output: 256-row tiles with two slice groups of two slices (the fp32-output build of that shape spills)
-    const bool mid256 = mid && nk >= 2 && nk < 4 && !f32o && big_m && amode == AM_CONV1;
+    const bool mid256 = nk >= 2 && nk < 4 && !f32o && big_m && amode == AM_CONV1;
     // (fp32 GEMMs -- the parity mode -- stay on 128-row tiles: their 256-row build does not fit the register file without a spill)
     // (f16x2: 4-byte operands like fp32, but its 256-row build -- 255 VGPRs, no scratch -- fits, and the kernel is bound by the bytes it
     // streams per FLOP, not by the matrix pipe: 256 x 128 tiles move 2/3 of the bytes of 128 x 128 ones)
     const bool wide_ok = sizeof(T) == 2 || IsSplit<T>::value;
-    // (f16x2 3x3 mode: 128-row tiles -- the 256-row build with the 3x3 mode's per-piece pointers and tap masks needs 8 VGPRs more than a wave has)
-    const bool c3_x2 = IsSplit<T>::value && amode == AM_CONV3;
-    const int bm = bn == 64 ? 256 : ((wide_ok && !c3_x2 && ((nk >= 4 && big_m) || mid256)) ? 256 : 128);
+    const int bm = bn == 64 ? 256 : ((wide_ok && ((nk >= 4 && big_m) || mid256)) ? 256 : 128);
     // one persistent workgroup per CU; a workgroup keeps its column tile, so the grid is Gm row-tile lanes x ntiles, with Gm chosen
     // for equal row-tile counts
     const int mtiles = cdiv(p.M, bm);
@@ -139,9 +127,6 @@ int launch_gemm_ring(const ConvParams& p_in, int amode, hipStream_t stream) {
     }
     if constexpr (sizeof(T) == 2 || IsSplit<T>::value) {
         if (bm == 256) return launch_ring_cfg<T, 256, 8, 1>(p, amode, grid, stream);
-    }
-    if constexpr (IsSplit<T>::value) {
-        if (amode == AM_CONV3) return launch_ring_f<T, 128, 8, 2, true, true>(p, grid, stream);
     }
     return launch_ring_cfg<T, 128, 8, 2>(p, amode, grid, stream);  // MI = 2: one group
 }
@@ -187,10 +172,9 @@ int launch_conv(const ConvParams& p_in, int amode, hipStream_t stream) {
     p.mg_oh = ((1ull << 40) / (unsigned long long)p.OH) + 1;
     p.identity_pix = (amode == AM_CONV1 && p.SH == 1 && p.SW == 1 && p.PH == 0 && p.PW == 0 && p.H == p.OH && p.W == p.OW &&
                       p.store_mode == ST_NHWC && p.res_mode != RES_UP2) ? 1 : 0;
-    {   // coalesced LDS-staged epilogue whenever 16-byte row chunks are aligned (A/B switch: OCRVI_CONV_EPI=direct)
-        static const bool direct = getenv("OCRVI_CONV_EPI") && !strcmp(getenv("OCRVI_CONV_EPI"), "direct");
+    {   // coalesced LDS-staged epilogue whenever 16-byte row chunks are aligned
         const int osz = (p.out_f32 || sizeof(T) == 4) ? 4 : 2, per = 16 / osz;
-        p.epi_lds = (!direct && p.store_mode == ST_NHWC && p.res_mode != RES_UP2 && p.N_g % per == 0 && p.ldo % per == 0 &&
+        p.epi_lds = (p.store_mode == ST_NHWC && p.res_mode != RES_UP2 && p.N_g % per == 0 && p.ldo % per == 0 &&
                      p.out_coff % per == 0 && ((uintptr_t)p.out & 15) == 0) ? 1 : 0;
         // (raw fp32 on both sides: an fp32 model, or fp32 output AND fp32 residual of a 16-bit / f16x2 one)
         const bool raw32 = IsF32<T>::value || (p.out_f32 && p.res_f32);
@@ -233,9 +217,6 @@ int launch_conv(const ConvParams& p_in, int amode, hipStream_t stream) {
     if (offs_conv_eligible(p, amode, TypeInfo<T>::dtype)) return launch_offs_conv<T>(p, stream);
     if constexpr (IsSplit<T>::value) {
         if (conv3_halo_eligible(p, amode, TypeInfo<T>::dtype)) return launch_conv3_halo<T>(p, stream);
-    }
-    if constexpr (IsSplit<T>::value) {
-        if (gemm_duo_eligible(p, amode, TypeInfo<T>::dtype)) return launch_gemm_duo<T>(p, stream);
     }
     if (gemm_ring_eligible(p, amode, TypeInfo<T>::dtype)) return launch_gemm_ring<T>(p, amode, stream);
     switch (amode) {

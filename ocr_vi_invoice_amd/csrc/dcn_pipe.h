@@ -29,11 +29,7 @@ __global__ __launch_bounds__(512, 2) void dcn_pipe_kernel(const ConvParams p) {
     constexpr int WST = BN * 128, SLAB = BM * 128;
     constexpr int NI = BN / 32;            // 16-channel MFMA blocks per wave (BN / 2 channels)
     constexpr int GW = BN / 64;            // weight DMA instructions per wave per stage (BN / 8 pieces over 8 waves)
-#ifdef OCRVI_TIMING_DCN_ONEC                // (development, timing only: one corner load per item instead of four -- wrong results)
-    constexpr int GG = 2;
-#else
     constexpr int GG = 8;                  // gather loads per lane per step: 2 (row, chunk) items x 4 corners
-#endif
     static_assert(BN == 128 || BN == 256, "column tile");
     constexpr bool PERM = sizeof(T) == 2;               // 16-bit output: weight rows permuted so a lane ends with 8 consecutive channels
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -126,12 +122,6 @@ __global__ __launch_bounds__(512, 2) void dcn_pipe_kernel(const ConvParams p) {
                 const int xc0 = min(max(x0, 0), p.W - 1), xc1 = min(max(x1, 0), p.W - 1);
                 ov = ((unsigned)(img * p.H * p.W + yc0 * p.W + xc0) * (unsigned)rowb) | (unsigned)(xc1 - xc0) | ((unsigned)(yc1 - yc0) << 1);
             }
-#ifdef OCRVI_TIMING_DCN_NEAR   // (development, timing only: every sample reads its own output pixel's neighbourhood -- the gathers hit L1)
-            if (m >= 0) {
-                const int oh = min(oh0 + (row >> lw), p.OH - 1) * p.SH, ow = min(ow0 + (row & (PW - 1)), p.OW - 1) * p.SW;
-                ov = ((unsigned)(img * p.H * p.W + min(oh, p.H - 2) * p.W + min(ow, p.W - 2)) * (unsigned)rowb) | 3u;
-            }
-#endif
             Gw[i] = wv;
             Go[i] = ov;
         }
@@ -163,11 +153,9 @@ __global__ __launch_bounds__(512, 2) void dcn_pipe_kernel(const ConvParams p) {
                 const unsigned o00 = (ov & ~3u) + coff, dxo = (ov & 1u) ? (unsigned)rowb : 0u, dyo = (ov & 2u) ? (unsigned)(rowb * p.W) : 0u;
                 S.w[it][0] = wv.x; S.w[it][1] = wv.y; S.w[it][2] = wv.z; S.w[it][3] = wv.w;
                 gload16s(S.c[it][0], xbase, o00);
-#ifndef OCRVI_TIMING_DCN_ONEC
                 gload16s(S.c[it][1], xbase, o00 + dxo);
                 gload16s(S.c[it][2], xbase, o00 + dyo);
                 gload16s(S.c[it][3], xbase, o00 + dyo + dxo);
-#endif
             }
         };
         auto blend = [&](int ks, GSet& S) {  // fp32 blend of step ks -> slab ks & 1
@@ -176,9 +164,6 @@ __global__ __launch_bounds__(512, 2) void dcn_pipe_kernel(const ConvParams p) {
             for (int it = 0; it < 2; ++it) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) bind16(S.c[it][q]);
-#ifdef OCRVI_TIMING_DCN_ONEC
-                S.c[it][1] = S.c[it][2] = S.c[it][3] = S.c[it][0];
-#endif
                 float acc[EPC], f[EPC];
 #pragma unroll
                 for (int e = 0; e < EPC; ++e) acc[e] = 0.f;

@@ -67,16 +67,7 @@ __device__ __forceinline__ void gload16s(u32x4& dst, const char* sbase, unsigned
 }
 template <int N> __device__ __forceinline__ void wait_vm_only() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ void bind16(u32x4& r) { asm volatile("" : "+v"(r)); }  // every later use of r is ordered after this point
-// (development: -DOCRVI_TIMING_RING_NOLDS replaces the fragment reads of the f16x2 ring by undefined registers -- wrong results, timing only)
-__device__ __forceinline__ uint4 lds16(const char* p) {
-#ifdef OCRVI_TIMING_RING_NOLDS
-    u32x4 v;
-    asm volatile("" : "=v"(v));
-    return make_uint4(v.x, v.y, v.z, v.w);
-#else
-    return *(const uint4*)p;
-#endif
-}
+__device__ __forceinline__ uint4 lds16(const char* p) { return *(const uint4*)p; }
 
 // Epilogue layout.  fp32 output: MFMA block a is channels 16a .. 16a+15, lane (lr, g) holds 4 consecutive ones -> a 16-byte access
 // per lane, 64 contiguous bytes per pixel row per instruction.  16-bit output: the weight fragment of block a reads tile row
@@ -180,11 +171,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_ring_kernel(const ConvPa
                 a_off[i] = (unsigned)((img * p.H + oh * p.SH) * p.W + ow * p.SW) * (unsigned)lda_b + chunk * 16;
             }
         } else {
-#ifdef OCRVI_TIMING_RING_AWRAP   // (development, timing only: every row tile reads one of four -- the activations stay in L2)
-            a_tile = uniform_ptr(A + (size_t)(mt & 3) * BM * lda_b);
-#else
             a_tile = uniform_ptr(A + (size_t)mt * BM * lda_b);
-#endif
             const int last = p.M - 1 - mt * BM;                   // last valid row of this tile
 #pragma unroll
             for (int i = 0; i < NA; ++i) a_off[i] = (unsigned)(min((i * NW + wave) * 8 + prow, last) * lda_b + chunk * 16);
@@ -368,11 +355,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_ring_kernel(const ConvPa
 #pragma unroll
         for (int j = 0; j < SPS; ++j) {
             const int m = pmt * BM + wm * TM + (q0 + j) * 16 + lr;
-#ifdef OCRVI_TIMING_RING_OWRAP   // (development, timing only: the output rows wrap at 2048 -- the stores stay in L2)
-            const unsigned row_b = m < p.M ? ((unsigned)(m & 2047) * (unsigned)p.ldo + (unsigned)(p.out_coff + nb)) * (unsigned)osz_b : OOB;
-#else
             const unsigned row_b = m < p.M ? ((unsigned)m * (unsigned)p.ldo + (unsigned)(p.out_coff + nb)) * (unsigned)osz_b : OOB;
-#endif
             if constexpr (F32O) {
 #pragma unroll
                 for (int a = 0; a < NI; ++a) {
@@ -399,10 +382,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_ring_kernel(const ConvPa
                     } else {
                         pk = (u32x4){__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
                     }
-                    // (nt: an output that outweighs the operands -- N >= 2 K -- written with the default policy pushes the activation rows the other
-                    // column tiles still want out of the XCD's L2; launch_gemm_ring sets the flag)
-                    if (p.nt_out) __builtin_amdgcn_raw_buffer_store_b128(pk, orsrc, off, 0, 2);
-                    else __builtin_amdgcn_raw_buffer_store_b128(pk, orsrc, off, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(pk, orsrc, off, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             } else {
@@ -488,9 +468,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_ring_kernel(const ConvPa
         // the previous step's stores (its residual loads were consumed, hence complete; VMEM ops retire in issue order).
         auto wait_stage = [&](auto NN) {
             constexpr int N = decltype(NN)::value;
-#ifdef OCRVI_TIMING_RING_NOBAR   // (development: no barrier -- races, timing only)
-            wait_vm_only<N>();
-#else
             if constexpr (PROF) {   // the wave's own DMA pieces (slot 4 of the report), then the workgroup (slot 0)
                 wait_vm_only<N>();
                 tick(4);
@@ -498,7 +475,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void gemm_ring_kernel(const ConvPa
             } else {
                 wait_vm_barrier<N>();
             }
-#endif
         };
         if (AHEAD > 1 && s + 1 < nsteps) {
             if (!stored) wait_stage(IC<G>{}); else wait_stage(IC<G + SG>{});

@@ -11,7 +11,6 @@
 
 #include "conv_gemm.h"
 #include "gemm_ring.h"
-#include "gemm_duo.h"
 #include "dcn_pipe.h"
 
 namespace ocrvi {
@@ -232,8 +231,7 @@ bool gemm_ring_eligible(const ConvParams& p, int amode, int dtype) {
     if (!on || p.groups != 1 || p.store_mode != ST_NHWC) return false;
     const int esz = (int)dtype_size(dtype), bke = conv_bke(dtype);
     if (amode == AM_CONV3) {  // 3x3 / stride 1 / pad 1 on the ring: 16-bit types, whole channel blocks per tap, 256-row tiles
-        static const bool x2c3 = getenv("OCRVI_RING_CONV3_X2") && atoi(getenv("OCRVI_RING_CONV3_X2"));   // experiment: f16x2 3x3 on the ring's 128-row build
-        if (!on3 || !(esz == 2 || (x2c3 && dtype == OCRVI_F16X2)) || (p.out_f32 && esz == 2) || p.KH != 3 || p.SH != 1 || p.SW != 1 || p.PH != 1 || p.PW != 1 || p.H != p.OH || p.W != p.OW) return false;
+        if (!on3 || esz != 2 || p.out_f32 || p.KH != 3 || p.SH != 1 || p.SW != 1 || p.PH != 1 || p.PW != 1 || p.H != p.OH || p.W != p.OW) return false;
         // measured (profiles/r01_conv_variants.md): +5..9 % over conv_gemm at M >= 300 k rows, -12 % at 77 k (too few tiles per CU)
         static const int min_m = getenv("OCRVI_RING_CONV3_MIN_M") ? atoi(getenv("OCRVI_RING_CONV3_MIN_M")) : (1 << 18);
         if (p.Cin_g % bke != 0 || p.Kp != 9 * p.Cin_g || p.M < min_m || p.Np % 128 != 0) return false;  // (64-wide: conv_gemm is 6 % faster)
@@ -275,34 +273,6 @@ bool conv3_halo_eligible(const ConvParams& p, int amode, int dtype) {
     if (p.act != ACT_NONE && p.act != ACT_RELU) return false;
     if (p.Cin % 4 != 0 || p.cin_off % 4 != 0 || p.N_g % 4 != 0 || p.ldo % 4 != 0 || p.out_coff % 4 != 0) return false;
     return ((uintptr_t)p.x & 15) == 0 && ((uintptr_t)p.w & 15) == 0 && ((uintptr_t)p.out & 15) == 0;
-}
-
-// The duo ring GEMM (gemm_duo.h): f16x2 1x1 convolutions / Linears that gemm_ring would take, whose column count tiles by 256 or 192,
-// with at least four K-steps (below that the layers sit on their HBM roof in either kernel) and an epilogue variant that is built
-// (duo_f16x2.hip: launch_duo_ni).  The choice depends on the layer only (N, K, epilogue), never on M, so a page alone and the same page
-// inside a batch take the same kernel.  OFF by default (OCRVI_GEMM_DUO=1 enables it, read once per process): measured end to end it
-// ties gemm_ring (260.1 vs 260.5 invoices/s) -- 12-20 % faster at K <= 384 with N >= 1024 and no GELU, equal at long K, slower with GELU;
-// why (a wave alone on its SIMD drives the matrix pipe at about half the rate two waves reach together, so the "solo" MFMA steps beside
-// the other group's epilogue are no shorter than shared ones) is measured in profiles/r04_duo.md with tools/mfma_mix.hip.
-bool gemm_duo_eligible(const ConvParams& p, int amode, int dtype) {
-    // OCRVI_GEMM_DUO: unset / 0 never; 1 every shape the kernel takes (ties gemm_ring end to end: profiles/r04_duo.md); 2 only wide outputs on a
-    // short K with a plain epilogue -- the recogniser's qkv projections (N = 3 D >= 768, K = D <= 384): 17.6 against 18.6 ms per step there,
-    // nothing measurable end to end (293-297 invoices/s either way).  The kernels are bit-identical, so the choice is invisible in the results.
-    static const int mode = getenv("OCRVI_GEMM_DUO") ? atoi(getenv("OCRVI_GEMM_DUO")) : 0;
-    if (mode == 0 || dtype != OCRVI_F16X2 || amode != AM_CONV1) return false;
-    if (!gemm_ring_eligible(p, amode, dtype)) return false;
-    if (mode == 2 && !(p.Np >= 768 && p.Kp <= 384 && p.act == ACT_NONE && p.res_mode == RES_NONE && !p.out_f32 && p.SH == 1 && p.SW == 1)) return false;
-    static const int min_nk = getenv("OCRVI_DUO_MIN_NK") ? atoi(getenv("OCRVI_DUO_MIN_NK")) : 4;
-    if (duo_bn_for(p.Np) == 0 || p.Kp / 32 < min_nk) return false;
-    const int resk = p.res_mode == RES_NONE ? 0 : (p.res_f32 ? 1 : 2);
-    const bool of32 = p.out_f32 != 0;
-    // (GELU epilogues stay on gemm_ring: ~80 VALU instructions per fragment spread over the next tile's MFMA steps by the same wave beat
-    // epilogue steps beside the other group's MFMAs -- 326 vs 390 us at M 61440, K 384, N 1536; OCRVI_DUO_GELU=1 routes them here anyway)
-    static const bool gelu = getenv("OCRVI_DUO_GELU") && atoi(getenv("OCRVI_DUO_GELU"));
-    if (p.act == ACT_GELU && !gelu) return false;
-    if (resk == 0) return of32 ? p.act == ACT_NONE : true;
-    if (resk == 2) return !of32 && p.act != ACT_GELU;
-    return of32 && p.act == ACT_NONE;     // raw fp32 residual stream: fp32 output
 }
 
 int device_cus(int* n_cu) {
@@ -438,14 +408,11 @@ int launch_conv_dt(int dtype, const ConvParams& p, int amode, hipStream_t stream
         const bool ring = gemm_ring_eligible(q, amode, dtype);
         const bool pipe = amode == AM_DCN && dcn_pipe_eligible(q, dtype);
         static const bool detail = getenv("OCRVI_PROF_DETAIL") != nullptr;
-        const bool duo = gemm_duo_eligible(q, amode, dtype);
         const bool halo = conv3_halo_eligible(q, amode, dtype);
         if (halo && !detail)
             snprintf(tag, sizeof(tag), "conv3x3_halo_%s", dtype_name(dtype));
         else if (halo)
             snprintf(tag, sizeof(tag), "conv3x3_halo_%s M%d N%d K%d g%d s%d", dtype_name(dtype), p.M, p.N_g, (int)kvalid, p.groups, p.SH);
-        else if (duo && !detail)
-            snprintf(tag, sizeof(tag), "gemm_duo_%s", dtype_name(dtype));
         else if (ring && !detail)
             snprintf(tag, sizeof(tag), "gemm_ring_%s", dtype_name(dtype));
         else if (pipe && !detail)

@@ -35,9 +35,6 @@ struct MlpX2Params {
     const float* b1 = nullptr;     // [4D]
     const float* b2 = nullptr;     // [D]
     int M = 0;
-    int stagger = 0;               // shader cycles between the start phases of the workgroups (see the kernel)
-    int dbg = 0;                   // OCRVI_MLPX2_DBG (development, wrong results): 1 no x stores, 2 no xn stores, 4 no residual loads
-    unsigned long long* prof = nullptr;   // development (OCRVI_MLPX2_PROF=1): cycles per wave in unit wait+barrier / GEMM1 (+ GELU) / GEMM2 / tile epilogue / prologue / drain
 };
 
 // TB = 16-token blocks per wave: 1 -> 8 waves of 16 tokens (two per SIMD, 256 registers each); 2 -> 4 waves of 32 tokens (one per SIMD with the
@@ -108,22 +105,6 @@ __global__ __launch_bounds__(512 / TB, TB == 2 ? 1 : 2) void mlp_x2_kernel(const
         return s;
     };
     for (int i = 0; i < PF; ++i) issue_unit();
-    // (Experiment, OCRVI_MLPX2_STAGGER=cycles, off by default: four start phases `stagger` cycles apart, to test whether the tile epilogues of all
-    // CUs -- which fall into the same few microseconds -- starve each other of HBM bandwidth.  They do not: 12 k ... 60 k cycles of stagger only add
-    // their own delay; removing every load and store of the epilogue saves 7 %.  The epilogue's cost is its ~1 300 vector instructions.)
-    if (p.stagger > 0) {
-        const long long until = clock64() + (long long)(blockIdx.x & 3) * p.stagger;
-        while (clock64() < until) __builtin_amdgcn_s_sleep(64);
-    }
-
-    long long tk[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tk0 = p.prof ? clock64() : 0;
-    auto tick = [&](int k) {
-        if (p.prof) {
-            const long long c = clock64();
-            tk[k] += c - tk0;
-            tk0 = c;
-        }
-    };
     const int sw = swz128(lr);
     const int fo0 = ((2 * g) ^ sw) << 4, fo1 = ((2 * g + 1) ^ sw) << 4;   // hi / lo quartet of this lane's 8 k-slots in a [row][128 B] image
     unsigned long long range_mask = 0;
@@ -176,11 +157,9 @@ __global__ __launch_bounds__(512 / TB, TB == 2 ? 1 : 2) void mlp_x2_kernel(const
                 Mma<T>::regroup(c0, c1, xH[ks][b], xL[ks][b]);
             }
         }
-        tick(4);
         // every VMEM op issued so far by this wave (ring DMAs, the previous tile's stores, the loads above) has completed: the counted
         // waits of the main loop start from the DMAs issued from here on (any older unit has landed)
         wait_vm_only<0>();
-        tick(5);
 
         f32x4 acc2[NB2][TB];
 #pragma unroll
@@ -280,37 +259,35 @@ __global__ __launch_bounds__(512 / TB, TB == 2 ? 1 : 2) void mlp_x2_kernel(const
         // the fc2 slice of a stream unit: behind its fc1 slice in the same ring unit, or (SPLIT) the next ring unit
         auto second = [&](const char* U1) -> const char* {
             if constexpr (SPLIT) {
-                const char* u = next_unit();
-                tick(0);
-                return u;
+                return next_unit();
             } else {
                 return U1 + W1B;
             }
         };
-        const float* const bias_g = c_b1 + 4 * g;
+        // GELU biases of chunk c.  The lane's offset is recomputed from an opaque copy of the thread index at each use, so that the register
+        // allocator does not carry it through the chunk loop (the D = 384 build, at 512 registers, spilled it there: a scratch load between
+        // the ring's counted waits)
+        auto bias_of = [&](int c) {
+            int l = threadIdx.x;
+            asm volatile("" : "+v"(l));
+            return c_b1 + 32 * c + 4 * ((l & 63) >> 4);
+        };
         {
             const char* const U1 = next_unit();
-            tick(0);
-            g1(U1, false, bias_g);
-            tick(1);
+            g1(U1, false, bias_of(0));
             (void)second(U1);    // (the fc2 half of stream unit 0 is zeros: nothing to multiply yet)
         }
         keep();
         for (int k = 1; k < NCH; ++k) {
             const char* const U1 = next_unit();
-            tick(0);
-            g1(U1, true, bias_g + 32 * (k - 1));
-            tick(1);
+            g1(U1, true, bias_of(k - 1));
             g2(second(U1));
-            tick(2);
             keep();
         }
         {
             const char* const U1 = next_unit();   // (its fc1 half is zeros)
-            tick(0);
-            gelu_vals(0, NV, bias_g + 32 * (NCH - 1));
+            gelu_vals(0, NV, bias_of(NCH - 1));
             g2(second(U1));
-            tick(2);
         }
 
         // ---- epilogue: x <- x + fc2(..) + b2, then the optional next norm / cast.  The MFMA leaves lane 16 g + lr with channels 16 a + 4 g .. + 4 of
@@ -335,8 +312,7 @@ __global__ __launch_bounds__(512 / TB, TB == 2 ? 1 : 2) void mlp_x2_kernel(const
             // branch and its own vmcnt(0), and x is read and written through the same pointer)
             float4 rvs[NB2];
 #pragma unroll
-            for (int a = 0; a < NB2; ++a) rvs[a] = (p.dbg & 4) ? make_float4(0.f, 0.f, 0.f, 0.f) : *(const float4*)(xr + 16 * a);
-            if (p.prof) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); tick(6); }
+            for (int a = 0; a < NB2; ++a) rvs[a] = *(const float4*)(xr + 16 * a);
 #pragma unroll
             for (int a = 0; a < NB2; ++a) {
                 const float4 bv2 = *(const float4*)(c_b2 + 16 * a + 4 * pn_g);
@@ -344,10 +320,9 @@ __global__ __launch_bounds__(512 / TB, TB == 2 ? 1 : 2) void mlp_x2_kernel(const
                 f32x4 v = acc2[a][b];
                 v[0] = v[0] * ws2 + bv2.x + rv.x; v[1] = v[1] * ws2 + bv2.y + rv.y; v[2] = v[2] * ws2 + bv2.z + rv.z; v[3] = v[3] * ws2 + bv2.w + rv.w;
                 acc2[a][b] = v;
-                if (ok && !(p.dbg & 1)) *(float4*)(xr + 16 * a) = make_float4(v[0], v[1], v[2], v[3]);
+                if (ok) *(float4*)(xr + 16 * a) = make_float4(v[0], v[1], v[2], v[3]);
                 sum += v[0] + v[1] + v[2] + v[3];
             }
-            tick(7);
             if (p.xn) {
                 float mean = 0.f, rstd = 1.f;
                 if (next_ln) {      // a token's D values sit in the four lanes of a quad
@@ -363,7 +338,6 @@ __global__ __launch_bounds__(512 / TB, TB == 2 ? 1 : 2) void mlp_x2_kernel(const
                     sq += __shfl_xor(sq, 2);
                     rstd = rsqrtf(sq / (float)D + 1e-5f);
                 }
-                tick(8);
                 T* nr = (T*)p.xn + (size_t)(ok ? tok : 0) * D + 4 * pn_g;
 #pragma unroll
                 for (int a = 0; a < NB2; ++a) {
@@ -372,16 +346,13 @@ __global__ __launch_bounds__(512 / TB, TB == 2 ? 1 : 2) void mlp_x2_kernel(const
                     const float o[4] = {(v[0] - mean) * rstd * gv.x + bvn.x, (v[1] - mean) * rstd * gv.y + bvn.y, (v[2] - mean) * rstd * gv.z + bvn.z,
                                         (v[3] - mean) * rstd * gv.w + bvn.w};
                     range_mask |= f16x2_out_of_range(o);
-                    if (ok && !(p.dbg & 2)) *(uint4*)(nr + 16 * a) = Chunk<T>::pack(o);
+                    if (ok) *(uint4*)(nr + 16 * a) = Chunk<T>::pack(o);
                 }
             }
         }
-        tick(3);
     }
     wait_vm_only<0>();  // the ring's run-ahead fetches
     f16x2_raise(range_mask);
-    if (p.prof && lane == 0)
-        for (int k = 0; k < 9; ++k) atomicAdd(p.prof + k, (unsigned long long)tk[k]);
 }
 
 // ---------------------------------------------------------------- host: packing + launch
@@ -457,29 +428,7 @@ static int launch_mlp_x2(const MlpX2Params& p, hipStream_t s) {
     const int ntiles = (p.M + 127) / 128;
     int grid = std::min(ntiles, n_cu);
     grid = cdiv(ntiles, cdiv(ntiles, grid));  // equal tile counts
-    static const int stagger_env = getenv("OCRVI_MLPX2_STAGGER") ? atoi(getenv("OCRVI_MLPX2_STAGGER")) : -1;
-    MlpX2Params ps = p;
-    ps.stagger = stagger_env > 0 ? stagger_env : 0;   // (experiment, off: see the kernel)
-    static const int dbg_env = getenv("OCRVI_MLPX2_DBG") ? atoi(getenv("OCRVI_MLPX2_DBG")) : 0;
-    ps.dbg = dbg_env;
-    static const bool prof = getenv("OCRVI_MLPX2_PROF") && atoi(getenv("OCRVI_MLPX2_PROF"));
-    if (prof) {   // development: phase cycles, printed per launch (synchronises)
-        static unsigned long long* dbuf = nullptr;
-        if (!dbuf) OCRVI_HIP(hipMalloc((void**)&dbuf, 72));
-        OCRVI_HIP(hipMemsetAsync(dbuf, 0, 72, s));
-        MlpX2Params q = ps;
-        q.prof = dbuf;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512 / TB), smem, s, q);
-        unsigned long long h[9];
-        OCRVI_HIP(hipMemcpyAsync(h, dbuf, 72, hipMemcpyDeviceToHost, s));
-        OCRVI_HIP(hipStreamSynchronize(s));
-        const double wv = (8.0 / TB) * grid, units = (double)ntiles / grid * (4 * D / 32 + 1);
-        fprintf(stderr, "mlp_x2 D %d TB %d split %d M %d grid %d: cycles per wave and stream unit: wait + barrier %.0f, GEMM1 (+ GELU) %.0f, GEMM2 %.0f; per tile: epilogue (x loads %.0f, x update + stores %.0f, statistics %.0f, xn %.0f), prologue (loads + LayerNorm) %.0f, drain %.0f\n", D, TB,
-                (int)SPLIT, p.M, grid, h[0] / wv / units, h[1] / wv / units, h[2] / wv / units, h[6] / wv / ((double)ntiles / grid), h[7] / wv / ((double)ntiles / grid), h[8] / wv / ((double)ntiles / grid), h[3] / wv / ((double)ntiles / grid),
-                h[4] / wv / ((double)ntiles / grid), h[5] / wv / ((double)ntiles / grid));
-        return OCRVI_OK;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512 / TB), smem, s, ps);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512 / TB), smem, s, p);
     OCRVI_HIP(hipGetLastError());
     return OCRVI_OK;
 }
@@ -493,9 +442,8 @@ int k_mlp_x2(float* x, void* xn, const float* ln_g, const float* ln_b, const flo
     char tag[64];
     snprintf(tag, sizeof(tag), "mlp_fused_d%d_f16x2", D);
     ProfScope ps(tag, 2.0 * M * 8.0 * D * D, (double)M * D * (8.0 + (xn ? 4.0 : 0.0)) + 8.0 * D * D * 4.0, s);
-    static const int tb2 = getenv("OCRVI_MLPX2_TB2") ? atoi(getenv("OCRVI_MLPX2_TB2")) : 0;   // (A/B: the 4-wave layout at D <= 256 too)
-    if (D == 128) return tb2 ? launch_mlp_x2<128, 8, 2, true>(p, s) : launch_mlp_x2<128, 4, 1, false>(p, s);
-    if (D == 256) return tb2 ? launch_mlp_x2<256, 4, 2, true>(p, s) : launch_mlp_x2<256, 2, 1, false>(p, s);
+    if (D == 128) return launch_mlp_x2<128, 4, 1, false>(p, s);
+    if (D == 256) return launch_mlp_x2<256, 2, 1, false>(p, s);
     return launch_mlp_x2<384, 3, 2, true>(p, s);
 }
 

@@ -47,7 +47,7 @@ static_assert(SP_NPX <= 256 && SP_NPX > 240, "sixteen MFMA blocks");
 // y [N][OH][OW][64] f16x2 with OH = H / 4, OW = W / 4 (H, W = the image; the conv map is H / 2 x W / 2)
 __global__ __launch_bounds__(512, 2) void stem_pool_kernel(const char* __restrict__ xpad, const char* __restrict__ w, const float* __restrict__ bias,
                                                           float wscale, char* __restrict__ y, int N, int CH, int CW, int OH, int OW, int Hp,
-                                                          int Wp, int tyN, int txN, int dbg, unsigned long long* __restrict__ prof) {
+                                                          int Wp, int tyN, int txN) {
     typedef f16x2_t T;
     typedef Mma<T>::u4v U;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -120,14 +120,6 @@ __global__ __launch_bounds__(512, 2) void stem_pool_kernel(const char* __restric
     // Two barriers per tile: [MFMAs of tile t from the patch, results -> staging] | A | [patch of tile t + 1 -> LDS, loads of tile t + 2's
     // patch issued, max-pool of tile t from the staging -> global] | B.  (A: every wave is done reading the patch and writing the staging;
     // B: the next patch is complete and the staging is free.)
-    long long tk[6] = {0, 0, 0, 0, 0, 0}, tk0 = 0;   // (OCRVI_STEM_DBG & 8: shader-clock cycles per phase, summed over the waves into prof[])
-    auto tick = [&](int k) {
-        if (dbg & 8) {
-            const long long c = clock64();
-            tk[k] += c - tk0;
-            tk0 = c;
-        }
-    };
     int t = xcd_remap(blockIdx.x, gridDim.x);
     const int G = (int)gridDim.x;
     {
@@ -140,7 +132,6 @@ __global__ __launch_bounds__(512, 2) void stem_pool_kernel(const char* __restric
         pre0 = fetch1(tn, 0); pre1 = fetch1(tn, 1); pre2 = fetch1(tn, 2);
     }
     __syncthreads();   // (also: the weights are in LDS)
-    if (dbg & 8) tk0 = clock64();
     for (; t < total; t += G) {
         int img, py0, px0;
         tile_of(t, img, py0, px0);
@@ -151,7 +142,7 @@ __global__ __launch_bounds__(512, 2) void stem_pool_kernel(const char* __restric
         for (int a = 0; a < 4; ++a) acc[a][0] = acc[a][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
         // (software-pipelined by hand: the 12 fragment reads of filter row r + 1 are issued before the 24 MFMAs of row r -- left to itself
         // hipcc reads every weight fragment right in front of its first MFMA and waits for it, ~5 exposed LDS round trips per row)
-        if (!(dbg & 2)) {    // (OCRVI_STEM_DBG, development, wrong results: 1 no pooling pass, 2 no MFMA phase, 4 no staging writes)
+        {
             U xH[2][2], xL[2][2], wH[2][4], wL[2][4];
             auto load_row = [&](auto R, auto S) {
                 constexpr int r = decltype(R)::value, sl = decltype(S)::value;
@@ -188,13 +179,12 @@ __global__ __launch_bounds__(512, 2) void stem_pool_kernel(const char* __restric
             load_row(IC<0>{}, IC<0>{});
             row(IC<0>{}); row(IC<1>{}); row(IC<2>{}); row(IC<3>{}); row(IC<4>{}); row(IC<5>{}); row(IC<6>{});
         }
-        tick(0);
         // ---- bias + ReLU -> staging (fp32, 16-byte chunk c of pixel p at chunk c ^ (p & 15): conflict-free writes and pool reads);
         // conv pixels outside the map are -inf, the max-pool's padding value
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
             const int p = (wave * 2 + b) * 16 + lr;
-            if (!dup[b] && !(dbg & 4)) {
+            if (!dup[b]) {
                 const int i = p / SP_CC, j = p - i * SP_CC;
                 const int cr = 2 * py0 - 1 + i, cc = 2 * px0 - 1 + j;
                 const bool ok = (unsigned)cr < (unsigned)CH && (unsigned)cc < (unsigned)CW;
@@ -209,9 +199,7 @@ __global__ __launch_bounds__(512, 2) void stem_pool_kernel(const char* __restric
                 }
             }
         }
-        tick(1);
         __syncthreads();   // A
-        tick(2);
         put(0, pre0);
         put(1, pre1);
         put(2, pre2);
@@ -219,12 +207,11 @@ __global__ __launch_bounds__(512, 2) void stem_pool_kernel(const char* __restric
             const int tn = min(t + 2 * G, total - 1);
             pre0 = fetch1(tn, 0); pre1 = fetch1(tn, 1); pre2 = fetch1(tn, 2);
         }
-        tick(3);
         // ---- 3 x 3 / 2 max-pool over the staging -> f16x2, 56 pixels x 16 chunks of 4 channels
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             const int item = tid + 512 * k;
-            if (item < SP_PH * SP_PW * 16 && !(dbg & 1)) {
+            if (item < SP_PH * SP_PW * 16) {
                 const int q = item >> 4, c = item & 15;
                 const int qy = q / SP_PW, qx = q - qy * SP_PW;
                 const int py = py0 + qy, px = px0 + qx;
@@ -243,13 +230,9 @@ __global__ __launch_bounds__(512, 2) void stem_pool_kernel(const char* __restric
                 }
             }
         }
-        tick(4);
         __syncthreads();   // B
-        tick(5);
     }
     f16x2_raise(range_mask);
-    if ((dbg & 8) && prof && lane == 0)
-        for (int k = 0; k < 6; ++k) atomicAdd(prof + k, (unsigned long long)tk[k]);
 }
 
 bool stem_pool_eligible(int dtype, int cout, int Kp, int KH, int H, int W) {
@@ -270,26 +253,10 @@ int k_stem_pool(int dtype, const void* xpad, const void* w, const float* bias, f
     OCRVI_TRY(device_cus(&n_cu));
     const int total = N * tyN * txN;
     const int grid = cdiv(total, cdiv(total, std::min(total, n_cu)));   // one persistent workgroup per CU, equal tile counts
-    static const int dbg = getenv("OCRVI_STEM_DBG") ? atoi(getenv("OCRVI_STEM_DBG")) : 0;
     OCRVI_TRY(ensure_max_smem((const void*)stem_pool_kernel, SP_SMEM));
-    unsigned long long* prof = nullptr;
-    if (dbg & 8) {   // development: phase cycles, printed per launch (synchronises)
-        static unsigned long long* dbuf = nullptr;
-        if (!dbuf) OCRVI_HIP(hipMalloc((void**)&dbuf, 64));
-        OCRVI_HIP(hipMemsetAsync(dbuf, 0, 64, s));
-        prof = dbuf;
-    }
     hipLaunchKernelGGL(stem_pool_kernel, dim3(grid), dim3(512), SP_SMEM, s, (const char*)xpad, (const char*)w, bias, wscale, (char*)y, N, CH, CW, OH,
-                       OW, Hp, Wp, tyN, txN, dbg, prof);
+                       OW, Hp, Wp, tyN, txN);
     OCRVI_HIP(hipGetLastError());
-    if (prof) {
-        unsigned long long h[6];
-        OCRVI_HIP(hipMemcpyAsync(h, prof, 48, hipMemcpyDeviceToHost, s));
-        OCRVI_HIP(hipStreamSynchronize(s));
-        const double wv = 8.0 * grid, tiles = (double)total / grid;
-        fprintf(stderr, "stem_pool grid %d tiles/wg %.1f: cycles per wave and tile: mfma %.0f staging %.0f barrier A %.0f patch write + fetch issue %.0f pool %.0f barrier B %.0f\n",
-                grid, tiles, h[0] / wv / tiles, h[1] / wv / tiles, h[2] / wv / tiles, h[3] / wv / tiles, h[4] / wv / tiles, h[5] / wv / tiles);
-    }
     return OCRVI_OK;
 }
 

@@ -83,6 +83,29 @@ def test_product_package_never_imports_the_oracle():
                 assert not re.search(r"^\s*(from|import)\s+oracle\b", src, re.M), fn
 
 
+# Every environment switch the library reads (DESIGN.md section 3 lists the same names)
+LIBRARY_SWITCHES = (
+    # read once per process
+    "OCRVI_GEMM_RING", "OCRVI_RING_CONV3", "OCRVI_RING_CONV3_MIN_M", "OCRVI_GCONV32", "OCRVI_MLP_FUSED", "OCRVI_MLP_X2", "OCRVI_STEM_FUSED",
+    "OCRVI_ATTN_STREAM", "OCRVI_ATTN_F32_W8", "OCRVI_ATTN_X2_W8", "OCRVI_OFFS_DIRECT", "OCRVI_CONV3_HALO", "OCRVI_DCN_PIPE", "OCRVI_DCN_PIPE_F32",
+    # read per launch
+    "OCRVI_OFFS_TH", "OCRVI_DCN_TILE_M",
+    # development
+    "OCRVI_PROF_DETAIL", "OCRVI_RING_PROF", "OCRVI_TEST_PADC",
+)
+
+
+def test_library_reads_only_the_listed_switches_and_no_timing_macros():
+    csrc = os.path.join(REPO, "ocr_vi_invoice_amd", "csrc")
+    found, timing = set(), []
+    for fn in sorted(os.listdir(csrc)):
+        src = open(os.path.join(csrc, fn), encoding="utf-8").read()
+        found |= set(re.findall(r'getenv\("(OCRVI_[A-Z0-9_]*)"', src))
+        timing += [fn] if "OCRVI_TIMING_" in src else []
+    assert found == set(LIBRARY_SWITCHES), found ^ set(LIBRARY_SWITCHES)
+    assert not timing, timing
+
+
 def test_reference_trained_checkpoint_with_numpy_scalars_loads_weights_only(tmp_path):
     """The reference's trainers store numpy scalars next to model_state_dict (src/det/val.py:111-115 -> src/det/train.py:266-272): the
     plain weights-only unpickler rejects them, the allow-listed one must not -- and must still refuse anything executable."""

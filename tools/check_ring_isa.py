@@ -61,7 +61,7 @@ def touches_before_wait(body, start, dst):
     return hits
 
 
-ALL_SOURCES = ["conv_bf16.hip", "conv_f16.hip", "conv_f32.hip", "conv_f16x2.hip", "duo_f16x2.hip", "mlp_fused.hip", "attention.hip", "stem_pool.hip", "mlp_x2.hip"]
+ALL_SOURCES = ["conv_bf16.hip", "conv_f16.hip", "conv_f32.hip", "conv_f16x2.hip", "mlp_fused.hip", "attention.hip", "stem_pool.hip", "mlp_x2.hip"]
 _ASM = {}
 
 
@@ -120,23 +120,9 @@ OTHER_KERNELS = ["_ZN5ocrvi15dcn_pipe_kernel", "_ZN5ocrvi16offs_conv_kernel", "_
                  "_ZN5ocrvi14gconv32_kernel", "_ZN5ocrvi16attention_kernel", "_ZN5ocrvi18attention16_kernel", "_ZN5ocrvi16stem_pool_kernel"]
 
 
-def check_duo(src="duo_f16x2.hip"):
-    """The duo ring GEMM (gemm_duo.h): per kernel -- scratch instructions (must be 0), compiler-inserted vmcnt waits before the last inline-asm
-    statement (at most the one behind the bias loads), and uses of M0 outside inline asm (must be 0: a DMA piece sets M0 and leaves it)."""
-    rep = {}
-    for name, body in kernel_bodies(asm_of(src), "_ZN5ocrvi15gemm_duo_kernel").items():
-        last_asm = max((i for i, (t, a) in enumerate(body) if a), default=len(body))
-        rep[name] = dict(scratch=sum("scratch_" in t for t, _ in body), mfma=sum("v_mfma" in t for t, _ in body),
-                         compiler_vmcnt_waits=[t for i, (t, a) in enumerate(body) if not a and i < last_asm and t.startswith("s_waitcnt") and "vmcnt" in t],
-                         m0_uses=[t for t, a in body if not a and re.search(r"\bm0\b", t)])
-    return rep
-
-
 def check_mlp_x2(src="mlp_x2.hip"):
     """The f16x2 fused MLP (mlp_x2.hip) counts the vmcnt of its weight ring by hand.  name -> (scratch instructions inside the chunk loop -- loop
-    depth >= 2, where a spill would sit between the counted waits --, scratch instructions elsewhere, MFMA instructions).  The 4-wave D = 384
-    build uses all 512 registers and spills a few loop-invariant values OUTSIDE the chunk loop (tile prologue / epilogue: extra VMEM operations
-    there only make the next counted wait stricter); the 8-wave builds must not spill at all."""
+    depth >= 2, where a spill would sit between the counted waits --, scratch instructions elsewhere, MFMA instructions)."""
     lines = asm_of(src).split("\n")
     rep = {}
     for i, l in enumerate(lines):
@@ -147,9 +133,11 @@ def check_mlp_x2(src="mlp_x2.hip"):
         for t in lines[i + 1:]:
             if t.strip().startswith(".Lfunc_end"):
                 break
+            d = re.search(r"Depth=(\d+)", t)
             if re.match(r"\s*(\.LBB\w+:|; %bb\.\d+:)", t):
-                d = re.search(r"Depth=(\d+)", t)
                 depth = int(d.group(1)) if d else 0
+            elif d and t.strip().startswith(";"):   # (a loop header's own depth can sit on the comment line after its label)
+                depth = int(d.group(1))
             body = t.split(";")[0]
             if "scratch_" in body:
                 if depth >= 2:

@@ -16,7 +16,7 @@ agg=collections.defaultdict(lambda: collections.defaultdict(float)); n=collectio
 for f in glob.glob(out+"/*/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         k=r["Kernel_Name"]
-        if "gemm_duo" not in k and "gemm_ring" not in k: continue
+        if "gemm_ring" not in k: continue
         key=(k[:70], r.get("Grid_Size",""))
         agg[key][r["Counter_Name"]]+=float(r["Counter_Value"]); n[key].add((f,r["Dispatch_Id"]))
 for k,v in agg.items():
