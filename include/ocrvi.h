@@ -70,10 +70,21 @@ int ocrvi_det_workspace_bytes(const ocrvi_det* h, int N, int H, int W, size_t* b
 /* Replaces DBNetPP.forward (dbnet.py:13-17).  x: float32 NCHW [N,3,H,W], H and W multiples of 32
  * (pipeline2.py:33-40 guarantees it).  Outputs are float32 [N,1,H,W]; `binary` is required, the other four
  * dict entries of head.py:42-48 may be NULL (then not written; the arithmetic that produces them is still
- * the same two-branch head). */
+ * the same two-branch head: a caller that reads `binary` alone wants ocrvi_det_forward_binary below). */
 int ocrvi_det_forward(ocrvi_det* h, const float* x, int N, int H, int W,
                       float* binary, float* thresh, float* thresh_binary, float* bin_logits, float* thresh_logits,
                       void* workspace, size_t workspace_bytes, void* stream);
+/* Replaces DBNetPP.forward as the page loop uses it: `pred_binary = preds['binary']` is the one map inference reads
+ * (src/pipeline/pipeline2.py:318); thresh, thresh_binary and the two logit maps exist for the training loss.  Backbone, FPN and ASF as in
+ * ocrvi_det_forward; of the head only the binarise branch runs (head.py:34: ConvBnRelu(256,64,3), two ConvTranspose2d, Sigmoid -- the
+ * threshold branch, head.py:38, about 8 % of the forward's FLOPs, is not computed), the sigmoid sits in the last deconvolution's epilogue
+ * and no logit map is written.  binary: float32 [N,1,H,W], bit for bit the `binary` of ocrvi_det_forward on the same handle and input in
+ * the OCRVI_F32 and OCRVI_F16X2 modes (the branch runs on views of the same packed weights).  Same contract otherwise: shape rules,
+ * 256-byte aligned workspace of ocrvi_det_binary_workspace_bytes (never more than ocrvi_det_workspace_bytes), OCRVI_ENOMEM when it is
+ * short, enqueue-only on `stream`, graph-capturable, range flag snapshot for ocrvi_det_status. */
+int ocrvi_det_binary_workspace_bytes(const ocrvi_det* h, int N, int H, int W, size_t* bytes);
+int ocrvi_det_forward_binary(ocrvi_det* h, const float* x, int N, int H, int W, float* binary,
+                             void* workspace, size_t workspace_bytes, void* stream);
 /* Test hook: copies of intermediate features as float32 NCHW (c2..c5 backbone.py:56-60, fused neck.py:79).
  * Any pointer may be NULL.  Must follow a forward on the same workspace and stream. */
 /* OCRVI_F16X2 handles: OCRVI_OK, or OCRVI_ERANGE when an f16x2 kernel on this handle's device has met a value fp16's exponent cannot

@@ -15,7 +15,7 @@ DTYPES = {"f32": OCRVI_F32, "fp32": OCRVI_F32, "float32": OCRVI_F32, "bf16": OCR
           "f16": OCRVI_F16, "fp16": OCRVI_F16, "float16": OCRVI_F16,
           # fp32-equivalent arithmetic on the 16-bit matrix pipe: every operand kept as two fp16 halves (include/ocrvi.h)
           "f16x2": OCRVI_F16X2}
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 EXPORTS = [
     "ocrvi_last_error", "ocrvi_abi_version",
@@ -27,6 +27,7 @@ EXPORTS = [
     "ocrvi_prof_enable", "ocrvi_prof_reset", "ocrvi_prof_report",
     "ocrvi_det_status", "ocrvi_rec_status", "ocrvi_range_reset", "ocrvi_range_flag",
     "ocrvi_resize_normalize_pages", "ocrvi_crop_resize_normalize_pages", "ocrvi_db_boxes_pages",
+    "ocrvi_det_binary_workspace_bytes", "ocrvi_det_forward_binary",
 ]
 PAGE_ENTRY = 4          # int64 fields of one page-table entry: (device address, height, width, 0) -- OCRVI_PAGE_ENTRY
 
@@ -64,6 +65,8 @@ def load() -> C.CDLL:
     lib.ocrvi_det_destroy.restype = None
     lib.ocrvi_det_workspace_bytes.argtypes = [vp, i32, i32, i32, C.POINTER(sz)]
     lib.ocrvi_det_forward.argtypes = [vp, f32p, i32, i32, i32, f32p, f32p, f32p, f32p, f32p, vp, sz, vp]
+    lib.ocrvi_det_binary_workspace_bytes.argtypes = [vp, i32, i32, i32, C.POINTER(sz)]
+    lib.ocrvi_det_forward_binary.argtypes = [vp, f32p, i32, i32, i32, f32p, vp, sz, vp]
     lib.ocrvi_det_debug_features.argtypes = [vp, i32, i32, i32, f32p, f32p, f32p, f32p, f32p, vp, sz, vp]
     lib.ocrvi_rec_create.argtypes = [i32, vp, sz, C.POINTER(RecCfg), C.POINTER(vp)]
     lib.ocrvi_rec_destroy.argtypes = [vp]

@@ -338,6 +338,9 @@ __device__ __forceinline__ float gelu_erf(float x) {
     return fmaxf(x, 0.f) - ax * h;   // x (1 - h) for x >= 0, x h = -|x| h otherwise
 }
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
+// The DB head's probability of a logit (head.py:34,38 end in nn.Sigmoid): libm expf and an IEEE division.  db_maps_kernel (kernels.hip) and the
+// ST_DB_BIN epilogue (conv_gemm.h) both call this one expression, so the binary map has the same bits on either path.
+__device__ __forceinline__ float db_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
 // XCD-aware block remap (cdna_hip_programming.md T1, bijective form): consecutive logical tiles land on one XCD.
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {

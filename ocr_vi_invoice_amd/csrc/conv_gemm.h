@@ -23,9 +23,11 @@ namespace ocrvi {
 enum { AM_CONV1 = 0, AM_CONV3 = 1, AM_ROWS = 2, AM_DCN = 3 };
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2 };
 enum { RES_NONE = 0, RES_SAME = 1, RES_UP2 = 2 };        // RES_UP2: nearest 2x upsample of a half-res tensor (neck.py:36-38)
-enum { ST_NHWC = 0, ST_SHUFFLE2 = 1, ST_DCN_OFFS = 2, ST_DB_TAIL = 3 };  // ST_SHUFFLE2: ConvTranspose2d(k=2,s=2) pixel shuffle (head.py:13,16)
+enum { ST_NHWC = 0, ST_SHUFFLE2 = 1, ST_DCN_OFFS = 2, ST_DB_TAIL = 3, ST_DB_BIN = 4 };  // ST_SHUFFLE2: ConvTranspose2d(k=2,s=2) pixel shuffle (head.py:13,16)
 // ST_DB_TAIL: ST_SHUFFLE2 (64 ch, +bias, ReLU) followed IN THE EPILOGUE by the next ConvTranspose2d(64,1,2,2) (head.py:16): the wave's 64
 // columns are all channels of one sub-pixel, so the 64->1 deconv is an in-register dot + butterfly; writes fp32 logit maps [n,1,4*OH,4*OW].
+// ST_DB_BIN: ST_DB_TAIL for the binarise branch alone (one group): the same dot, butterfly and + b2, then db_sigmoid in the epilogue and the
+// probability stored straight into `out` = the binary map [n,1,4*OH,4*OW] (head.py:34 is all inference reads, pipeline2.py:318): no logit map.
 
 struct ConvParams {
     const void* x = nullptr;      // T   [n_img][H][W][Cin]   (AM_ROWS: [n_img][Hp][Wp][4])
@@ -36,7 +38,8 @@ struct ConvParams {
     const void* zero_page = nullptr;  // gemm_ring: >= 128 B of zeros (source of A rows past M)
     void* dump_page = nullptr;        // gemm_ring: >= 1 KiB sink for the stores of out-of-range lanes
     const void* res = nullptr;    // T or f32, or null
-    const float* offs = nullptr;  // AM_DCN: f32 [M][32] = 18 offsets (dy,dx per tap), 9 sigmoided masks, 5 pad
+    const float* offs = nullptr;  // AM_DCN: f32 [M][32] = 18 offsets (dy,dx per tap), 9 sigmoided masks, 5 pad; ST_DB_TAIL / ST_DB_BIN: second-deconv
+                                  // weights [2][64][4] + biases [2] (ST_DB_BIN reads branch 0's)
     int n_img = 1, H = 1, W = 1, Cin = 0;
     int OH = 1, OW = 1;
     int KH = 1, SH = 1, SW = 1, PH = 0, PW = 0;
@@ -346,7 +349,7 @@ __global__ __launch_bounds__(256, (ConvOccT<T, AMODE, BM, BN>::value)) void conv
             return;
         }
         if constexpr (TN == 64) {
-            if (p.store_mode == ST_DB_TAIL) {
+            if (p.store_mode == ST_DB_TAIL || p.store_mode == ST_DB_BIN) {   // (ST_DB_BIN: one group, grp == 0)
                 const float* w2 = p.offs + grp * 256;    // [64][4] second-deconv weights of this branch (c_in, a'b')
                 const float b2 = p.offs[512 + grp];
                 float* map = grp == 0 ? (float*)p.out : (float*)p.out2;
@@ -375,7 +378,7 @@ __global__ __launch_bounds__(256, (ConvOccT<T, AMODE, BM, BN>::value)) void conv
                         const int t = fastdiv(m, p.mg_ow), ow = m - t * p.OW, img = fastdiv(t, p.mg_oh), oh = t - img * p.OH;
                         const float val = (g == 0 ? q[0] : (g == 1 ? q[1] : (g == 2 ? q[2] : q[3]))) + b2;
                         const size_t row = (size_t)img * (4 * p.OH) + 4 * oh + 2 * (ab >> 1) + (g >> 1);
-                        map[row * (4 * p.OW) + 4 * ow + 2 * (ab & 1) + (g & 1)] = val;
+                        map[row * (4 * p.OW) + 4 * ow + 2 * (ab & 1) + (g & 1)] = p.store_mode == ST_DB_BIN ? db_sigmoid(val) : val;
                     }
                 }
                 return;

@@ -189,6 +189,9 @@ int launch_conv(const ConvParams& p_in, int amode, hipStream_t stream) {
     if (p.store_mode == ST_DB_TAIL) {
         OCRVI_CHECK(amode == AM_CONV1 && p.shuffle_co == 64 && p.N_g == 256 && p.Np == 256 && p.out2 && p.offs && p.bias && p.groups == 2,
                     OCRVI_EINVAL, "db-tail deconv: needs 2 groups of 4x64 columns, both logit maps and the second-deconv weights");
+    } else if (p.store_mode == ST_DB_BIN) {
+        OCRVI_CHECK(amode == AM_CONV1 && p.shuffle_co == 64 && p.N_g == 256 && p.Np == 256 && p.offs && p.bias && p.groups == 1 && p.out_f32,
+                    OCRVI_EINVAL, "db-bin deconv: needs one group of 4x64 columns, the fp32 binary map and the second-deconv weights");
     } else if (p.store_mode != ST_DCN_OFFS) {
         OCRVI_CHECK(p.N_g % 4 == 0 && p.ldo % 4 == 0 && p.out_coff % 4 == 0, OCRVI_EINVAL,
                     "conv: N_g=%d ldo=%d coff=%d must be multiples of 4", p.N_g, p.ldo, p.out_coff);

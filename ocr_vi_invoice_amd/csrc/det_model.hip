@@ -123,8 +123,10 @@ static int check_det_shape(const ocrvi_det* h, int N, int H, int W) {
     return OCRVI_OK;
 }
 
+// binary_head: the head of ocrvi_det_forward_binary -- the binarise branch alone, its probability written by the deconvolution's epilogue
+// (thresh / tbin / blog / tlog are not used).  Backbone, FPN and ASF are the same launches either way.
 static int det_run(ocrvi_det* h, Runner& r, const float* x, int N, int H, int W, float* binary, float* thresh, float* tbin, float* blog,
-                   float* tlog) {
+                   float* tlog, bool binary_head = false) {
     const int dt = h->cfg.dtype;
     const int Hp = H + 6, Wp = W + 8;
     Tensor xpad = r.alloc(N, Hp, Wp, 4);
@@ -219,6 +221,26 @@ static int det_run(ocrvi_det* h, Runner& r, const float* x, int N, int H, int W,
     float* asf_scratch = (float*)r.arena.alloc(asf_scratch_bytes(N, p[0].h, p[0].w));
     if (!r.dry()) OCRVI_TRY(k_asf(dt, p[0].p, p[1].p, p[2].p, p[3].p, h->asf_w, h->asf_b, asf_scratch, fused.p, N, p[0].h, p[0].w, r.stream));
     h->tap_fused = fused;
+    if (binary_head) {
+        // ---- DB head, binarise branch only (head.py:34; the page loop reads preds['binary'] and nothing else, pipeline2.py:318).  Both
+        // layers are VIEWS of the weights the two-branch head is packed into, not a second pack: fold_det puts the binarise branch's 64
+        // output channels first, so the first 64 rows (and biases) of head_conv are its 3x3 conv, and group 0 of head_dc1 is its deconv1.
+        // Same packed bits and same f16x2 layer scale as the five-map path, hence the same binary map.
+        ConvLayer hconv = h->head_conv, hdc = h->head_dc1;
+        hconv.N_g = hconv.Np = 64;
+        hdc.groups = 1;
+        Tensor hc1 = r.alloc(N, fused.h, fused.w, 64);
+        {
+            ConvOpts o;
+            o.pad = 1; o.act = ACT_RELU;
+            OCRVI_TRY(conv(r, hconv, fused, hc1, o));
+        }
+        // deconv1 (+BN+ReLU), deconv2 (64 -> 1) and the sigmoid in ONE GEMM: neither the deconv1 activation nor a logit map is written
+        Tensor bm; bm.p = binary; bm.n = N; bm.h = H; bm.w = W; bm.c = 1; bm.f32 = true;
+        ConvOpts o;
+        o.store_mode = ST_DB_BIN; o.offs = h->dc2_wb;
+        return conv(r, hdc, hc1, bm, o);
+    }
     // ---- DB head (head.py:32-48): both branches' 3x3 convs as one 256->128 conv, both deconv1 as one grouped pixel-shuffle GEMM
     Tensor hc = r.alloc(N, fused.h, fused.w, 128);
     {
@@ -262,6 +284,31 @@ extern "C" int ocrvi_det_forward(ocrvi_det* h, const float* x, int N, int H, int
     Runner r(h->cfg.dtype, (hipStream_t)stream, workspace, workspace_bytes);
     OCRVI_TRY(det_run(h, r, x, N, H, W, binary, thresh, thresh_binary, bin_logits, thresh_logits));
     OCRVI_CHECK(!r.arena.overflow, OCRVI_ENOMEM, "det_forward: workspace overflow");
+    return h->range.snapshot((hipStream_t)stream);
+}
+
+extern "C" int ocrvi_det_binary_workspace_bytes(const ocrvi_det* h, int N, int H, int W, size_t* bytes) {
+    OCRVI_CHECK(bytes, OCRVI_EINVAL, "det_binary_workspace_bytes: null out");
+    OCRVI_TRY(check_det_shape(h, N, H, W));
+    Runner r(h->cfg.dtype, nullptr, nullptr, 0);
+    OCRVI_TRY(det_run(const_cast<ocrvi_det*>(h), r, nullptr, N, H, W, nullptr, nullptr, nullptr, nullptr, nullptr, true));
+    *bytes = r.arena.peak + 256;
+    return OCRVI_OK;
+}
+
+extern "C" int ocrvi_det_forward_binary(ocrvi_det* h, const float* x, int N, int H, int W, float* binary, void* workspace, size_t workspace_bytes,
+                                        void* stream) {
+    OCRVI_TRY(check_det_shape(h, N, H, W));
+    OCRVI_CHECK(x && binary && workspace, OCRVI_EINVAL, "det_forward_binary: x, binary and workspace are required");
+    DeviceGuard dg(h->device);
+    OCRVI_HIP(dg.err);
+    size_t need = 0;
+    OCRVI_TRY(ocrvi_det_binary_workspace_bytes(h, N, H, W, &need));
+    OCRVI_CHECK(workspace_bytes >= need, OCRVI_ENOMEM, "det_forward_binary: workspace %zu < %zu bytes", workspace_bytes, need);
+    OCRVI_CHECK(((uintptr_t)workspace & 255) == 0, OCRVI_EINVAL, "det_forward_binary: workspace must be 256-byte aligned");
+    Runner r(h->cfg.dtype, (hipStream_t)stream, workspace, workspace_bytes);
+    OCRVI_TRY(det_run(h, r, x, N, H, W, binary, nullptr, nullptr, nullptr, nullptr, true));
+    OCRVI_CHECK(!r.arena.overflow, OCRVI_ENOMEM, "det_forward_binary: workspace overflow");
     return h->range.snapshot((hipStream_t)stream);
 }
 

@@ -217,7 +217,7 @@ ProfScope::~ProfScope() {
 
 static const char* amode_name(int amode, const ConvParams& p) {
     switch (amode) {
-        case AM_CONV1: return p.store_mode == ST_SHUFFLE2 ? "deconv2x2" : (p.store_mode == ST_DB_TAIL ? "deconv2x2_dbtail" : "conv1x1");
+        case AM_CONV1: return p.store_mode == ST_SHUFFLE2 ? "deconv2x2" : (p.store_mode == ST_DB_TAIL ? "deconv2x2_dbtail" : (p.store_mode == ST_DB_BIN ? "deconv2x2_dbbin" : "conv1x1"));
         case AM_CONV3: return p.store_mode == ST_DCN_OFFS ? "dcn_offset_conv3x3" : (p.groups > 1 ? "gconv3x3" : "conv3x3");
         case AM_ROWS: return "stem_conv";
         case AM_DCN: return "dcn3x3";
@@ -491,4 +491,4 @@ extern "C" int ocrvi_test_pack_f16x2(const float* src, size_t n, void* dst, floa
 }
 
 extern "C" const char* ocrvi_last_error(void) { return ocrvi::last_error_cstr(); }
-extern "C" int ocrvi_abi_version(void) { return 2; }
+extern "C" int ocrvi_abi_version(void) { return 3; }

@@ -683,8 +683,8 @@ __global__ void db_maps_kernel(const float* __restrict__ bl, const float* __rest
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
         const float4 b = ((const float4*)bl)[i], t = ((const float4*)tl)[i];
         float4 pb, pt, st;
-        pb.x = 1.f / (1.f + expf(-b.x)); pb.y = 1.f / (1.f + expf(-b.y)); pb.z = 1.f / (1.f + expf(-b.z)); pb.w = 1.f / (1.f + expf(-b.w));
-        pt.x = 1.f / (1.f + expf(-t.x)); pt.y = 1.f / (1.f + expf(-t.y)); pt.z = 1.f / (1.f + expf(-t.z)); pt.w = 1.f / (1.f + expf(-t.w));
+        pb.x = db_sigmoid(b.x); pb.y = db_sigmoid(b.y); pb.z = db_sigmoid(b.z); pb.w = db_sigmoid(b.w);
+        pt.x = db_sigmoid(t.x); pt.y = db_sigmoid(t.y); pt.z = db_sigmoid(t.z); pt.w = db_sigmoid(t.w);
         ((float4*)binary)[i] = pb;
         if (thresh) ((float4*)thresh)[i] = pt;
         if (tbin) {

@@ -27,6 +27,7 @@ class DBNetPP:
         self.dtype = _lib.dtype_code(dtype)
         self._handle = None
         self._ws = {}
+        self._ws_bin = {}
         self.training = False
         self._seed = seed
         if blob is not None:        # already folded + packed (weights.pack_blob): what rank 0 broadcasts to the other ranks
@@ -87,6 +88,7 @@ class DBNetPP:
                 raise RuntimeError("no weights retained to move")
             self.device = dev
             self._ws = {}
+            self._ws_bin = {}
             self.load_blob(self._blob)
         return self
 
@@ -135,6 +137,32 @@ class DBNetPP:
         return out
 
     __call__ = forward
+
+    def _workspace_binary(self, N, H, W) -> torch.Tensor:
+        key = (N, H, W)
+        ws = self._ws_bin.get(key)
+        if ws is None:
+            n = C.c_size_t()
+            _lib.check(_lib.load().ocrvi_det_binary_workspace_bytes(self._handle, N, H, W, C.byref(n)))
+            self._ws_bin.clear()
+            ws = torch.empty(n.value, dtype=torch.uint8, device=self.device)
+            self._ws_bin[key] = ws
+        return ws
+
+    def forward_binary(self, x: torch.Tensor) -> torch.Tensor:
+        """(N,3,H,W), H,W % 32 == 0 -> the ``binary`` map (N,1,H,W) float32 alone: what the page loop reads of the reference's dict
+        (``preds['binary']``, pipeline2.py:318).  Unlike ``forward(x, binary_only=True)``, which computes the whole two-branch head and skips
+        four stores, this runs the binarise branch only (head.py:34): the threshold branch (head.py:38) is not computed and no logit map is
+        written.  Same bits as ``forward(x)['binary']`` in the f32 and f16x2 modes.  Its workspace is cached apart from ``forward``'s."""
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f"expected (N,3,H,W) input, got {tuple(x.shape)}")
+        x = x.to(device=self.device, dtype=torch.float32).contiguous()
+        N, _, H, W = x.shape
+        ws = self._workspace_binary(N, H, W)
+        out = torch.empty((N, 1, H, W), dtype=torch.float32, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(_lib.load().ocrvi_det_forward_binary(self._handle, x.data_ptr(), N, H, W, out.data_ptr(), ws.data_ptr(), ws.numel(), stream))
+        return out
 
     def check_range(self) -> None:
         """f16x2 mode only (a no-op otherwise): synchronise the current stream and raise OverflowError if an activation left fp16's

@@ -394,17 +394,18 @@ def recognize_text_batch(model: SVTRv2, crops: List[np.ndarray], device: str = "
 
 
 def detect_and_recognize(original_image, det_model, rec_model, post_processor: DBPostProcessor, device: str = "cuda:0", det_size: int = 640,
-                         rec_size: Tuple[int, int] = (32, 256), rec_batch_size: int = 64):
+                         rec_size: Tuple[int, int] = (32, 256), rec_batch_size: int = 64, binary_head: bool = False):
     """Steps 2 and 3 of the reference's per-image loop (pipeline2.py:306-352) with every stage on this library: resize + normalise on the
     device -> ``det_model`` -> ``post_processor`` on the host copy of the binary map -> boxes rescaled to the original image -> the
     bounding rectangle of each box cropped, resized and normalised on the device straight from the uploaded page -> ``rec_model`` greedy
     CTC in batches of ``rec_batch_size``.  ``original_image``: RGB uint8 HxWx3 (numpy or device tensor).
+    ``binary_head``: call ``det_model.forward_binary`` (the binarise branch alone; same map in f32 / f16x2) instead of ``det_model(...)``.
     Returns (rescaled_boxes [int32 (n_i, 2)], scores, texts); empty crops decode the all-zero tensor as pipeline2.py:154-156 does."""
     page = original_image if isinstance(original_image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(original_image))
     page = page.to(device).contiguous()
     h, w = page.shape[:2]
     resized, (scale_h, scale_w) = resize_image_for_det(page, det_size)
-    det_preds = det_model(normalize_for_det(resized))
+    det_preds = det_model.forward_binary(normalize_for_det(resized)) if binary_head else det_model(normalize_for_det(resized))
     pred_binary = det_preds["binary"] if isinstance(det_preds, dict) else det_preds
     boxes, scores = post_processor(pred_binary[0])       # (copies the map to the host: the stream is synchronised from here on)
     if hasattr(det_model, "check_range"):
@@ -424,12 +425,12 @@ def detect_and_recognize(original_image, det_model, rec_model, post_processor: D
 
 
 def detect_and_recognize_pages(images, det_model, rec_model, post_processor: DBPostProcessor, device: str = "cuda:0", det_size: int = 640,
-                               rec_size: Tuple[int, int] = (32, 256), rec_batch_size: int = 64):
+                               rec_size: Tuple[int, int] = (32, 256), rec_batch_size: int = 64, binary_head: bool = False):
     """``detect_and_recognize`` for a list of pages of any sizes in one call: a one-shot ``engine.Engine`` (pages bucketed by detector
     shape, detector chunks and recogniser batches across pages).  ``det_model`` / ``rec_model`` are the library's DBNetPP / SVTRv2 on
     ``device``.  Returns [(rescaled_boxes, scores, texts) per page, in input order], each what ``detect_and_recognize`` returns for that
-    page alone."""
+    page alone (``binary_head`` as there)."""
     from .engine import Engine
     if torch.device(device).type != "cuda" or _dev_index(device) != det_model._dev_index():
         raise ValueError(f"models live on cuda:{det_model._dev_index()}, not {device}")
-    return Engine(det_model, rec_model, post_processor, det_size=det_size, rec_size=rec_size, rec_batch=rec_batch_size).run(images)
+    return Engine(det_model, rec_model, post_processor, det_size=det_size, rec_size=rec_size, rec_batch=rec_batch_size, binary_head=binary_head).run(images)

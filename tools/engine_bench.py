@@ -9,7 +9,8 @@ pre-processing kernel against the two-kernel path it replaces.  Prints ONE JSON 
 Both runs use SVTRv2-base and DBNet++ with bench.py's seeded weights in f16x2, crops of 48x320 in batches of 256, det_chunk 16, and
 bench.py's map blend through ``prob_hook``: every page's ground-truth line boxes, scaled to its bucket and shrunk by the DB shrink rule,
 at 0.75 + 0.25 binary (elsewhere 0.25 binary).  Each ``run`` drains at its end (bench.py's timed region carries the recogniser's last
-partial batch over into the next step instead)."""
+partial batch over into the next step instead).
+``--binary-head`` repeats the uniform / mixed sets with ``Engine(binary_head=True)`` under the key ``runs_binary_head``."""
 import argparse
 import json
 import os
@@ -127,6 +128,8 @@ def main():
     ap.add_argument("--lines", type=int, default=30)
     ap.add_argument("--dtype", default="f16x2", choices=["f32", "f16x2", "bf16", "f16"])
     ap.add_argument("--sets", default="uniform,mixed,preproc")
+    ap.add_argument("--binary-head", action="store_true",
+                    help="run the uniform / mixed sets a second time with Engine(binary_head=True); results under 'runs_binary_head'")
     args = ap.parse_args()
     import torch
     from ocr_vi_invoice_amd import DBNetPP, SVTRv2, weights
@@ -149,6 +152,14 @@ def main():
             sizes = [MIXED[i % len(MIXED)] for i in range(args.pages)]
             runs.append(run_set("mixed " + ",".join(f"{h}x{w}" for h, w in MIXED), kw, sizes, 960, args, det, rec, pp))
         res["runs"] = runs
+        if args.binary_head:   # the same sets with the binarise-branch-only detector forward (ocrvi_det_forward_binary)
+            kwb = dict(kw, binary_head=True)
+            runs_b = []
+            if "uniform" in sets:
+                runs_b.append(run_set("uniform 960x1280 binary_head", kwb, [(960, 1280)] * args.pages, 1280, args, det, rec, pp))
+            if "mixed" in sets:
+                runs_b.append(run_set("mixed binary_head " + ",".join(f"{h}x{w}" for h, w in MIXED), kwb, sizes, 960, args, det, rec, pp))
+            res["runs_binary_head"] = runs_b
     print(json.dumps(res), flush=True)
 
 
