@@ -118,7 +118,8 @@ int ocrvi_rec_workspace_bytes(const ocrvi_rec* h, int B, int H, int W, size_t* b
 /* Replaces SVTRv2.forward(x, targets=None) (svtrv2.py:503-536) fused with decode_probs' device half
  * (svtrv2.py:555-566).  x: float32 NCHW [B,3,H,W], H % 16 == 0 and W % 4 == 0, T = W/4.
  *   log_probs [T,B,num_classes] float32 (may be NULL)
- *   argmax_ids [B,T] int32: per-step argmax over classes, first index wins ties (may be NULL)
+ *   argmax_ids [B,T] int32: per-step argmax over classes, first index wins ties; 0 for a step whose log-probs are NaN (a NaN or +inf
+ *              logit, or nothing but -inf), as ocrvi_ctc_greedy gives -- always inside [0, num_classes) (may be NULL)
  *   ids [B,T] int32: greedy CTC path after collapsing repeats and dropping `blank_id`, padded with -1
  *   lens [B] int32: number of valid entries of each ids row
  * ids/lens may both be NULL.  Mapping ids -> text (which also drops pad id 1, tokenizer.py:73) is host work. */
@@ -280,6 +281,31 @@ int ocrvi_test_mlp(int device, int dtype, float* x, const float* ln_g_host, cons
  * 4 consecutive elements [hi0 hi1 hi2 hi3 | lo0 lo1 lo2 lo3] (fp16), hi + lo = src * 2^s with one power of two s per layer that puts the
  * largest magnitude into [2^13, 2^14); *wscale = 2^-s.  (What ocrvi_*_create does to every GEMM weight in that mode.) */
 int ocrvi_test_pack_f16x2(const float* src, size_t n, void* dst, float* wscale);
+
+/* The memory-bound kernels of the hot path, one hook each.  Same conventions as above: float32 DEVICE tensors in and out (converted to and
+ * from `dtype`, the element type the kernel runs in, around the call), weights and vectors float32 HOST; each hook allocates, binds the
+ * f16x2 range flag and synchronises.  No timing arguments. */
+/* LayerNorm over the last dim, eps 1e-5 (nn.LayerNorm, svtrv2.py:93,95,446): x [rows][D] -> out [rows][D].  x_f32 / out_f32 != 0: the kernel
+ * reads / writes float32 directly (the residual stream), else `dtype` elements.  D % 4 == 0, D <= 1024. */
+int ocrvi_test_layernorm(int device, int dtype, const float* x, int x_f32, int out_f32, const float* gamma_host, const float* beta_host,
+                         int rows, int D, float* out);
+/* FRM vertical cross-attention with the precomputed query (svtrv2.py:236-243), head_dim 32: kv [B*H*W][2D] (token = h*W + w per image, k in
+ * columns 0..D-1, v in D..2D-1), vq host [D] -> out [B*W][D].  1 <= H <= 8, D % 32 == 0. */
+int ocrvi_test_frm_vertical(int device, int dtype, const float* kv, const float* vq_host, int B, int H, int W, int D, float* out);
+/* Adaptive scale fusion (neck.py:57-79): p2 [N,256,H,W], p3 [N,256,H/2,W/2], p4 [N,256,H/4,W/4], p5 [N,256,H/8,W/8] float32 NCHW; w host
+ * [4][1024] (the 1x1 attention conv over the concatenation p2 | up(p3) | up(p4) | up(p5)), b host [4] -> out [N,256,H,W].  H, W % 8 == 0. */
+int ocrvi_test_asf(int device, int dtype, const float* p2, const float* p3, const float* p4, const float* p5, const float* w_host,
+                   const float* b_host, int N, int H, int W, float* out);
+/* MaxPool2d(3, stride 2, padding 1) (torchvision resnet stem, backbone.py:34): x [N,C,H,W] -> out [N,C,(H-1)/2+1,(W-1)/2+1].  C % 8 == 0. */
+int ocrvi_test_maxpool(int device, int dtype, const float* x, int N, int C, int H, int W, float* out);
+/* DB head maps (head.py:28-40): binary = sigmoid(bin_logits), thresh = sigmoid(thresh_logits), thresh_binary = 1 / (1 + exp(-k (binary -
+ * thresh))); n float32 elements per map (n % 4 == 0, 16-byte aligned).  thresh and thresh_binary may be NULL (then not written). */
+int ocrvi_test_db_maps(int device, const float* bin_logits, const float* thresh_logits, float k, float* binary, float* thresh,
+                       float* thresh_binary, size_t n);
+/* The recogniser's decode head (svtrv2.py:536,555): logits [B*T][ld] (row = b*T + t, columns C..ld-1 are never read) -> log_softmax over the
+ * C classes into log_probs [T][B][C] and its per-step argmax into argmax_ids [B][T] (first index wins ties; 0 for a row whose log-probs
+ * are NaN, as ocrvi_ctc_greedy gives).  Either output may be NULL.  C <= 1024, ld >= C. */
+int ocrvi_test_ctc_logsoftmax(int device, const float* logits, int ld, int B, int T, int C, float* log_probs, int32_t* argmax_ids);
 
 /* Per-launch HIP-event profiler (process-global, off by default).  While enabled every MFMA / bandwidth kernel launch
  * of the graphs above is bracketed by two events recorded on its launch stream.  ocrvi_prof_report synchronises those

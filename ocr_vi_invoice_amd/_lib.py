@@ -15,7 +15,7 @@ DTYPES = {"f32": OCRVI_F32, "fp32": OCRVI_F32, "float32": OCRVI_F32, "bf16": OCR
           "f16": OCRVI_F16, "fp16": OCRVI_F16, "float16": OCRVI_F16,
           # fp32-equivalent arithmetic on the 16-bit matrix pipe: every operand kept as two fp16 halves (include/ocrvi.h)
           "f16x2": OCRVI_F16X2}
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 EXPORTS = [
     "ocrvi_last_error", "ocrvi_abi_version",
@@ -28,6 +28,7 @@ EXPORTS = [
     "ocrvi_det_status", "ocrvi_rec_status", "ocrvi_range_reset", "ocrvi_range_flag",
     "ocrvi_resize_normalize_pages", "ocrvi_crop_resize_normalize_pages", "ocrvi_db_boxes_pages",
     "ocrvi_det_binary_workspace_bytes", "ocrvi_det_forward_binary",
+    "ocrvi_test_layernorm", "ocrvi_test_frm_vertical", "ocrvi_test_asf", "ocrvi_test_maxpool", "ocrvi_test_db_maps", "ocrvi_test_ctc_logsoftmax",
 ]
 PAGE_ENTRY = 4          # int64 fields of one page-table entry: (device address, height, width, 0) -- OCRVI_PAGE_ENTRY
 
@@ -101,6 +102,12 @@ def load() -> C.CDLL:
     lib.ocrvi_test_attention.argtypes = [i32, i32, f32p, i32, i32, i32, f32p, i32, C.POINTER(C.c_float)]
     lib.ocrvi_test_mlp.argtypes = [i32, i32, f32p, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32p, i32, C.POINTER(C.c_float)]
     lib.ocrvi_test_pack_f16x2.argtypes = [f32p, sz, vp, C.POINTER(C.c_float)]
+    lib.ocrvi_test_layernorm.argtypes = [i32, i32, f32p, i32, i32, vp, vp, i32, i32, f32p]
+    lib.ocrvi_test_frm_vertical.argtypes = [i32, i32, f32p, vp, i32, i32, i32, i32, f32p]
+    lib.ocrvi_test_asf.argtypes = [i32, i32, f32p, f32p, f32p, f32p, vp, vp, i32, i32, i32, f32p]
+    lib.ocrvi_test_maxpool.argtypes = [i32, i32, f32p, i32, i32, i32, i32, f32p]
+    lib.ocrvi_test_db_maps.argtypes = [i32, f32p, f32p, C.c_float, f32p, f32p, f32p, sz]
+    lib.ocrvi_test_ctc_logsoftmax.argtypes = [i32, f32p, i32, i32, i32, i32, f32p, i32p]
     lib.ocrvi_det_status.argtypes = [vp]
     lib.ocrvi_rec_status.argtypes = [vp]
     lib.ocrvi_range_reset.argtypes = [i32, vp]

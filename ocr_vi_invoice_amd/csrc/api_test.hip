@@ -1,6 +1,7 @@
 // Kernel-level hooks of the C ABI (include/ocrvi.h, "test/bench hooks"): run ONE production kernel on
 // caller-supplied float32 NCHW device tensors.  They allocate scratch, convert layouts, time with HIP events on
-// their own stream, and synchronise -- test infrastructure around the same kernels the model graphs launch.
+// their own stream (the MFMA kernels' hooks; the memory-bound kernels' hooks at the end take no timing arguments),
+// and synchronise -- test infrastructure around the same kernels the model graphs launch.
 #include <memory>
 
 #include "model.h"
@@ -296,6 +297,123 @@ extern "C" int ocrvi_test_mlp(int device, int dtype, float* x, const float* ln_g
     // one clean application for the result
     OCRVI_TRY(k_mlp_fused(dtype, x, xn, g, b, ng, nb, ws, b1, b2, M, D, sc.s));
     if (want_xn && xn_out) OCRVI_TRY(k_nhwc_to_nchw_f32(dtype, xn, xn_out, 1, 1, M * D, 1, 1, 0, sc.s));
+    OCRVI_HIP(hipStreamSynchronize(sc.s));
+    return OCRVI_OK;
+}
+
+// ---- the memory-bound kernels of kernels.hip, one hook each (no timing arguments: nothing benchmarks these)
+namespace {
+// [n] T -> float32 (same order): a C = 1 "NHWC -> NCHW" copy is a plain cast
+int cast_to_f32(int dtype, const void* x, float* y, size_t n, hipStream_t s) {
+    OCRVI_CHECK(n < ((size_t)1 << 31), OCRVI_EINVAL, "test hook: tensor too large");
+    return k_nhwc_to_nchw_f32(dtype, x, y, 1, 1, (int)n, 1, 1, 0, s);
+}
+}  // namespace
+
+extern "C" int ocrvi_test_layernorm(int device, int dtype, const float* x, int x_f32, int out_f32, const float* gamma_host, const float* beta_host,
+                                    int rows, int D, float* out) {
+    OCRVI_CHECK(x && gamma_host && beta_host && out && rows > 0 && D > 0 && dtype_valid(dtype), OCRVI_EINVAL, "test_layernorm: bad argument");
+    OCRVI_HIP(hipSetDevice(device));
+    Scratch sc;
+    OCRVI_TRY(sc.init());
+    DeviceStore st;
+    float *g = nullptr, *b = nullptr;
+    OCRVI_TRY(st.upload(gamma_host, (size_t)D * 4, (void**)&g));
+    OCRVI_TRY(st.upload(beta_host, (size_t)D * 4, (void**)&b));
+    const size_t n = (size_t)rows * D;
+    const void* xin = x;
+    void* yo = out;
+    if (!x_f32) {
+        void* xt = nullptr;
+        OCRVI_TRY(sc.alloc(n * dtype_size(dtype), &xt));
+        OCRVI_TRY(k_cast_from_f32(dtype, x, xt, n, sc.s));
+        xin = xt;
+    }
+    if (!out_f32) OCRVI_TRY(sc.alloc(n * dtype_size(dtype), &yo));
+    OCRVI_TRY(k_layernorm(dtype, xin, x_f32, yo, out_f32, g, b, rows, D, sc.s));
+    if (!out_f32) OCRVI_TRY(cast_to_f32(dtype, yo, out, n, sc.s));
+    OCRVI_HIP(hipStreamSynchronize(sc.s));
+    return OCRVI_OK;
+}
+
+extern "C" int ocrvi_test_frm_vertical(int device, int dtype, const float* kv, const float* vq_host, int B, int H, int W, int D, float* out) {
+    OCRVI_CHECK(kv && vq_host && out && B > 0 && H > 0 && W > 0 && D > 0 && D % 4 == 0 && dtype_valid(dtype), OCRVI_EINVAL,
+                "test_frm_vertical: bad argument");
+    OCRVI_HIP(hipSetDevice(device));
+    Scratch sc;
+    OCRVI_TRY(sc.init());
+    DeviceStore st;
+    float* vq = nullptr;
+    OCRVI_TRY(st.upload(vq_host, (size_t)D * 4, (void**)&vq));
+    const size_t nin = (size_t)B * H * W * 2 * D, nout = (size_t)B * W * D;
+    void *kt = nullptr, *ot = nullptr;
+    OCRVI_TRY(sc.alloc(nin * dtype_size(dtype), &kt));
+    OCRVI_TRY(sc.alloc(nout * dtype_size(dtype), &ot));
+    OCRVI_TRY(k_cast_from_f32(dtype, kv, kt, nin, sc.s));
+    OCRVI_TRY(k_frm_vertical(dtype, kt, vq, ot, B, H, W, D, sc.s));
+    OCRVI_TRY(cast_to_f32(dtype, ot, out, nout, sc.s));
+    OCRVI_HIP(hipStreamSynchronize(sc.s));
+    return OCRVI_OK;
+}
+
+extern "C" int ocrvi_test_asf(int device, int dtype, const float* p2, const float* p3, const float* p4, const float* p5, const float* w_host,
+                              const float* b_host, int N, int H, int W, float* out) {
+    OCRVI_CHECK(p2 && p3 && p4 && p5 && w_host && b_host && out && N > 0 && H >= 8 && W >= 8 && dtype_valid(dtype), OCRVI_EINVAL,
+                "test_asf: bad argument");
+    OCRVI_HIP(hipSetDevice(device));
+    Scratch sc;
+    OCRVI_TRY(sc.init());
+    DeviceStore st;
+    float *w = nullptr, *b = nullptr;
+    OCRVI_TRY(st.upload(w_host, (size_t)4 * 1024 * 4, (void**)&w));
+    OCRVI_TRY(st.upload(b_host, (size_t)4 * 4, (void**)&b));
+    const float* src[4] = {p2, p3, p4, p5};
+    void* lv[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int l = 0; l < 4; ++l) {
+        const int hw = (H >> l) * (W >> l);
+        OCRVI_TRY(sc.alloc((size_t)N * hw * 256 * dtype_size(dtype), &lv[l]));
+        OCRVI_TRY(to_nhwc(dtype, src[l], lv[l], N, 256, hw, sc.s));
+    }
+    void *on = nullptr, *scr = nullptr;
+    OCRVI_TRY(sc.alloc((size_t)N * H * W * 256 * dtype_size(dtype), &on));
+    OCRVI_TRY(sc.alloc(asf_scratch_bytes(N, H, W), &scr));
+    OCRVI_TRY(k_asf(dtype, lv[0], lv[1], lv[2], lv[3], w, b, (float*)scr, on, N, H, W, sc.s));
+    OCRVI_TRY(k_nhwc_to_nchw_f32(dtype, on, out, N, H, W, 256, 256, 0, sc.s));
+    OCRVI_HIP(hipStreamSynchronize(sc.s));
+    return OCRVI_OK;
+}
+
+extern "C" int ocrvi_test_maxpool(int device, int dtype, const float* x, int N, int C, int H, int W, float* out) {
+    OCRVI_CHECK(x && out && N > 0 && C > 0 && C % 4 == 0 && H > 0 && W > 0 && dtype_valid(dtype), OCRVI_EINVAL, "test_maxpool: bad argument");
+    OCRVI_HIP(hipSetDevice(device));
+    Scratch sc;
+    OCRVI_TRY(sc.init());
+    const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
+    void *xn = nullptr, *yn = nullptr;
+    OCRVI_TRY(sc.alloc((size_t)N * H * W * C * dtype_size(dtype), &xn));
+    OCRVI_TRY(sc.alloc((size_t)N * OH * OW * C * dtype_size(dtype), &yn));
+    OCRVI_TRY(to_nhwc(dtype, x, xn, N, C, H * W, sc.s));
+    OCRVI_TRY(k_maxpool3x3s2(dtype, xn, yn, N, H, W, C, sc.s));
+    OCRVI_TRY(k_nhwc_to_nchw_f32(dtype, yn, out, N, OH, OW, C, C, 0, sc.s));
+    OCRVI_HIP(hipStreamSynchronize(sc.s));
+    return OCRVI_OK;
+}
+
+extern "C" int ocrvi_test_db_maps(int device, const float* bin_logits, const float* thresh_logits, float k, float* binary, float* thresh,
+                                  float* thresh_binary, size_t n) {
+    OCRVI_HIP(hipSetDevice(device));
+    Scratch sc;
+    OCRVI_TRY(sc.init());
+    OCRVI_TRY(k_db_maps(bin_logits, thresh_logits, k, binary, thresh, thresh_binary, n, sc.s));
+    OCRVI_HIP(hipStreamSynchronize(sc.s));
+    return OCRVI_OK;
+}
+
+extern "C" int ocrvi_test_ctc_logsoftmax(int device, const float* logits, int ld, int B, int T, int C, float* log_probs, int32_t* argmax_ids) {
+    OCRVI_HIP(hipSetDevice(device));
+    Scratch sc;
+    OCRVI_TRY(sc.init());
+    OCRVI_TRY(k_ctc_logsoftmax_argmax(logits, ld, log_probs, argmax_ids, B, T, C, sc.s));
     OCRVI_HIP(hipStreamSynchronize(sc.s));
     return OCRVI_OK;
 }

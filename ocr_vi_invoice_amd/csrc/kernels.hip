@@ -1,5 +1,5 @@
 // Memory-bound kernels of the hot path: layout conversion, max-pool, LayerNorm, FRM column attention, ASF,
-// DB head tail, CTC log-softmax / argmax / collapse.  wave64 reductions, 8..16-byte vector accesses.
+// DB maps, CTC log-softmax / argmax / collapse.  wave64 reductions, 8..16-byte vector accesses.
 #include "kernels.h"
 
 namespace ocrvi {
@@ -600,83 +600,7 @@ int k_asf(int dtype, const void* p2, const void* p3, const void* p4, const void*
 // bytes of fp32 scratch k_asf needs for the coarse score maps
 size_t asf_scratch_bytes(int N, int H, int W) { return ((size_t)N * (H / 2) * (W / 2) + (size_t)N * (H / 4) * (W / 4) + (size_t)N * (H / 8) * (W / 8)) * 16; }
 
-// ------------------------------------------------------------------ DB head tail: deconv2 (64->1, 2x2 s2) x2 branches + sigmoid + step
-// 128/EPC lanes share one pixel's 128-channel row (one 16-byte chunk per lane -> the wave reads whole contiguous rows):
-// lanes of the first half own the binarise branch (ch 0..63), of the second the threshold branch.  Each lane keeps the
-// deconv weights of its own channels in registers, partial sums are butterflied inside the branch, and lanes 0..3 of a
-// pixel write the four 2x2 output positions.
-template <typename T>
-__global__ __launch_bounds__(256) void db_tail_kernel(const T* __restrict__ y, const float* __restrict__ w2, const float* __restrict__ b2, float k,
-                                                      float* __restrict__ binary, float* __restrict__ thresh, float* __restrict__ tbin,
-                                                      float* __restrict__ blog, float* __restrict__ tlog, int N, int H2, int W2) {
-    constexpr int EPC = TypeInfo<T>::EPC;
-    constexpr int LPP = 128 / EPC;      // lanes per pixel (16 or 32)
-    constexpr int PPW = 64 / LPP;       // pixels per wave pass
-    const int lane = threadIdx.x & 63;
-    const int j = lane % LPP, sub = lane / LPP;
-    const int br = j >= LPP / 2 ? 1 : 0;
-    float wr[EPC][4];
-#pragma unroll
-    for (int e = 0; e < EPC; ++e) {
-        const float4 t = *(const float4*)(w2 + (size_t)(j * EPC + e) * 4);  // w2 is [2][64][4] = [128][4] in channel order
-        wr[e][0] = t.x; wr[e][1] = t.y; wr[e][2] = t.z; wr[e][3] = t.w;
-    }
-    const float bias = b2[br];
-    const size_t total = (size_t)N * H2 * W2;
-    const size_t wave = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nwaves = (size_t)gridDim.x * (blockDim.x >> 6);
-    const int OW = 2 * W2;
-    for (size_t p0 = wave * PPW; p0 < total; p0 += nwaves * PPW) {
-        const size_t pix = p0 + sub;
-        const bool ok = pix < total;
-        float f[EPC];
-        uint4 raw = make_uint4(0, 0, 0, 0);
-        if (ok) raw = *(const uint4*)(y + pix * 128 + j * EPC);
-        Chunk<T>::unpack(raw, f);
-        float a[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) a[q] = fmaf(f[e], wr[e][q], a[q]);
-        }
-#pragma unroll
-        for (int o = 1; o < LPP / 2; o <<= 1) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) a[q] += __shfl_xor(a[q], o);
-        }
-        // every lane of a branch now holds that branch's 4 logits; fetch the other branch's from the partner half
-        float mine[4], other[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            mine[q] = a[q] + bias;
-            other[q] = __shfl_xor(mine[q], LPP / 2);
-        }
-        if (ok && j < 4) {  // lane j of the binarise half writes output position q = j
-            const float lb = j == 0 ? mine[0] : (j == 1 ? mine[1] : (j == 2 ? mine[2] : mine[3]));
-            const float lt = j == 0 ? other[0] : (j == 1 ? other[1] : (j == 2 ? other[2] : other[3]));
-            const int x = (int)(pix % W2);
-            const size_t t = pix / W2;
-            const int yy = (int)(t % H2), n = (int)(t / H2);
-            const size_t o = ((size_t)n * (2 * H2) + 2 * yy + (j >> 1)) * OW + 2 * x + (j & 1);
-            const float pb = 1.f / (1.f + expf(-lb)), pt = 1.f / (1.f + expf(-lt));
-            binary[o] = pb;
-            if (thresh) thresh[o] = pt;
-            if (tbin) tbin[o] = 1.f / (1.f + expf(-k * (pb - pt)));
-            if (blog) blog[o] = lb;
-            if (tlog) tlog[o] = lt;
-        }
-    }
-}
-int k_db_tail(int dtype, const void* y, const float* w2, const float* b2, float k, float* binary, float* thresh, float* thresh_binary,
-              float* bin_logits, float* thresh_logits, int N, int H2, int W2, hipStream_t s) {
-    OCRVI_CHECK(y && w2 && b2 && binary && N > 0, OCRVI_EINVAL, "db tail: null operand");
-    ProfScope ps_("db_head_tail", 0.0, (double)N*H2*W2*(128.0*dtype_size(dtype)+16.0*((thresh?1:0)+(thresh_binary?1:0)+(bin_logits?1:0)+(thresh_logits?1:0)+1)), s);
-    const size_t total = (size_t)N * H2 * W2;
-    const int grid = (int)std::min<size_t>((total + 15) / 16, 256 * 8);
-    DISPATCH_DT(dtype, hipLaunchKernelGGL(db_tail_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)y, w2, b2, k, binary, thresh, thresh_binary, bin_logits, thresh_logits, N, H2, W2));
-    OCRVI_HIP(hipGetLastError());
-    return OCRVI_OK;
-}
-
+// ------------------------------------------------------------------ DB maps
 // logits -> binary = sigmoid(bin), thresh = sigmoid(thr), thresh_binary = 1/(1+exp(-k(binary-thresh)))  (head.py:28-40)
 __global__ void db_maps_kernel(const float* __restrict__ bl, const float* __restrict__ tl, float k, float* __restrict__ binary,
                                float* __restrict__ thresh, float* __restrict__ tbin, size_t n4) {
@@ -749,7 +673,9 @@ __global__ void ctc_logsoftmax_argmax_kernel(const float* __restrict__ logits, i
         }
     }
     wave_argmax(best, bi);
-    if (argmax_ids && lane == 0) argmax_ids[(size_t)b * T + t] = bi;
+    // a row whose log-probs are NaN (a NaN or +inf logit, or nothing but -inf) leaves every lane without a candidate: index 0, the rule of
+    // ctc_argmax_tbc_kernel below and what torch.log_softmax(..).argmax(-1) gives -- never an id outside [0, C)
+    if (argmax_ids && lane == 0) argmax_ids[(size_t)b * T + t] = bi == 0x7fffffff ? 0 : bi;
 }
 int k_ctc_logsoftmax_argmax(const float* logits, int ld, float* log_probs, int32_t* argmax_ids, int B, int T, int C, hipStream_t s) {
     OCRVI_CHECK(logits && B > 0 && T > 0 && C > 0 && C <= 1024 && ld >= C, OCRVI_EINVAL, "ctc: bad shape B=%d T=%d C=%d", B, T, C);

@@ -196,3 +196,164 @@ def test_model_level_overflow_is_reported_not_swallowed():
     with pytest.raises(OverflowError):
         det.check_range()
     det.reset_range()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# One test per remaining f16x2 writer.  include/ocrvi.h promises that EVERY kernel that writes f16x2 elements raises the flag when it
+# packs |x| >= 65520; each writer carries its own copy of the check, and the pointer to the flag word is a per-translation-unit device
+# variable (a silent no-op in a unit that forgot OCRVI_RANGE_FLAG_TU()).  Per writer, with inputs that are themselves in range: the flag
+# stays 0 at ordinary scale, is 1 when the OUTPUT passes 65520 (activation x 2^10, weight x 2^7, as case (2) above), and stays 0 for the
+# same call in f32.  Not covered: the ring GEMM's 3x3 mode is 16-bit only (gemm_ring_eligible: esz == 2), so no f16x2 shape selects it;
+# conv_gemm's generic store4 path (RES_UP2 / pixel-shuffle stores, unaligned rows) cannot be reached through ocrvi_test_conv, whose buffers
+# are always 16-byte aligned rows -- it packs through common.h's store4, the check the cast and LayerNorm cases exercise.
+from test_gpu_kernels import _run_dcn, _run_stem_pool, run_conv      # noqa: E402
+
+
+def _three_calls(run):
+    """run(dt, activation scale, weight scale) -> output tensor(s)."""
+    _reset()
+    out = run("f16x2", 1.0, 1.0)
+    assert _flag() == 0 and torch.isfinite(out).all()
+    _reset()
+    out = run("f16x2", 2.0 ** 10, 2.0 ** 7)
+    assert _flag() == 1, "output past 65520 packed without raising the range flag"
+    _reset()
+    out = run("f32", 2.0 ** 10, 2.0 ** 7)
+    assert _flag() == 0 and torch.isfinite(out).all() and float(out.abs().max()) > 65520.0
+    _reset()
+
+
+@pytest.mark.parametrize("case", [
+    # conv_gemm, LDS-staged tile store (epi_lds: 16-byte aligned NHWC rows), 128-column tile: 3x3 / stride 2 is neither halo- nor ring-eligible
+    (2, 64, 24, 32, 128, 3, 2, 1),
+    # conv_gemm, the same store from the 32-column tile: a grouped 3x3 (N_g = 32 per group)
+    (2, 128, 12, 20, 128, 3, 1, 4),
+    # conv_gemm AM_CONV1: a 1x1 whose 48 input channels are not whole 32-channel K-steps (the ring needs Cin % 32 == 0)
+    (2, 48, 12, 20, 128, 1, 1, 1),
+])
+def test_conv_gemm_output_overflow_raises_the_flag(case):
+    N, Cin, H, W, Co, ks, st, groups = case
+    g = torch.Generator().manual_seed(sum(case))
+    x = torch.randn(N, Cin, H, W, generator=g)
+    w = torch.randn(Co, Cin // groups, ks, ks, generator=g) / np.sqrt(Cin // groups * ks * ks)
+    b = torch.zeros(Co)
+    _three_calls(lambda dt, sa, sw: run_conv(x * sa, w * sw, b, ks, st, st, groups, 0, dt))
+
+
+def test_conv3_halo_output_overflow_raises_the_flag():
+    N, Cin, H, W, Co = 3, 256, 12, 16, 256          # HALO_CASES: neck.fpn[2]
+    g = torch.Generator().manual_seed(21)
+    x = torch.randn(N, Cin, H, W, generator=g)
+    w = torch.randn(Co, Cin, 3, 3, generator=g) / np.sqrt(9 * Cin)
+    _three_calls(lambda dt, sa, sw: run_conv(x * sa, w * sw, torch.zeros(Co), 3, 1, 1, 1, 0, dt))
+
+
+def test_dcn_pipe_output_overflow_raises_the_flag():
+    g = torch.Generator().manual_seed(22)
+    N, C_, H, W = 2, 128, 14, 18
+    x = torch.randn(N, C_, H, W, generator=g)
+    off = torch.randn(N, 18, H, W, generator=g) * 3.0
+    mask = torch.rand(N, 9, H, W, generator=g)
+    w = torch.randn(C_, C_, 3, 3, generator=g) / np.sqrt(9 * C_)
+    _three_calls(lambda dt, sa, sw: _run_dcn(x * sa, off, mask, w * sw, torch.zeros(C_), 1, dt))
+
+
+def test_stem_pool_output_overflow_raises_the_flag():
+    g = torch.Generator().manual_seed(23)
+    x = torch.randn(2, 3, 36, 52, generator=g)
+    w = torch.randn(64, 3, 7, 7, generator=g) / 147 ** 0.5
+    b = torch.zeros(64)
+    # (the fused kernel is the f16x2 form; f32 runs the conv + max-pool pair)
+    _three_calls(lambda dt, sa, sw: _run_stem_pool(x * sa, w * sw, b, dt, dt == "f16x2")[0])
+
+
+@pytest.mark.parametrize("D", [128, 384])
+def test_mlp_x2_hidden_and_xn_overflow_raise_the_flag(D):
+    """mlp_x2.hip packs twice: the hidden activations gelu(fc1(..)) it feeds to fc2, and the xn output.  (No f32 call: the fused MLP has no
+    f32 form, ocrvi_test_mlp rejects it.)"""
+    L = _L()
+    g = torch.Generator().manual_seed(24 + D)
+    M = 200
+    x = torch.randn(M, D, generator=g)
+    lg, lb = torch.ones(D), torch.zeros(D)
+    w1, b1 = torch.randn(4 * D, D, generator=g) * np.sqrt(2.0 / D), torch.zeros(4 * D)
+    w2, b2 = torch.randn(D, 4 * D, generator=g) * np.sqrt(0.5 / (4 * D)), torch.zeros(D)
+    ng, nb = torch.ones(D), torch.zeros(D)
+
+    def run(w1s, ngs):
+        h = lambda t: np.ascontiguousarray(t.numpy(), dtype=np.float32)
+        arrs = [h(lg), h(lb), h(w1 * w1s), h(b1), h(w2), h(b2), h(ng * ngs), h(nb)]
+        xdev = x.cuda().clone()
+        xn = torch.zeros((M, D), device="cuda")
+        L.check(L.load().ocrvi_test_mlp(0, DT["f16x2"], xdev.data_ptr(), *[a.ctypes.data for a in arrs], 1, M, D, xn.data_ptr(), 0, None))
+        return xdev.cpu(), xn.cpu()
+
+    _reset()
+    xo, xn = run(1.0, 1.0)
+    assert _flag() == 0 and torch.isfinite(xo).all() and torch.isfinite(xn).all()
+    _reset()
+    run(2.0 ** 17, 1.0)                                   # hidden activations ~ 2^17
+    assert _flag() == 1, "hidden activation past 65520 packed without raising the range flag"
+    _reset()
+    xo, _ = run(1.0, 2.0 ** 17)                           # xn = LayerNorm(x_new) * 2^17; the fp32 residual stream itself is fine
+    assert _flag() == 1 and torch.isfinite(xo).all(), "xn past 65520 packed without raising the range flag"
+    _reset()
+
+
+@pytest.mark.parametrize("D", [128, 384, 1024])
+def test_layernorm_output_overflow_raises_the_flag(D):
+    from test_gpu_aux_kernels import run_layernorm
+    g = torch.Generator().manual_seed(25)
+    x = torch.randn(100, D, generator=g)
+    gamma, beta = torch.ones(D), torch.zeros(D)
+    _reset()
+    assert torch.isfinite(run_layernorm(x, gamma, beta, "f16x2", 1, 0)).all() and _flag() == 0
+    run_layernorm(x, gamma * 2.0 ** 17, beta, "f16x2", 1, 0)
+    assert _flag() == 1
+    _reset()
+    assert torch.isfinite(run_layernorm(x, gamma * 2.0 ** 17, beta, "f16x2", 1, 1)).all() and _flag() == 0      # fp32 output: representable
+    assert torch.isfinite(run_layernorm(x, gamma * 2.0 ** 17, beta, "f32", 1, 0)).all() and _flag() == 0
+    _reset()
+
+
+def test_convex_and_max_writers_do_not_raise_at_the_largest_fp16_magnitude():
+    """Attention, FRM vertical, max-pool and ASF output convex combinations or maxima of in-range inputs and cannot overflow: with the
+    blended / pooled values AT +-65504 the flag stays 0 and the output is finite (no false positive at the edge)."""
+    from test_gpu_aux_kernels import run_asf, run_frm, run_maxpool
+    L = _L()
+    g = torch.Generator().manual_seed(26)
+    BIG = 65504.0
+
+    def edge(out, what):
+        assert _flag() == 0, what + ": false positive"
+        assert torch.isfinite(out).all(), what
+        assert BIG * (1 - 1e-3) <= float(out.abs().max()) < 65520.0, (what, float(out.abs().max()))
+        _reset()
+
+    _reset()
+    for B, N, heads in ((2, 100, 4), (1, 640, 2)):        # one pass, and the key-chunk merge of > 512 keys
+        D = heads * 32
+        qkv = torch.randn(B, N, 3 * D, generator=g)
+        sign = torch.where(torch.rand(D, generator=g) < 0.5, -1.0, 1.0)
+        qkv[:, :, 2 * D:] = sign * BIG                    # v: every key holds +-65504 in every channel
+        qkv[:, :, 2 * D + 1::2] = torch.randn(B, N, D // 2, generator=g) * 1000.0
+        out = torch.empty((B, N, D), device="cuda")
+        qd = qkv.cuda()
+        L.check(L.load().ocrvi_test_attention(0, DT["f16x2"], qd.data_ptr(), B, N, heads, out.data_ptr(), 0, None))
+        edge(out.cpu(), f"attention N={N}")
+    for H in (1, 3, 8):
+        B, W, D = 2, 40, 128
+        kv = torch.randn(B * H * W, 2 * D, generator=g)
+        kv[:, D:] = torch.where(torch.rand(D, generator=g) < 0.5, -1.0, 1.0) * BIG
+        edge(run_frm(kv, torch.randn(D, generator=g), B, H, W, D, "f16x2"), f"frm H={H}")
+    x = torch.randn(2, 64, 17, 23, generator=g) * 1000.0
+    x[torch.rand(x.shape, generator=g) < 0.05] = BIG
+    x[torch.rand(x.shape, generator=g) < 0.05] = -BIG
+    x[:, 3] = -BIG                                        # a channel whose every maximum is -65504
+    edge(run_maxpool(x, "f16x2"), "maxpool")
+    ps = [torch.relu(torch.randn(1, 256, 56 >> l, 40 >> l, generator=g)) for l in range(4)]
+    for p in ps:
+        p[:, 8:16] = BIG
+        p[:, 16:24] = -BIG
+    w = torch.randn(4, 1024, generator=g) * (4.0 / 1024) ** 0.5
+    edge(run_asf(ps, w, torch.zeros(4), "f16x2"), "asf")
