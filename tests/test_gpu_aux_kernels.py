@@ -40,17 +40,7 @@ def _h(t):
     return np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float32)
 
 
-def _half_ulp(y, dt):
-    """Half an ulp of element type `dt` at the float64 values y: the error of one round-to-nearest."""
-    a = y.abs().double()
-    e = torch.floor(torch.log2(torch.clamp(a, min=2.0 ** -60)))
-    if dt == "bf16":
-        return torch.exp2(e - 8)                                   # 8 significant bits
-    if dt == "f16":
-        return torch.exp2(torch.clamp(e, min=-14.0) - 11)          # 11 significant bits; subnormal spacing 2^-24 below 2^-14
-    if dt == "f16x2":
-        return torch.clamp(a * 2.0 ** -23, min=2.0 ** -25)
-    return torch.zeros_like(a)
+_half_ulp = R.half_ulp
 
 
 # ------------------------------------------------------------------------------------------------ LayerNorm
