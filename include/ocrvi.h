@@ -174,6 +174,51 @@ int ocrvi_resize_normalize_pages(int device, const int64_t* pages, int n, int H,
 int ocrvi_crop_resize_normalize_pages(int device, const int64_t* pages, int n_pages, const int32_t* boxes, int B, int out_h, int out_w,
                                       float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Four-point page rectification: the geometric half of the reference's stage 1, `--preprocess` (src/pipeline/pipeline2.py:291-302 ->
+ * preprocess_image, src/preprocess/scanner.py:168-196 -> four_point_transform, scanner.py:29-53).  Finding the document's corners (the
+ * rembg network, scanner.py:78-132) is the caller's business; enhance_document (scanner.py:55-76) is not built (the pipeline passes
+ * enhance=False).
+ * ------------------------------------------------------------------------------------------------ */
+/* Host only, needs no GPU.  Replaces order_points (scanner.py:13-27), the output size (scanner.py:36-42), the destination corners
+ * (scanner.py:44-48) and cv2.getPerspectiveTransform (scanner.py:50).  pts: four (x, y) corners of the document in the image, any order.
+ *   order    x + y and y - x in float64; top-left = argmin of the sum, bottom-right = argmax, top-right = argmin of the difference,
+ *            bottom-left = argmax; the first index wins ties (numpy).  The ordered corners are kept as float32.
+ *   size     the four side lengths in float32 throughout (differences, squares, sum, correctly rounded sqrt), each truncated by int();
+ *            *out_w = max(top, bottom), *out_h = max(left, right).
+ *   corners  the destination corners (0,0), (w-1,0), (w-1,h-1), (0,h-1) as float32.
+ *   m_fwd    [9] row-major, source -> destination (may be NULL): the 8 x 8 linear system of the four correspondences with h22 = 1, solved
+ *            in double by Gaussian elimination with partial pivoting.
+ *   m_inv    [9] destination -> source, what the warp entries below take: adjugate of m_fwd over its determinant, in double.
+ * OCRVI_EINVAL with a message when out_w < 1 or out_h < 1, when the system is singular (three of the ordered corners on one line, or
+ * two of them equal) or when the determinant is 0, and for non-finite corners.  The ordering can pick one point twice -- the diamond
+ * (10,0) (20,10) (10,20) (0,10) orders to (10,0) (10,0) (20,10) (10,20) --; the reference then hands cv2 a degenerate system, this
+ * entry refuses. */
+int ocrvi_four_point_transform(const double* pts /*[4][2]*/, double* m_fwd /*[9]*/, double* m_inv /*[9]*/, int32_t* out_w, int32_t* out_h);
+/* Replaces cv2.warpPerspective(image, M, (w, h)) as four_point_transform calls it (scanner.py:51: bilinear, constant border 0):
+ * src uint8 HWC [src_h,src_w,3] -> dst uint8 HWC [dst_h,dst_w,3], both DEVICE; m_inv_host: HOST [9] destination -> source (it is copied
+ * into the launch: free again on return).  Enqueue-only on `stream`, graph-capturable: no allocation, no synchronisation.
+ * The arithmetic is the library's own definition, modelled on OpenCV's classic fixed-point bilinear remap.  OpenCV's own implementation
+ * differs between versions and between its block sizes and cv2 is absent from the build container: parity with cv2 is UNPINNED, as for
+ * ocrvi_resize_u8.  For destination pixel (x, y) and m = m_inv:
+ *   X0 = (m0 x + m1 y) + m2,  Y0 = (m3 x + m4 y) + m5,  W0 = (m6 x + m7 y) + m8   IEEE double, in this order, no fused multiply-add
+ *   s  = W0 != 0 ? 32.0 / W0 : 0.0
+ *   X  = rint(clamp(X0 s, -2147483648.0, 2147483647.0)) as int32, round half to even (a NaN product counts as the lower bound); Y likewise
+ *   sx = X >> 5 (arithmetic), ax = X & 31; sy, ay likewise
+ *   weights (32-ax)(32-ay) 32, ax (32-ay) 32, (32-ax) ay 32, ax ay 32 (sum 32768) on the taps (sy, sx), (sy, sx+1), (sy+1, sx), (sy+1, sx+1);
+ *   a tap outside [0,src_h) x [0,src_w) contributes 0 (decided on the integers: no address is formed for it)
+ *   out_c = (sum w p_c + 16384) >> 15
+ * No alignment is asked of src or dst (a dst that is a multiple of 4 is written in 4-byte words). */
+int ocrvi_warp_perspective_u8(int device, const uint8_t* src, int src_h, int src_w, const double* m_inv_host /*[9]*/,
+                              uint8_t* dst, int dst_h, int dst_w, void* stream);
+/* The same warp for n pages in one launch (1 <= n <= 65535): src_pages and dst_pages are page tables as above (OCRVI_PAGE_ENTRY), m_inv
+ * DEVICE float64 [n][9]; page i of dst_pages = ocrvi_warp_perspective_u8 of page i of src_pages under matrix i, bit for bit.  Tables,
+ * matrices and pages are read when the kernel runs: a captured graph survives moved pages and rewritten tables and matrices.  A
+ * destination whose source entry is invalid is filled with 0; an invalid destination entry is skipped and never dereferenced.
+ * Destination addresses need no alignment.  Enqueue-only on `stream`. */
+int ocrvi_warp_perspective_pages(int device, const int64_t* src_pages, const int64_t* dst_pages, const double* m_inv /*DEVICE [n][9]*/, int n,
+                                 void* stream);
+
 /* Replaces DBPostProcessor(thresh, box_thresh, max_candidates, unclip_ratio).__call__ with .min_area (src/det/test.py:46-106) on a HOST
  * probability map prob[H*W] (the reference also runs this stage on the CPU after `.cpu().numpy()`, pipeline2.py:320-321).
  * Output: the unclipped polygons as int32 (x, y) pairs in points[2*cap_points]; box i owns points box_offsets[i] .. box_offsets[i+1]

@@ -15,7 +15,7 @@ DTYPES = {"f32": OCRVI_F32, "fp32": OCRVI_F32, "float32": OCRVI_F32, "bf16": OCR
           "f16": OCRVI_F16, "fp16": OCRVI_F16, "float16": OCRVI_F16,
           # fp32-equivalent arithmetic on the 16-bit matrix pipe: every operand kept as two fp16 halves (include/ocrvi.h)
           "f16x2": OCRVI_F16X2}
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 EXPORTS = [
     "ocrvi_last_error", "ocrvi_abi_version",
@@ -28,6 +28,7 @@ EXPORTS = [
     "ocrvi_det_status", "ocrvi_rec_status", "ocrvi_range_reset", "ocrvi_range_flag",
     "ocrvi_resize_normalize_pages", "ocrvi_crop_resize_normalize_pages", "ocrvi_db_boxes_pages",
     "ocrvi_det_binary_workspace_bytes", "ocrvi_det_forward_binary",
+    "ocrvi_four_point_transform", "ocrvi_warp_perspective_u8", "ocrvi_warp_perspective_pages",
     "ocrvi_test_layernorm", "ocrvi_test_frm_vertical", "ocrvi_test_asf", "ocrvi_test_maxpool", "ocrvi_test_db_maps", "ocrvi_test_ctc_logsoftmax",
 ]
 PAGE_ENTRY = 4          # int64 fields of one page-table entry: (device address, height, width, 0) -- OCRVI_PAGE_ENTRY
@@ -90,6 +91,9 @@ def load() -> C.CDLL:
                                          vp, vp, i32, vp, i32]
     lib.ocrvi_resize_normalize_pages.argtypes = [i32, vp, i32, i32, i32, f32p, vp]
     lib.ocrvi_crop_resize_normalize_pages.argtypes = [i32, vp, i32, i32p, i32, i32, i32, f32p, vp]
+    lib.ocrvi_four_point_transform.argtypes = [vp, vp, vp, i32p, i32p]
+    lib.ocrvi_warp_perspective_u8.argtypes = [i32, vp, i32, i32, vp, vp, i32, i32, vp]
+    lib.ocrvi_warp_perspective_pages.argtypes = [i32, vp, vp, vp, i32, vp]
     lib.ocrvi_db_boxes_pages.argtypes = [vp, i32, i32, i32, C.c_float, C.c_float, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp,
                                          vp, i32, vp, vp, vp, i32, vp, vp, i32]
     lib.ocrvi_test_deform_conv.argtypes = [i32, i32, f32p, f32p, f32p, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32p, i32,

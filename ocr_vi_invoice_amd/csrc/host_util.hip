@@ -491,4 +491,4 @@ extern "C" int ocrvi_test_pack_f16x2(const float* src, size_t n, void* dst, floa
 }
 
 extern "C" const char* ocrvi_last_error(void) { return ocrvi::last_error_cstr(); }
-extern "C" int ocrvi_abi_version(void) { return 4; }
+extern "C" int ocrvi_abi_version(void) { return 5; }

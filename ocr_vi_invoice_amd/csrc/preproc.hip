@@ -6,6 +6,11 @@
 // in int32, vertical pass ((b0*(r0>>4))>>16 + (b1*(r1>>4))>>16 + 2) >> 2, and the exact-2x-downscale special case that
 // OpenCV routes to the 2x2 box filter.  cv2 is absent from the build container: parity with cv2 itself is UNPINNED; the
 // CPU oracle (oracle/preproc_cpu.py) restates the same published algorithm independently in numpy.
+#include <math.h>
+
+#include <algorithm>
+#include <cmath>
+
 #include "common.h"
 
 namespace ocrvi {
@@ -248,6 +253,100 @@ __global__ void crop_resize_normalize_pages_kernel(const int64_t* __restrict__ t
     }
 }
 
+// ---------------------------------------------------------------- four-point rectification (src/preprocess/scanner.py:29-53)
+// The perspective warp behind four_point_transform's cv2.warpPerspective call (scanner.py:51), as include/ocrvi.h states it: the inverse
+// map in IEEE double without fused multiply-adds, source coordinates quantised to 1/32 pixel, 15-bit bilinear weights, constant border 0.
+// OpenCV's own code differs between versions and block sizes and cv2 is absent from the build container: parity with cv2 is UNPINNED,
+// as for the resize above; tests/warp_ref.py restates the same definition in numpy and the kernel is bit-equal to it.
+struct WarpMat { double m[9]; };
+
+// one source coordinate in 1/32 pixel: rint(clamp(v0 * s)) as int32 (a NaN product counts as the lower bound)
+__device__ __forceinline__ int warp_coord(double v0, double s) {
+#pragma clang fp contract(off)
+    double v = v0 * s;
+    if (!(v >= -2147483648.0)) v = -2147483648.0;
+    if (v > 2147483647.0) v = 2147483647.0;
+    return (int)rint(v);     // round half to even; exact after the clamp
+}
+
+// destination pixel (x, y) of the warp of a valid sh x sw page: the three channel values
+__device__ __forceinline__ void warp_px(const uint8_t* __restrict__ src, int sh, int sw, const WarpMat& M, int x, int y, int v[3]) {
+#pragma clang fp contract(off)
+    const double dx = (double)x, dy = (double)y;
+    const double X0 = (M.m[0] * dx + M.m[1] * dy) + M.m[2];
+    const double Y0 = (M.m[3] * dx + M.m[4] * dy) + M.m[5];
+    const double W0 = (M.m[6] * dx + M.m[7] * dy) + M.m[8];
+    const double s = (W0 != 0.0) ? 32.0 / W0 : 0.0;
+    const int X = warp_coord(X0, s), Y = warp_coord(Y0, s);
+    const int sx = X >> 5, sy = Y >> 5, ax = X & 31, ay = Y & 31;
+    // the range is decided on the integers (sx is up to +-2^26) before any address is formed; sx + 1 and sy + 1 cannot overflow
+    const bool x0in = (unsigned)sx < (unsigned)sw, x1in = (unsigned)(sx + 1) < (unsigned)sw;
+    const bool y0in = (unsigned)sy < (unsigned)sh, y1in = (unsigned)(sy + 1) < (unsigned)sh;
+    v[0] = v[1] = v[2] = 0;
+    if (!((x0in || x1in) && (y0in || y1in))) return;
+    const int w00 = (32 - ax) * (32 - ay) * 32, w01 = ax * (32 - ay) * 32, w10 = (32 - ax) * ay * 32, w11 = ax * ay * 32;
+    const size_t rs = (size_t)sw * 3;
+    int acc[3] = {16384, 16384, 16384};
+    if (y0in) {
+        const uint8_t* r = src + (size_t)sy * rs;
+        if (x0in) { const uint8_t* p = r + (size_t)sx * 3; acc[0] += w00 * p[0]; acc[1] += w00 * p[1]; acc[2] += w00 * p[2]; }
+        if (x1in) { const uint8_t* p = r + (size_t)(sx + 1) * 3; acc[0] += w01 * p[0]; acc[1] += w01 * p[1]; acc[2] += w01 * p[2]; }
+    }
+    if (y1in) {
+        const uint8_t* r = src + (size_t)(sy + 1) * rs;
+        if (x0in) { const uint8_t* p = r + (size_t)sx * 3; acc[0] += w10 * p[0]; acc[1] += w10 * p[1]; acc[2] += w10 * p[2]; }
+        if (x1in) { const uint8_t* p = r + (size_t)(sx + 1) * 3; acc[0] += w11 * p[0]; acc[1] += w11 * p[1]; acc[2] += w11 * p[2]; }
+    }
+    v[0] = acc[0] >> 15; v[1] = acc[1] >> 15; v[2] = acc[2] >> 15;
+}
+
+// One page: groups first, first + stride, ... of 4 consecutive pixels of the destination taken as one flat run of dh * dw pixels (a
+// group may cross a row end).  A group is 12 bytes at dst + 12 g, so whether it can go out as three 4-byte words depends on the page's
+// base address alone, whatever the row length: a wave then writes 768 contiguous bytes.  A base that is no multiple of 4, and the
+// last, partial group, are written byte by byte.  sh == 0 (an invalid source) writes zeros.
+__device__ __forceinline__ void warp_page(const uint8_t* __restrict__ src, int sh, int sw, const WarpMat& M, uint8_t* __restrict__ dst, int dh,
+                                          int dw, size_t first, size_t stride) {
+    const size_t npx = (size_t)dh * dw, groups = (npx + 3) >> 2;
+    const bool words = (((uintptr_t)dst) & 3) == 0;
+    for (size_t g = first; g < groups; g += stride) {
+        const size_t i0 = g * 4;
+        int y = (int)(i0 / (size_t)dw), x = (int)(i0 - (size_t)y * dw);
+        const int cnt = (int)min((size_t)4, npx - i0);
+        uint32_t w[3] = {0u, 0u, 0u};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            int v[3] = {0, 0, 0};
+            if (k < cnt && sh != 0) warp_px(src, sh, sw, M, x, y, v);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) w[(3 * k + c) >> 2] |= (uint32_t)v[c] << (8 * ((3 * k + c) & 3));
+            if (++x == dw) { x = 0; ++y; }
+        }
+        uint8_t* o = dst + i0 * 3;
+        if (words && cnt == 4) {
+            ((uint32_t*)o)[0] = w[0]; ((uint32_t*)o)[1] = w[1]; ((uint32_t*)o)[2] = w[2];
+        } else {
+            for (int j = 0; j < cnt * 3; ++j) o[j] = (uint8_t)(w[j >> 2] >> (8 * (j & 3)));
+        }
+    }
+}
+
+__global__ void warp_perspective_u8_kernel(const uint8_t* __restrict__ src, int sh, int sw, WarpMat M, uint8_t* __restrict__ dst, int dh, int dw) {
+    warp_page(src, sh, sw, M, dst, dh, dw, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
+}
+
+// blockIdx.y = page: both tables and the page's matrix are read here, when the kernel runs
+__global__ void warp_perspective_pages_kernel(const int64_t* __restrict__ src_table, const int64_t* __restrict__ dst_table,
+                                              const double* __restrict__ m_inv) {
+    const int pg = blockIdx.y;
+    const PageRef d = load_page(dst_table, pg);
+    if (d.h == 0) return;                          // an invalid destination entry is skipped, never dereferenced
+    const PageRef s = load_page(src_table, pg);    // invalid source: h = 0 -> the destination is filled with 0
+    WarpMat M;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) M.m[k] = m_inv[(size_t)pg * 9 + k];
+    warp_page(s.p, s.h, s.w, M, (uint8_t*)d.p, d.h, d.w, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
+}
+
 }  // namespace ocrvi
 
 using namespace ocrvi;
@@ -306,6 +405,127 @@ extern "C" int ocrvi_crop_resize_normalize_pages(int device, const int64_t* page
     const size_t total = (size_t)B * out_h * out_w;
     const int grid = (int)std::min<size_t>((total + 255) / 256, 16384);
     hipLaunchKernelGGL(crop_resize_normalize_pages_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, pages, n_pages, boxes, B, out_h, out_w, out);
+    OCRVI_HIP(hipGetLastError());
+    return OCRVI_OK;
+}
+
+// ---------------------------------------------------------------- four-point rectification: host geometry and the two warp entries
+// src/preprocess/scanner.py:13-53 restated: order_points (:13-27), the output size from the float32 side lengths (:36-42), the destination
+// corners (:44-48) and cv2.getPerspectiveTransform (:50) as the 8 x 8 system of the four correspondences with h22 = 1.
+static bool three_collinear(const double (*p)[2]) {
+    for (int a = 0; a < 4; ++a) {          // the triple that leaves corner a out
+        const double* q[3];
+        for (int i = 0, k = 0; i < 4; ++i) if (i != a) q[k++] = p[i];
+        const double ux = q[1][0] - q[0][0], uy = q[1][1] - q[0][1], vx = q[2][0] - q[0][0], vy = q[2][1] - q[0][1];
+        const double cross = ux * vy - uy * vx;
+        if (!(fabs(cross) > 1e-12 * sqrt((ux * ux + uy * uy) * (vx * vx + vy * vy)))) return true;
+    }
+    return false;
+}
+
+extern "C" int ocrvi_four_point_transform(const double* pts, double* m_fwd, double* m_inv, int32_t* out_w, int32_t* out_h) {
+#pragma clang fp contract(off)
+    OCRVI_CHECK(pts && m_inv && out_w && out_h, OCRVI_EINVAL, "four_point_transform: null argument");
+    for (int i = 0; i < 8; ++i) OCRVI_CHECK(std::isfinite(pts[i]), OCRVI_EINVAL, "four_point_transform: corner %d is not finite", i / 2);
+    // order_points: sums and differences in float64, first index wins ties (numpy argmin / argmax), corners kept as float32
+    int tl = 0, br = 0, tr = 0, bl = 0;
+    for (int i = 1; i < 4; ++i) {
+        const double s = pts[2 * i] + pts[2 * i + 1], d = pts[2 * i + 1] - pts[2 * i];
+        if (s < pts[2 * tl] + pts[2 * tl + 1]) tl = i;
+        if (s > pts[2 * br] + pts[2 * br + 1]) br = i;
+        if (d < pts[2 * tr + 1] - pts[2 * tr]) tr = i;
+        if (d > pts[2 * bl + 1] - pts[2 * bl]) bl = i;
+    }
+    const int order[4] = {tl, tr, br, bl};
+    float rect[4][2];
+    for (int i = 0; i < 4; ++i) {
+        rect[i][0] = (float)pts[2 * order[i]];
+        rect[i][1] = (float)pts[2 * order[i] + 1];
+        OCRVI_CHECK(std::isfinite(rect[i][0]) && std::isfinite(rect[i][1]), OCRVI_EINVAL, "four_point_transform: corner %d overflows float32", order[i]);
+    }
+    // side lengths entirely in float32 (numpy on the float32 rect), truncated by int()
+    auto side = [&](int a, int b) -> float {
+        const float dx = rect[a][0] - rect[b][0], dy = rect[a][1] - rect[b][1];
+        const float xx = dx * dx, yy = dy * dy;
+        return sqrtf(xx + yy);
+    };
+    const float top = side(1, 0), bottom = side(2, 3), left = side(0, 3), right = side(1, 2);
+    OCRVI_CHECK(top < 2147483648.f && bottom < 2147483648.f && left < 2147483648.f && right < 2147483648.f, OCRVI_EINVAL,
+                "four_point_transform: a side of the quad is longer than an int32");
+    const int w = std::max((int)top, (int)bottom), h = std::max((int)left, (int)right);
+    OCRVI_CHECK(w >= 1 && h >= 1, OCRVI_EINVAL, "four_point_transform: the quad rectifies to %d x %d pixels (a side shorter than one pixel)", w, h);
+    const float dstf[4][2] = {{0.f, 0.f}, {(float)(w - 1), 0.f}, {(float)(w - 1), (float)(h - 1)}, {0.f, (float)(h - 1)}};
+    double sp[4][2], dp[4][2];
+    for (int i = 0; i < 4; ++i) { sp[i][0] = rect[i][0]; sp[i][1] = rect[i][1]; dp[i][0] = dstf[i][0]; dp[i][1] = dstf[i][1]; }
+    // (the ordering can pick one point twice -- a diamond does --; the reference hands cv2 the degenerate system, the library refuses)
+    OCRVI_CHECK(!three_collinear(sp), OCRVI_EINVAL, "four_point_transform: singular system: three of the ordered corners (%g,%g) (%g,%g) (%g,%g) (%g,%g) "
+                "lie on one line or coincide", sp[0][0], sp[0][1], sp[1][0], sp[1][1], sp[2][0], sp[2][1], sp[3][0], sp[3][1]);
+    OCRVI_CHECK(!three_collinear(dp), OCRVI_EINVAL, "four_point_transform: singular system: a %d x %d output has coinciding corners", w, h);
+    // rows i / i + 4:  x h0 + y h1 + h2 - x u h6 - y u h7 = u,   x h3 + y h4 + h5 - x v h6 - y v h7 = v
+    double A[8][9];
+    for (int i = 0; i < 4; ++i) {
+        const double x = sp[i][0], y = sp[i][1], u = dp[i][0], v = dp[i][1];
+        const double r0[9] = {x, y, 1, 0, 0, 0, -x * u, -y * u, u}, r1[9] = {0, 0, 0, x, y, 1, -x * v, -y * v, v};
+        for (int j = 0; j < 9; ++j) { A[i][j] = r0[j]; A[i + 4][j] = r1[j]; }
+    }
+    for (int c = 0; c < 8; ++c) {          // Gaussian elimination with partial pivoting
+        int piv = c;
+        for (int r = c + 1; r < 8; ++r) if (fabs(A[r][c]) > fabs(A[piv][c])) piv = r;
+        OCRVI_CHECK(A[piv][c] != 0.0 && std::isfinite(A[piv][c]), OCRVI_EINVAL, "four_point_transform: singular system (no pivot in column %d)", c);
+        if (piv != c) for (int j = 0; j < 9; ++j) std::swap(A[c][j], A[piv][j]);
+        for (int r = c + 1; r < 8; ++r) {
+            const double f = A[r][c] / A[c][c];
+            if (f == 0.0) continue;
+            for (int j = c; j < 9; ++j) A[r][j] -= f * A[c][j];
+        }
+    }
+    double hv[9];
+    for (int r = 7; r >= 0; --r) {
+        double acc = A[r][8];
+        for (int j = r + 1; j < 8; ++j) acc -= A[r][j] * hv[j];
+        hv[r] = acc / A[r][r];
+        OCRVI_CHECK(std::isfinite(hv[r]), OCRVI_EINVAL, "four_point_transform: singular system (unknown %d is not finite)", r);
+    }
+    hv[8] = 1.0;
+    // inverse: adjugate over determinant
+    const double *m = hv;
+    const double c00 = m[4] * m[8] - m[5] * m[7], c01 = m[5] * m[6] - m[3] * m[8], c02 = m[3] * m[7] - m[4] * m[6];
+    const double det = m[0] * c00 + m[1] * c01 + m[2] * c02;
+    OCRVI_CHECK(det != 0.0 && std::isfinite(det), OCRVI_EINVAL, "four_point_transform: the forward matrix has determinant %g", det);
+    const double adj[9] = {c00, m[2] * m[7] - m[1] * m[8], m[1] * m[5] - m[2] * m[4],
+                           c01, m[0] * m[8] - m[2] * m[6], m[2] * m[3] - m[0] * m[5],
+                           c02, m[1] * m[6] - m[0] * m[7], m[0] * m[4] - m[1] * m[3]};
+    for (int i = 0; i < 9; ++i) {
+        const double q = adj[i] / det;
+        OCRVI_CHECK(std::isfinite(q), OCRVI_EINVAL, "four_point_transform: the inverse matrix is not finite (determinant %g)", det);
+        m_inv[i] = q;
+    }
+    if (m_fwd) for (int i = 0; i < 9; ++i) m_fwd[i] = hv[i];
+    *out_w = w;
+    *out_h = h;
+    return OCRVI_OK;
+}
+
+extern "C" int ocrvi_warp_perspective_u8(int device, const uint8_t* src, int src_h, int src_w, const double* m_inv_host, uint8_t* dst, int dst_h,
+                                         int dst_w, void* stream) {
+    OCRVI_CHECK(src && dst && m_inv_host && src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0, OCRVI_EINVAL, "warp_perspective_u8: bad argument");
+    DeviceGuard dg(device);  // the caller's current device is restored on return
+    OCRVI_HIP(dg.err);
+    WarpMat M;               // passed by value: the host matrix is free again when the call returns
+    for (int i = 0; i < 9; ++i) M.m[i] = m_inv_host[i];
+    const size_t groups = ((size_t)dst_h * dst_w + 3) / 4;
+    const int grid = (int)std::min<size_t>((groups + 255) / 256, 16384);
+    hipLaunchKernelGGL(warp_perspective_u8_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, src_h, src_w, M, dst, dst_h, dst_w);
+    OCRVI_HIP(hipGetLastError());
+    return OCRVI_OK;
+}
+
+extern "C" int ocrvi_warp_perspective_pages(int device, const int64_t* src_pages, const int64_t* dst_pages, const double* m_inv, int n, void* stream) {
+    OCRVI_CHECK(src_pages && dst_pages && m_inv && n > 0 && n <= 65535, OCRVI_EINVAL, "warp_perspective_pages: bad argument (1 <= n <= 65535)");
+    DeviceGuard dg(device);  // the caller's current device is restored on return
+    OCRVI_HIP(dg.err);
+    // the page sizes live in device memory: a fixed 1024 blocks per page stride over whatever size the table holds when the kernel runs
+    hipLaunchKernelGGL(warp_perspective_pages_kernel, dim3(1024, n), dim3(256), 0, (hipStream_t)stream, src_pages, dst_pages, m_inv);
     OCRVI_HIP(hipGetLastError());
     return OCRVI_OK;
 }

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .pipeline import DBPostProcessor, db_boxes_pages
+from .pipeline import DBPostProcessor, db_boxes_pages, four_point_geometry
 
 _ARENA_ALIGN = 256
 _STREAMS: Dict[int, Tuple[torch.cuda.Stream, torch.cuda.Stream]] = {}
@@ -56,6 +56,28 @@ def plan_buckets(sizes: Sequence[Tuple[int, int]], det_size: int):
     return shapes, scales, buckets
 
 
+def plan_rectified(sizes: Sequence[Tuple[int, int]], quads, det_size: int):
+    """``plan_buckets`` for pages of which some are rectified first (``Engine.run(pages, quads)``): page i with ``quads[i]`` (four (x, y)
+    corners, any order) is bucketed by the size ``four_point_transform`` (src/preprocess/scanner.py:29-53) gives it, a page with ``None`` by
+    its own.  Host only.  Returns (rectified sizes [(h, w)], m_inv [None or float64 [9], destination -> source], shapes, scales, buckets),
+    the last three as ``plan_buckets`` returns them for the rectified sizes.  ValueError naming the page for a quad that is not four finite
+    (x, y) points or that the geometry refuses (``ocrvi_four_point_transform``: shorter than a pixel, degenerate after ordering)."""
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    quads = [None] * len(sizes) if quads is None else list(quads)
+    if len(quads) != len(sizes):
+        raise ValueError(f"quads: {len(quads)} entries for {len(sizes)} pages")
+    out_sizes, mats = [], []
+    for i, (hw, q) in enumerate(zip(sizes, quads)):
+        if q is None:
+            out_sizes.append(hw)
+            mats.append(None)
+            continue
+        _, m_inv, w, h = four_point_geometry(q, what=f"page {i}: quad")
+        out_sizes.append((h, w))
+        mats.append(m_inv.reshape(9))
+    return (out_sizes, mats) + plan_buckets(out_sizes, det_size)
+
+
 def _usable_cores(cap: int = 16) -> int:
     try:
         n = len(os.sched_getaffinity(0))
@@ -75,6 +97,9 @@ class Engine:
     captured graphs.  ``post_threads``: host threads of the box stage (0 = the cores this process may use, at most 16).
     ``binary_head=True``: the detector runs ``ocrvi_det_forward_binary`` (the binarise branch alone; the same map in f32 / f16x2, about 8 % fewer
     detector FLOPs) with its own, never larger workspace; everything after the map is unchanged.
+    ``run(pages, quads)``: ``quads[i]`` is ``None`` or the four corners of page i's document; such a page is rectified on the device
+    (``ocrvi_warp_perspective_pages`` into its arena slot, ahead of its chunk's detector launch) and everything downstream sees the
+    rectified page, as ``detect_and_recognize(page, ..., quad=quads[i])`` does: boxes are in its coordinates.
     The captured graphs hold the models' weights as they were: after reloading a model's weights, build a new Engine."""
 
     def __init__(self, det_model, rec_model, post_processor: DBPostProcessor, det_size: int = 960, rec_size: Tuple[int, int] = (32, 256),
@@ -136,6 +161,13 @@ class Engine:
         self.arena = torch.empty(0, dtype=torch.uint8, **d)
         self.h_stage = torch.empty(0, dtype=torch.uint8)
         self.h_table = torch.zeros((self.max_pages, _lib.PAGE_ENTRY), dtype=torch.int64).pin_memory()
+        # ---- rectification (run(pages, quads)): per detector chunk, the raw pixels of its quad pages that came from the host (device region
+        #      + two pinned slots, grown on demand) and one block of int64 words per chunk = source table | destination table | matrices
+        self.d_raw = torch.empty(0, dtype=torch.uint8, **d)
+        self.h_raw = [torch.empty(0, dtype=torch.uint8), torch.empty(0, dtype=torch.uint8)]
+        words = self.det_chunk * (2 * _lib.PAGE_ENTRY + 9)
+        self.d_warp = torch.zeros(words, dtype=torch.int64, **d)
+        self.h_warp = [torch.zeros(words, dtype=torch.int64).pin_memory() for _ in range(2)]
         # one stream pair per device for every engine of the process: each new HIP stream takes the next hardware queue round-robin
         if self.devi not in _STREAMS:
             _STREAMS[self.devi] = (torch.cuda.Stream(self.dev), torch.cuda.Stream(self.dev))
@@ -214,19 +246,50 @@ class Engine:
             raise ValueError(f"page {i}: expected an RGB uint8 HxWx3 array, got dtype {p.dtype} shape {tuple(p.shape)}")
         return int(p.shape[0]), int(p.shape[1])
 
-    def _stage(self, pages, wave, lo, hi):
-        """Pages wave[lo:hi] (consecutive arena slots) -> the arena, on the detector stream."""
+    def _stage(self, pages, wave, lo, hi, s=0):
+        """Pages wave[lo:hi] (consecutive arena slots) -> the arena, on the detector stream.  A page with a quad is warped into its slot
+        (one ``ocrvi_warp_perspective_pages`` launch per chunk) from its raw pixels: a device page where it lies, a host page through
+        pinned slot ``s`` and the raw region (chunk c - 2, the previous user of slot ``s``, has been waited for by now)."""
+        PE, dc = _lib.PAGE_ENTRY, self.det_chunk
+        tabs, roff, n_warp = None, 0, 0
         for slot in range(lo, hi):
             i = wave[slot]
             p, off, nb = pages[i], self._offs[slot], self._nbytes[slot]
             dst = self.arena[off:off + nb]
-            if isinstance(p, torch.Tensor) and p.is_cuda:
+            if self._mats[i] is not None:
+                if tabs is None:
+                    tabs = self.h_warp[s].numpy()
+                    tabs[:] = 0                    # rows of pages without a quad stay invalid: the kernel skips them
+                rh, rw = self._raw_sizes[i]
+                if isinstance(p, torch.Tensor) and p.is_cuda:
+                    src = p if p.is_contiguous() else p.contiguous()
+                    self._keep.append(src)         # alive until the wave has drained
+                    src_ptr = src.data_ptr()
+                else:
+                    src = p.numpy() if isinstance(p, torch.Tensor) else p
+                    rb = rh * rw * 3
+                    np.copyto(self.h_raw[s][roff:roff + rb].numpy().reshape(src.shape), src)
+                    self.d_raw[roff:roff + rb].copy_(self.h_raw[s][roff:roff + rb], non_blocking=True)
+                    src_ptr = self.d_raw.data_ptr() + roff
+                    roff += (rb + _ARENA_ALIGN - 1) // _ARENA_ALIGN * _ARENA_ALIGN
+                k = slot - lo
+                tabs[k * PE:k * PE + PE] = (src_ptr, rh, rw, 0)
+                tabs[(dc + k) * PE:(dc + k) * PE + PE] = (dst.data_ptr(), self._sizes[i][0], self._sizes[i][1], 0)
+                tabs[2 * dc * PE + 9 * k:2 * dc * PE + 9 * k + 9] = self._mats[i].view(np.int64)
+                n_warp += 1
+            elif isinstance(p, torch.Tensor) and p.is_cuda:
                 dst.copy_(p.contiguous().view(-1), non_blocking=True)
             else:
                 src = p.numpy() if isinstance(p, torch.Tensor) else p
                 stage = self.h_stage[off:off + nb].numpy()
                 np.copyto(stage.reshape(src.shape), src)
                 dst.copy_(self.h_stage[off:off + nb], non_blocking=True)
+        if n_warp:
+            self.d_warp.copy_(self.h_warp[s], non_blocking=True)
+            base = self.d_warp.data_ptr()
+            _lib.check(self.lib.ocrvi_warp_perspective_pages(self.devi, base, base + dc * PE * 8, base + 2 * dc * PE * 8, hi - lo,
+                                                             self.s_det.cuda_stream))
+            self.stats["rectified"] += n_warp
 
     # ------------------------------------------------------------------------------------------------ recogniser batches
     def _launch_rec(self, rows, tags):
@@ -292,7 +355,7 @@ class Engine:
         idx = wave[lo:hi]
         t0 = time.perf_counter()
         with torch.cuda.stream(self.s_det):
-            self._stage(pages, wave, lo, hi)
+            self._stage(pages, wave, lo, hi, s)
             self.d_det_table[:n].copy_(self.h_table[lo:hi], non_blocking=True)
             self._run_det(n, H, W)
             if self.prob_hook is not None:
@@ -313,7 +376,8 @@ class Engine:
         self._offs, self._nbytes = offs, nbytes
         if self.arena.numel() < off:               # (the previous wave has drained: nothing reads the old arena any more)
             self.arena = torch.empty(off, dtype=torch.uint8, device=self.dev)
-        if any(not (isinstance(pages[i], torch.Tensor) and pages[i].is_cuda) for i in wave) and self.h_stage.numel() < off:
+        on_host = [not (isinstance(pages[i], torch.Tensor) and pages[i].is_cuda) for i in wave]
+        if any(h and self._mats[i] is None for h, i in zip(on_host, wave)) and self.h_stage.numel() < off:
             self.h_stage = torch.empty(off, dtype=torch.uint8).pin_memory()
         tab = self.h_table.numpy()
         tab[:] = 0
@@ -331,6 +395,14 @@ class Engine:
                 hi += 1
             chunks.append((lo, hi, shape))
             lo = hi
+        # the raw region: the largest chunk's host pages with a quad (per chunk, not per wave: 256 raw 12-megapixel pages would be 9 GB)
+        raw = 0
+        for lo, hi, _ in chunks:
+            raw = max(raw, sum((self._raw_sizes[wave[k]][0] * self._raw_sizes[wave[k]][1] * 3 + _ARENA_ALIGN - 1) // _ARENA_ALIGN * _ARENA_ALIGN
+                               for k in range(lo, hi) if on_host[k] and self._mats[wave[k]] is not None))
+        if self.d_raw.numel() < raw:               # (the previous wave has drained)
+            self.d_raw = torch.empty(raw, dtype=torch.uint8, device=self.dev)
+            self.h_raw = [torch.empty(raw, dtype=torch.uint8).pin_memory() for _ in range(2)]
         pending = collections.deque()
         for c, (lo, hi, shape) in enumerate(chunks):
             if len(pending) == 2:                  # its pinned map slot is the one chunk c reuses
@@ -346,21 +418,24 @@ class Engine:
             self._decode_oldest()
         self.s_det.synchronize()
         self.s_rec.synchronize()                   # (the table upload, even when the wave produced no crop)
+        self._keep = []
 
     # ------------------------------------------------------------------------------------------------ public
-    def run(self, pages: Sequence) -> List[Tuple[list, list, list]]:
+    def run(self, pages: Sequence, quads: Sequence = None) -> List[Tuple[list, list, list]]:
         pages = list(pages)
-        sizes = [self._check_page(i, p) for i, p in enumerate(pages)]
-        shapes, scales, buckets = plan_buckets(sizes, self.det_size)     # raises before any GPU work
+        raw_sizes = [self._check_page(i, p) for i, p in enumerate(pages)]
+        # (every ValueError -- pages, quads, sizes that round to 0 -- is raised here, before any GPU work)
+        sizes, mats, shapes, scales, buckets = plan_rectified(raw_sizes, quads, self.det_size)
         for i, (h, w) in enumerate(shapes):
             if h > self.L or w > self.L:
                 raise RuntimeError(f"page {i}: bucket {h}x{w} exceeds the {self.L}x{self.L} the workspace was sized for")
         self.stats = {"pages": len(pages), "buckets": {f"{h}x{w}": len(v) for (h, w), v in buckets.items()}, "crops": 0, "rec_batches": 0,
-                      "launch_s": 0.0, "det_wait_s": 0.0, "post_s": 0.0, "rec_wait_s": 0.0}
+                      "rectified": 0, "launch_s": 0.0, "det_wait_s": 0.0, "post_s": 0.0, "rec_wait_s": 0.0}
         if not pages:
             return []
         t_start = time.perf_counter()
         self._sizes, self._shapes, self._scales = sizes, shapes, scales
+        self._raw_sizes, self._mats, self._keep = raw_sizes, mats, []
         self._boxes, self._scores, self._texts = [None] * len(pages), [None] * len(pages), [None] * len(pages)
         self._pend_rects, self._pend_tags = [], []
         self._rec_inflight, self._rec_slot = collections.deque(), 0

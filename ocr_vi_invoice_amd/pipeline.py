@@ -3,7 +3,8 @@
 Same names and argument meaning as the reference for the pieces either side of the two models:
 ``load_detection_model`` (:43), ``load_recognition_model`` (:72), ``preprocess_for_recognition`` (:92), ``recognize_text`` (:131),
 ``recognize_text_batch`` (:144), ``resize_image_for_det`` (:33), ``crop_image`` (src/det/test.py:123) plus ``normalize_for_det`` (the
-inline code at :312-314), ``rescale_boxes`` (:324-328) and ``detect_and_recognize`` (steps 2-3 of the per-image loop, :306-352).
+inline code at :312-314), ``rescale_boxes`` (:324-328) and ``detect_and_recognize`` (steps 2-3 of the per-image loop, :306-352), and the geometric half of step 1
+(``four_point_transform``, ``preprocess_image``: src/preprocess/scanner.py:29-53,168-196 with the corners supplied by the caller).
 Image resizing and crop pre-processing run on the GPU (ocrvi_crop_resize_normalize / ocrvi_normalize_u8).
 
 ``DBPostProcessor`` (src/det/test.py:46-106) is the host C++ implementation behind ``ocrvi_db_postprocess``; like the reference's, it works on
@@ -393,16 +394,90 @@ def recognize_text_batch(model: SVTRv2, crops: List[np.ndarray], device: str = "
     return texts
 
 
+def as_quad(pts, what: str = "quad") -> np.ndarray:
+    """The four corners as a float64 [4, 2] array; ValueError (starting with ``what``) for another shape or a non-finite value.  (4, 1, 2), the
+    layout of a cv2 contour, is accepted as ``screen_cnt.reshape(4, 2)`` accepts it (scanner.py:187)."""
+    try:
+        q = np.asarray(pts, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: expected four (x, y) corners, got {type(pts).__name__}") from None
+    if q.shape == (4, 1, 2):
+        q = q.reshape(4, 2)
+    if q.shape != (4, 2):
+        raise ValueError(f"{what}: expected four (x, y) corners (shape (4, 2)), got shape {q.shape}")
+    if not np.isfinite(q).all():
+        raise ValueError(f"{what}: a corner is not finite")
+    return np.ascontiguousarray(q)
+
+
+def four_point_geometry(pts, what: str = "quad"):
+    """The host half of four_point_transform (scanner.py:33-50, ``ocrvi_four_point_transform``): corner order, output size and the two
+    matrices.  Returns (m_fwd float64 [3,3] source -> rectified, m_inv float64 [3,3], out_w, out_h).  Needs no GPU.  ValueError when the
+    quad rectifies to less than one pixel or its ordered corners are degenerate (the reference passes those to cv2)."""
+    q = as_quad(pts, what)
+    m_fwd, m_inv = np.empty(9, np.float64), np.empty(9, np.float64)
+    w, h = ctypes.c_int32(0), ctypes.c_int32(0)
+    lib = _lib.load()
+    rc = lib.ocrvi_four_point_transform(q.ctypes.data, m_fwd.ctypes.data, m_inv.ctypes.data, ctypes.byref(w), ctypes.byref(h))
+    if rc == -1:
+        raise ValueError(f"{what}: {_lib.last_error()}")
+    _lib.check(rc)
+    return m_fwd.reshape(3, 3), m_inv.reshape(3, 3), w.value, h.value
+
+
+def warp_perspective(image: torch.Tensor, m_inv, out_h: int, out_w: int) -> torch.Tensor:
+    """``ocrvi_warp_perspective_u8`` on the current stream: uint8 HxWx3 device tensor -> uint8 out_h x out_w x 3 device tensor under the
+    destination -> source matrix ``m_inv`` (cv2.warpPerspective(image, M, (out_w, out_h)) with m_inv = M^-1, scanner.py:51)."""
+    assert image.is_cuda and image.dtype == torch.uint8 and image.dim() == 3 and image.shape[2] == 3
+    image = image.contiguous()
+    m = np.ascontiguousarray(np.asarray(m_inv, np.float64).reshape(9))
+    out = torch.empty((int(out_h), int(out_w), 3), dtype=torch.uint8, device=image.device)
+    stream = torch.cuda.current_stream(image.device).cuda_stream
+    _lib.check(_lib.load().ocrvi_warp_perspective_u8(_dev_index(image.device), image.data_ptr(), image.shape[0], image.shape[1], m.ctypes.data,
+                                                     out.data_ptr(), int(out_h), int(out_w), stream))
+    return out
+
+
+def four_point_transform(image, pts, device: str = "cuda:0"):
+    """scanner.py:29-53: the document whose corners are ``pts`` (four (x, y) points of ``image``, any order) flattened to a
+    max_width x max_height page.  The geometry runs on the host, the warp on the device.  ``image``: uint8 HxWx3, a numpy array (the
+    result is a numpy array) or a device tensor (the result stays on its device)."""
+    _, m_inv, w, h = four_point_geometry(pts)
+    if isinstance(image, torch.Tensor) and image.is_cuda:
+        return warp_perspective(image, m_inv, h, w)
+    img = image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image))
+    if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
+        raise ValueError(f"four_point_transform: expected a uint8 HxWx3 image, got dtype {img.dtype} shape {tuple(img.shape)}")
+    out = warp_perspective(img.to(device), m_inv, h, w).cpu()
+    return out if isinstance(image, torch.Tensor) else out.numpy()
+
+
+def preprocess_image(image, quad, enhance: bool = False, device: str = "cuda:0"):
+    """scanner.py:168-196 with the document's corners supplied by the caller instead of found by the rembg network (``quad`` is what
+    ``screen_cnt.reshape(4, 2) * ratio`` is there, :187).  ``quad=None`` returns the image, as the reference does when no document is
+    found (:183-184).  ``enhance=True`` is not built: the pipeline calls this stage with enhance=False (pipeline2.py:296)."""
+    if enhance:
+        raise NotImplementedError("preprocess_image(enhance=True): enhance_document (scanner.py:55-76: CLAHE, non-local-means denoising, sharpening) "
+                                  "is outside this library; the reference's pipeline runs this stage with enhance=False")
+    if quad is None:
+        return image
+    return four_point_transform(image, quad, device)
+
+
 def detect_and_recognize(original_image, det_model, rec_model, post_processor: DBPostProcessor, device: str = "cuda:0", det_size: int = 640,
-                         rec_size: Tuple[int, int] = (32, 256), rec_batch_size: int = 64, binary_head: bool = False):
+                         rec_size: Tuple[int, int] = (32, 256), rec_batch_size: int = 64, binary_head: bool = False, quad=None):
     """Steps 2 and 3 of the reference's per-image loop (pipeline2.py:306-352) with every stage on this library: resize + normalise on the
     device -> ``det_model`` -> ``post_processor`` on the host copy of the binary map -> boxes rescaled to the original image -> the
     bounding rectangle of each box cropped, resized and normalised on the device straight from the uploaded page -> ``rec_model`` greedy
     CTC in batches of ``rec_batch_size``.  ``original_image``: RGB uint8 HxWx3 (numpy or device tensor).
     ``binary_head``: call ``det_model.forward_binary`` (the binarise branch alone; same map in f32 / f16x2) instead of ``det_model(...)``.
+    ``quad``: the document's four corners in ``original_image`` (step 1, pipeline2.py:291-302): the page is rectified first
+    (``four_point_transform``) and replaces the original, so the boxes are in the rectified page's coordinates (:297).
     Returns (rescaled_boxes [int32 (n_i, 2)], scores, texts); empty crops decode the all-zero tensor as pipeline2.py:154-156 does."""
     page = original_image if isinstance(original_image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(original_image))
     page = page.to(device).contiguous()
+    if quad is not None:
+        page = four_point_transform(page, quad)
     h, w = page.shape[:2]
     resized, (scale_h, scale_w) = resize_image_for_det(page, det_size)
     det_preds = det_model.forward_binary(normalize_for_det(resized)) if binary_head else det_model(normalize_for_det(resized))
