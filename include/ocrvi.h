@@ -279,6 +279,90 @@ int ocrvi_db_boxes_batch_sparse(const uint32_t* mask_bits, const int32_t* comps,
                                 int32_t* rects, float* scores, int cap_per_page, int32_t* counts, int threads, int32_t* skipped);
 
 /* ------------------------------------------------------------------------------------------------
+ * Validation: the numbers the reference's two validation loops report (src/det/val.py, src/rec2/val.py) from maps, log-probs and ids
+ * that stay on the device.  Forward values only: no backward pass, no SGM term (both are training).  All three
+ * entries are enqueue-only on `stream`, allocate nothing and never synchronise; every pointer is DEVICE memory.
+ * ------------------------------------------------------------------------------------------------ */
+/* Replaces DBLoss.forward (model/det/loss.py:70-90, with BalanceCrossEntropyLoss :10-31, DiceLoss :38-50, MaskL1Loss :57-59) and the
+ * counts of compute_metrics (src/det/val.py:26-35), up to the final divisions, which are host arithmetic on the record below.
+ * Eight float32 maps of n = N*H*W elements ([N,1,H,W]): binary, thresh, thresh_binary, bin_logits as ocrvi_det_forward writes them; gt, mask,
+ * thresh_map, thresh_mask from the batch.  No alignment is asked of them (16-byte aligned maps are read four pixels at a time).
+ * Per pixel, every term in float32 exactly as the reference forms it:
+ *   gm = gt * mask, ngm = (1 - gt) * mask;  p = (int)gm & 255, q = (int)ngm & 255   (`.byte()`: truncation, so a fractional product is 0)
+ *   loss = max(x, 0) - x * gt + log1p(exp(-|x|)),  x = bin_logits                   (binary_cross_entropy_with_logits, reduction 'none')
+ *   P = (binary > 0.5 ? 1 : 0) * mask;  tp += (P == 1 and gm == 1), fp += (P == 1 and gm == 0), fn += (P == 0 and gm == 1)
+ * Record (OCRVI_DET_EVAL_RECORD_BYTES bytes, 8-byte aligned, 13 slots of 8 bytes; slots 0..5 int64, 6..12 float64):
+ *   TP, FP, FN        the three counts above
+ *   POSITIVES         sum p            NEGATIVES  sum q
+ *   K                 negative_count = min(NEGATIVES, (int64)trunc((double)POSITIVES * negative_ratio)), formed on the device; 0 when the
+ *                     product is below 1 or NaN
+ *   POS_BCE           sum loss * p
+ *   TOPK_BCE          sum of the K largest values of loss * q over all pixels (torch.topk(negative_loss.view(-1), negative_count).sum());
+ *                     0 when K = 0
+ *   DICE_INTER        sum (thresh_binary * gt) * mask     PRED_MASK  sum thresh_binary * mask     GT_MASK  sum gm
+ *   L1_NUM            sum |thresh - thresh_map| * thresh_mask        THRESH_MASK  sum thresh_mask
+ * so that, with eps = 1e-6:  l_prob = (POS_BCE + TOPK_BCE) / (POSITIVES + K + eps),  l_binary = 1 - 2 DICE_INTER / (PRED_MASK + GT_MASK + eps),
+ * l_thresh = L1_NUM / (THRESH_MASK + eps),  loss = l_prob + alpha l_binary + beta l_thresh.
+ * Sums: each float32 term is widened to float64 and added in float64, per thread, then per wave, per block and over the blocks in index
+ * order; the grid is a function of n alone and the counts are integer atomics, so two runs on the same inputs give the same bits.
+ * Top-k: the fused pass also writes loss * q as a 4-byte stream into the workspace.  For gt in [0, 1] the values are non-negative, so
+ * their bit patterns order as the values do: a radix select over the 31 bits below the sign (9 + 11 + 11, one LDS histogram pass each, the first inside
+ * the fused pass) finds the K-th largest value v, and TOPK_BCE = sum of the values above v + (K - their number) * v, exact whatever the
+ * ties.  Zeros are not counted: when fewer than K values are non-zero, v = 0.  Non-finite logits may give NaN or infinite sums (a NaN
+ * orders above every number in the select); every pass is a fixed number of steps whatever the data.
+ * workspace: 256-byte aligned, ocrvi_det_eval_workspace_bytes(N, H, W, &bytes) bytes (114944 + 4 n rounded up to a multiple of 256); OCRVI_ENOMEM when it is short. */
+#define OCRVI_DET_EVAL_RECORD_BYTES 104
+#define OCRVI_DET_EVAL_TP 0
+#define OCRVI_DET_EVAL_FP 1
+#define OCRVI_DET_EVAL_FN 2
+#define OCRVI_DET_EVAL_POSITIVES 3
+#define OCRVI_DET_EVAL_NEGATIVES 4
+#define OCRVI_DET_EVAL_K 5
+#define OCRVI_DET_EVAL_POS_BCE 6
+#define OCRVI_DET_EVAL_TOPK_BCE 7
+#define OCRVI_DET_EVAL_DICE_INTER 8
+#define OCRVI_DET_EVAL_PRED_MASK 9
+#define OCRVI_DET_EVAL_GT_MASK 10
+#define OCRVI_DET_EVAL_L1_NUM 11
+#define OCRVI_DET_EVAL_THRESH_MASK 12
+int ocrvi_det_eval_workspace_bytes(int N, int H, int W, size_t* bytes);
+int ocrvi_det_eval(int device, const float* binary, const float* thresh, const float* thresh_binary, const float* bin_logits,
+                   const float* gt, const float* mask, const float* thresh_map, const float* thresh_mask, int N, int H, int W,
+                   double negative_ratio, void* record, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Replaces nn.CTCLoss(blank, reduction='none') as SVTRv2Loss.forward calls it (model/rec2/loss.py:44-63), before zero_infinity and the
+ * reduction, which are host arithmetic on B numbers.  log_probs float32 [T,B,C], exactly what ocrvi_rec_forward writes; targets int32
+ * [B,Lmax] (row b holds target_lengths[b] labels, the rest is never read; the reference's flattening, loss.py:57-61, is not needed);
+ * target_lengths int32 [B]; input_lengths int32 [B] or NULL, which means T for every row; 0 <= blank < C; Lmax <=
+ * OCRVI_CTC_LOSS_MAX_TARGET.  nll float64 [B].
+ * Row b, with L = target_lengths[b], Tb = input_lengths[b]: the extended sequence l' has S = 2L + 1 states, blank at the even ones and
+ * label (s - 1) / 2 at the odd ones.  In float64 log space, from the float32 log-probs y:
+ *   alpha_0(0) = y[0,b,blank], alpha_0(1) = y[0,b,l'_1], alpha_0(s) = -inf otherwise
+ *   alpha_t(s) = logsumexp(alpha_{t-1}(s), alpha_{t-1}(s-1), alpha_{t-1}(s-2) if s is odd, s >= 3 and l'_s != l'_{s-2}) + y[t,b,l'_s]
+ *   nll[b] = -logsumexp(alpha_{Tb-1}(S-1), alpha_{Tb-1}(S-2))
+ * logsumexp subtracts the largest term first and is -inf when every term is.  No alignment of the labels over Tb steps (L plus the
+ * number of adjacent repeats exceeds Tb) gives +inf.  Lengths outside [0, Lmax] / [0, T] are clamped into them and a label outside
+ * [0, C) has probability 0, so no address outside the buffers is formed; Tb = 0 gives 0 for L = 0 and +inf otherwise.
+ * One wave per row: state s in lane s mod 64, the two alpha rows in LDS. */
+#define OCRVI_CTC_LOSS_MAX_TARGET 1024
+int ocrvi_ctc_loss(int device, const float* log_probs, int T, int B, int C, const int32_t* targets, int Lmax, const int32_t* target_lengths,
+                   const int32_t* input_lengths, int blank, double* nll, void* stream);
+
+/* Replaces editdistance.eval(pred, gt) inside compute_cer (src/rec2/val.py:14-24) for B pairs of id rows: dist int32 [B] = the
+ * Levenshtein distance (insertion, deletion and substitution cost 1 each) between
+ *   the first pred_lens[b] ids of pred_ids [B,T] with every id < 2 dropped -- the ids / lens buffers of ocrvi_rec_forward: the collapse there
+ *   drops the blank and keeps pad id 1, Tokenizer.decode drops both (tokenizer.py:73) -- and
+ *   the first gt_lens[b] ids of gt_ids [B,G], encoded on the host, a character outside the alphabet as -2: it equals no prediction id,
+ *   which is what the string distance does with such a character.
+ * Lengths are clamped into [0, T] / [0, G]; T, G <= OCRVI_EDIT_DISTANCE_MAX_LEN.  One wave per pair: a row of the DP (one row per
+ * prediction id, one column per ground-truth id) lies across the lanes, 64 columns at a time; with t[j] = min(above + 1, diagonal +
+ * (ids differ)) the insertion chain is a prefix minimum, d[j] = j + min over k <= j of (t[k] - k), carried from one group of 64 columns
+ * to the next. */
+#define OCRVI_EDIT_DISTANCE_MAX_LEN 2048
+int ocrvi_edit_distance(int device, const int32_t* pred_ids, int T, const int32_t* pred_lens, const int32_t* gt_ids, int G,
+                        const int32_t* gt_lens, int B, int32_t* dist, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Kernel-level test/bench hooks (same kernels the models launch; used by tests/ and bench.py for
  * per-kernel parity and roofline timing).
  * ------------------------------------------------------------------------------------------------ */

@@ -1,7 +1,8 @@
 """MI355X-native (gfx950) inference engine for the DBNet++ -> SVTRv2 -> CTC invoice OCR hot path.
 
 Importing the package is cheap and CPU-safe; ``DBNetPP`` / ``SVTRv2`` / ``Engine`` (batched OCR over pages of mixed sizes) load ``lib/libocrvi.so`` on first use and
-raise if it is missing (there is no CPU fallback)."""
+raise if it is missing (there is no CPU fallback).  ``DBLoss`` / ``SVTRv2Loss`` / ``compute_metrics`` / ``compute_cer`` / ``compute_acc`` /
+``validate_detection`` / ``validate_recognition`` (``val.py``) mirror the reference's validation loops on the device."""
 from .vocab import VOCAB, Tokenizer  # noqa: F401
 
 
@@ -15,4 +16,10 @@ def __getattr__(name):
     if name == "Engine":
         from .engine import Engine
         return Engine
+    if name in _VAL_NAMES:      # validation: the reference's loss values, pixel metrics, CER and accuracy (val.py)
+        from . import val
+        return getattr(val, name)
     raise AttributeError(name)
+
+
+_VAL_NAMES = ("DBLoss", "compute_metrics", "SVTRv2Loss", "compute_cer", "compute_acc", "validate_detection", "validate_recognition")

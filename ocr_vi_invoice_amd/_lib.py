@@ -30,8 +30,15 @@ EXPORTS = [
     "ocrvi_det_binary_workspace_bytes", "ocrvi_det_forward_binary",
     "ocrvi_four_point_transform", "ocrvi_warp_perspective_u8", "ocrvi_warp_perspective_pages",
     "ocrvi_test_layernorm", "ocrvi_test_frm_vertical", "ocrvi_test_asf", "ocrvi_test_maxpool", "ocrvi_test_db_maps", "ocrvi_test_ctc_logsoftmax",
+    "ocrvi_det_eval_workspace_bytes", "ocrvi_det_eval", "ocrvi_ctc_loss", "ocrvi_edit_distance",
 ]
 PAGE_ENTRY = 4          # int64 fields of one page-table entry: (device address, height, width, 0) -- OCRVI_PAGE_ENTRY
+# ocrvi_det_eval's record: 13 slots of 8 bytes (OCRVI_DET_EVAL_*), the first six int64, the rest float64
+DET_EVAL_RECORD_BYTES = 104
+DET_EVAL_INT_SLOTS = ("tp", "fp", "fn", "positive_count", "negatives", "negative_count")
+DET_EVAL_F64_SLOTS = ("pos_bce", "topk_bce", "dice_inter", "pred_mask", "gt_mask", "l1_num", "thresh_mask")
+CTC_LOSS_MAX_TARGET = 1024      # OCRVI_CTC_LOSS_MAX_TARGET
+EDIT_DISTANCE_MAX_LEN = 2048    # OCRVI_EDIT_DISTANCE_MAX_LEN
 
 
 class DetCfg(C.Structure):
@@ -112,6 +119,10 @@ def load() -> C.CDLL:
     lib.ocrvi_test_maxpool.argtypes = [i32, i32, f32p, i32, i32, i32, i32, f32p]
     lib.ocrvi_test_db_maps.argtypes = [i32, f32p, f32p, C.c_float, f32p, f32p, f32p, sz]
     lib.ocrvi_test_ctc_logsoftmax.argtypes = [i32, f32p, i32, i32, i32, i32, f32p, i32p]
+    lib.ocrvi_det_eval_workspace_bytes.argtypes = [i32, i32, i32, C.POINTER(sz)]
+    lib.ocrvi_det_eval.argtypes = [i32, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, i32, i32, i32, C.c_double, vp, vp, sz, vp]
+    lib.ocrvi_ctc_loss.argtypes = [i32, f32p, i32, i32, i32, i32p, i32, i32p, i32p, i32, vp, vp]
+    lib.ocrvi_edit_distance.argtypes = [i32, i32p, i32, i32p, i32p, i32, i32p, i32, i32p, vp]
     lib.ocrvi_det_status.argtypes = [vp]
     lib.ocrvi_rec_status.argtypes = [vp]
     lib.ocrvi_range_reset.argtypes = [i32, vp]
