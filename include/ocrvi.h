@@ -177,7 +177,7 @@ int ocrvi_crop_resize_normalize_pages(int device, const int64_t* pages, int n_pa
 /* ------------------------------------------------------------------------------------------------
  * Four-point page rectification: the geometric half of the reference's stage 1, `--preprocess` (src/pipeline/pipeline2.py:291-302 ->
  * preprocess_image, src/preprocess/scanner.py:168-196 -> four_point_transform, scanner.py:29-53).  Finding the document's corners (the
- * rembg network, scanner.py:78-132) is the caller's business; enhance_document (scanner.py:55-76) is not built (the pipeline passes
+ * rembg network, scanner.py:78-132) is the caller's business; enhance_document (scanner.py:55-76) is below (the pipeline passes
  * enhance=False).
  * ------------------------------------------------------------------------------------------------ */
 /* Host only, needs no GPU.  Replaces order_points (scanner.py:13-27), the output size (scanner.py:36-42), the destination corners
@@ -218,6 +218,70 @@ int ocrvi_warp_perspective_u8(int device, const uint8_t* src, int src_h, int src
  * Destination addresses need no alignment.  Enqueue-only on `stream`. */
 int ocrvi_warp_perspective_pages(int device, const int64_t* src_pages, const int64_t* dst_pages, const double* m_inv /*DEVICE [n][9]*/, int n,
                                  void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * enhance_document, the reference's "Magic Color" (src/preprocess/scanner.py:55-76): COLOR_BGR2LAB (:60), CLAHE(clipLimit 2.0, 8 x 8 tiles)
+ * on L (:63-64), COLOR_LAB2BGR (:67), fastNlMeansDenoisingColored(h 10, hColor 10, template 7, search 21) (:70), filter2D with the 3 x 3
+ * sharpen kernel (:73-74).  The reference's constants are fixed: none is a parameter.
+ * Pages are RGB uint8 HWC [h,w,3] in DEVICE memory, 16 <= h, w and h w <= 2^29 (the 13-pixel reflection and the 8 x 8 grid need 16); Lab
+ * pages have the same layout with (L, a, b) in the three bytes.  The Lab of an RGB pixel is the reference's COLOR_BGR2LAB of the swapped
+ * pixel and the other stages treat the channels alike, so no channel swap is needed anywhere.
+ * The arithmetic is the library's own definition, modelled on OpenCV's 8-bit integer paths and stated in full here.  OpenCV's Lab, CLAHE
+ * and NLM code differ between versions and cv2 is absent from the build container: parity with cv2 is UNPINNED, as for ocrvi_resize_u8 and
+ * the warp.  Everything on the device is integer: tests/enhance_ref.py restates it in numpy and the kernels are bit-equal to it.
+ *
+ * Tables: built on the host in double, each entry rounded with rint, uploaded once per device by ocrvi_enhance_init.  g is the sRGB
+ * decode (c <= 0.04045 ? c / 12.92 : ((c + 0.055) / 1.055)^2.4), g^-1 the sRGB encode (l <= 0.0031308 ? 12.92 l : 1.055 l^(1/2.4) - 0.055),
+ * f(t) = cbrt(t) for t > 216/24389, else (841/108) t + 4/29.  M is OpenCV's sRGB -> XYZ D65 matrix (0.412453 0.357580 0.180423 / 0.212671
+ * 0.715160 0.072169 / 0.019334 0.119193 0.950227), white its row sums.
+ *   LIN[256]  = rint(2040 g(v / 255))                  F[2041]  = rint(32768 f(t / 2040))          ENC[2041] = rint(255 g^-1(t / 2040))
+ *   FY[256]   = rint((L 100 / 255 + 16) / 116 * 32768) DA[256]  = rint((a - 128) 32768 / 500)      DB[256]   = rint((b - 128) 32768 / 200)
+ *   W1[1024], W2[1024]: WC[k] = rint(255 exp(-(k 64 / 49) / (100 C))) for C = 1, 2 (last non-zero entry: k = 477, k = 954)
+ *   CF[3][3]  = rint(4096 M[i][j] / white[i])          CI[3][3] = rint(4096 M^-1[i][j] white[j])   (M^-1 = adjugate / determinant); in each
+ *               row the entry of largest magnitude is then adjusted so that the row sums to exactly 4096
+ * RGB -> Lab:  l = LIN[rgb];  XYZ = (CF l + 2048) >> 12 (each <= 2040);  fX, fY, fZ = F[XYZ];
+ *   L = clamp((2958 fY - 13369344 + 163840) // 327680, 0, 255);  a = clamp(((500 (fX - fY) + 16384) >> 15) + 128, 0, 255);
+ *   b = clamp(((200 (fY - fZ) + 16384) >> 15) + 128, 0, 255).  Shifts are arithmetic, // is floor division.
+ * Lab -> RGB:  fy = FY[L], fx = fy + DA[a], fz = fy - DB[b], each clamped to [0, 49151];
+ *   t(f) = (f^3 2040 + 2^44) >> 45 in 64 bits for f > 6781, else max(((f - 4520) 8383 + 2^19) >> 20, 0);
+ *   r = clamp((CI t + 2048) >> 12, 0, 2040);  out = ENC[r].
+ * CLAHE on channel 0 (a and b are copied):  Hp, Wp = h, w rounded up to multiples of 8, the plane extended right and down by reflect-101;
+ *   th = Hp / 8, tw = Wp / 8.  Per tile, on its 256-bin histogram: clip = max(2 th tw // 256, 1); excess = sum max(hist - clip, 0);
+ *   hist = min(hist, clip) + excess // 256; r = excess % 256; if r > 0, step = max(256 // r, 1) and bins 0, step, 2 step, ... get +1 each
+ *   until r are given.  LUT[v] = (255 cdf(v) + th tw // 2) // (th tw).  For pixel (y, x) with level v: nx = 2x + 1 - tw, tx1 = floor(nx /
+ *   2tw), ax = nx - tx1 2tw, tx2 = tx1 + 1, both clamped to [0, 7]; likewise in y; out = (sum of the four LUT[v] weighted by (2tw - ax | ax)
+ *   (2th - ay | ay), + 2 tw th) // (4 tw th), in 64 bits.
+ * NLM: once on the L plane with W1 and once on the (a, b) pair jointly with W2.  The page is extended by 13 pixels each side with
+ *   reflect-101.  For pixel p and each of the 21 x 21 offsets q: D = sum over the 7 x 7 template t and the channels of the group of
+ *   (I(p + t) - I(p + q + t))^2;  w = WC[min(D >> 6, 1023)];  out_c(p) = (sum_q w I_c(p + q) + floor(sum_q w / 2)) // sum_q w  (sum w >=
+ *   255: q = 0 has D = 0; every sum fits int32).
+ * Sharpen: per channel clamp(9 c - the eight neighbours, 0, 255), reflect-101 borders.
+ * ------------------------------------------------------------------------------------------------ */
+/* Builds the tables and uploads them to `device`; idempotent.  The only entry of this section that allocates or synchronises. */
+int ocrvi_enhance_init(int device);
+/* Host only, needs no GPU: the tables as int32, in the order LIN, F, ENC, FY, DA, DB, W1, W2, CF, CI (7172 values, 28688 bytes) -> out.
+ * *bytes = the size; out == NULL asks for the size alone; OCRVI_ENOMEM when cap is smaller. */
+int ocrvi_enhance_tables(void* out, size_t cap, size_t* bytes);
+/* Scratch DEVICE memory of ocrvi_enhance_u8 for an h x w page: 16384 + 2 * (3 h w rounded up to a multiple of 256) bytes (the 64 tile
+ * LUTs and two Lab / RGB pages). */
+int ocrvi_enhance_workspace_bytes(int h, int w, size_t* bytes);
+/* Replaces enhance_document(image) (scanner.py:55-76): the stages below in the reference's order -- rgb_to_lab, clahe_lab, lab_to_rgb,
+ * rgb_to_lab, nlm_lab, lab_to_rgb, sharpen --, every stage boundary a uint8 page as there (two boundaries stay in registers: the bytes are
+ * those of the composition).  No alignment is asked of src, dst or workspace (a multiple of 4 is read and written in 4-byte words).
+ * All entries from here on are enqueue-only on `stream` and graph-capturable: no allocation, no synchronisation.  They return
+ * OCRVI_EINVAL, with a message and without touching dst, for a null pointer, a side below 16, a dst that overlaps src and a device on
+ * which ocrvi_enhance_init has not run; OCRVI_ENOMEM for a short workspace. */
+int ocrvi_enhance_u8(int device, const uint8_t* src, int h, int w, uint8_t* dst, void* workspace, size_t workspace_bytes, void* stream);
+/* The stages on their own (the same kernels).  cv2.cvtColor(COLOR_BGR2LAB) (scanner.py:60) / cv2.cvtColor(COLOR_LAB2BGR) (:67): */
+int ocrvi_rgb_to_lab_u8(int device, const uint8_t* src, int h, int w, uint8_t* dst, void* stream);
+int ocrvi_lab_to_rgb_u8(int device, const uint8_t* src, int h, int w, uint8_t* dst, void* stream);
+/* cv2.createCLAHE(2.0, (8, 8)).apply on channel 0 of a Lab page (scanner.py:61-66); workspace: OCRVI_CLAHE_WORKSPACE_BYTES of DEVICE memory. */
+#define OCRVI_CLAHE_WORKSPACE_BYTES 16384
+int ocrvi_clahe_lab_u8(int device, const uint8_t* src, int h, int w, uint8_t* dst, void* workspace, size_t workspace_bytes, void* stream);
+/* The Lab-space middle of cv2.fastNlMeansDenoisingColored(img, None, 10, 10, 7, 21) (scanner.py:70): Lab page -> Lab page. */
+int ocrvi_nlm_lab_u8(int device, const uint8_t* src, int h, int w, uint8_t* dst, void* stream);
+/* cv2.filter2D(img, -1, [[-1,-1,-1],[-1,9,-1],[-1,-1,-1]]) (scanner.py:73-74) on any 3-channel page. */
+int ocrvi_sharpen_u8(int device, const uint8_t* src, int h, int w, uint8_t* dst, void* stream);
 
 /* Replaces DBPostProcessor(thresh, box_thresh, max_candidates, unclip_ratio).__call__ with .min_area (src/det/test.py:46-106) on a HOST
  * probability map prob[H*W] (the reference also runs this stage on the CPU after `.cpu().numpy()`, pipeline2.py:320-321).

@@ -31,6 +31,8 @@ EXPORTS = [
     "ocrvi_four_point_transform", "ocrvi_warp_perspective_u8", "ocrvi_warp_perspective_pages",
     "ocrvi_test_layernorm", "ocrvi_test_frm_vertical", "ocrvi_test_asf", "ocrvi_test_maxpool", "ocrvi_test_db_maps", "ocrvi_test_ctc_logsoftmax",
     "ocrvi_det_eval_workspace_bytes", "ocrvi_det_eval", "ocrvi_ctc_loss", "ocrvi_edit_distance",
+    "ocrvi_enhance_init", "ocrvi_enhance_tables", "ocrvi_enhance_workspace_bytes", "ocrvi_enhance_u8",
+    "ocrvi_rgb_to_lab_u8", "ocrvi_lab_to_rgb_u8", "ocrvi_clahe_lab_u8", "ocrvi_nlm_lab_u8", "ocrvi_sharpen_u8",
 ]
 PAGE_ENTRY = 4          # int64 fields of one page-table entry: (device address, height, width, 0) -- OCRVI_PAGE_ENTRY
 # ocrvi_det_eval's record: 13 slots of 8 bytes (OCRVI_DET_EVAL_*), the first six int64, the rest float64
@@ -39,6 +41,8 @@ DET_EVAL_INT_SLOTS = ("tp", "fp", "fn", "positive_count", "negatives", "negative
 DET_EVAL_F64_SLOTS = ("pos_bce", "topk_bce", "dice_inter", "pred_mask", "gt_mask", "l1_num", "thresh_mask")
 CTC_LOSS_MAX_TARGET = 1024      # OCRVI_CTC_LOSS_MAX_TARGET
 EDIT_DISTANCE_MAX_LEN = 2048    # OCRVI_EDIT_DISTANCE_MAX_LEN
+CLAHE_WORKSPACE_BYTES = 16384   # OCRVI_CLAHE_WORKSPACE_BYTES
+ENHANCE_MIN_SIDE = 16           # the smallest page side the enhance entries take
 
 
 class DetCfg(C.Structure):
@@ -123,6 +127,13 @@ def load() -> C.CDLL:
     lib.ocrvi_det_eval.argtypes = [i32, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, i32, i32, i32, C.c_double, vp, vp, sz, vp]
     lib.ocrvi_ctc_loss.argtypes = [i32, f32p, i32, i32, i32, i32p, i32, i32p, i32p, i32, vp, vp]
     lib.ocrvi_edit_distance.argtypes = [i32, i32p, i32, i32p, i32p, i32, i32p, i32, i32p, vp]
+    lib.ocrvi_enhance_init.argtypes = [i32]
+    lib.ocrvi_enhance_tables.argtypes = [vp, sz, C.POINTER(sz)]
+    lib.ocrvi_enhance_workspace_bytes.argtypes = [i32, i32, C.POINTER(sz)]
+    lib.ocrvi_enhance_u8.argtypes = [i32, vp, i32, i32, vp, vp, sz, vp]
+    for name in ("ocrvi_rgb_to_lab_u8", "ocrvi_lab_to_rgb_u8", "ocrvi_nlm_lab_u8", "ocrvi_sharpen_u8"):
+        getattr(lib, name).argtypes = [i32, vp, i32, i32, vp, vp]
+    lib.ocrvi_clahe_lab_u8.argtypes = [i32, vp, i32, i32, vp, vp, sz, vp]
     lib.ocrvi_det_status.argtypes = [vp]
     lib.ocrvi_rec_status.argtypes = [vp]
     lib.ocrvi_range_reset.argtypes = [i32, vp]

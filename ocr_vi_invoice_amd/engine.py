@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .pipeline import DBPostProcessor, db_boxes_pages, four_point_geometry
+from .pipeline import DBPostProcessor, db_boxes_pages, enhance_init, enhance_workspace_bytes, four_point_geometry
 
 _ARENA_ALIGN = 256
 _STREAMS: Dict[int, Tuple[torch.cuda.Stream, torch.cuda.Stream]] = {}
@@ -100,6 +100,9 @@ class Engine:
     ``run(pages, quads)``: ``quads[i]`` is ``None`` or the four corners of page i's document; such a page is rectified on the device
     (``ocrvi_warp_perspective_pages`` into its arena slot, ahead of its chunk's detector launch) and everything downstream sees the
     rectified page, as ``detect_and_recognize(page, ..., quad=quads[i])`` does: boxes are in its coordinates.
+    ``run(pages, quads, enhance)``: ``enhance`` is a bool for all pages or one bool per page; such a page goes through
+    ``ocrvi_enhance_u8`` (``pipeline.enhance_document``, src/preprocess/scanner.py:55-76) in its arena slot, after its rectification and
+    ahead of its chunk's detector launch, eagerly on the detector stream, as ``detect_and_recognize(page, ..., enhance=True)`` does.
     The captured graphs hold the models' weights as they were: after reloading a model's weights, build a new Engine."""
 
     def __init__(self, det_model, rec_model, post_processor: DBPostProcessor, det_size: int = 960, rec_size: Tuple[int, int] = (32, 256),
@@ -168,6 +171,10 @@ class Engine:
         words = self.det_chunk * (2 * _lib.PAGE_ENTRY + 9)
         self.d_warp = torch.zeros(words, dtype=torch.int64, **d)
         self.h_warp = [torch.zeros(words, dtype=torch.int64).pin_memory() for _ in range(2)]
+        # ---- enhancement (run(pages, quads, enhance)): the workspace of the largest enhanced page and a page to enhance into (the entry
+        #      refuses to work in place), grown per run
+        self.d_enh_ws = torch.empty(0, dtype=torch.uint8, **d)
+        self.d_enh_out = torch.empty(0, dtype=torch.uint8, **d)
         # one stream pair per device for every engine of the process: each new HIP stream takes the next hardware queue round-robin
         if self.devi not in _STREAMS:
             _STREAMS[self.devi] = (torch.cuda.Stream(self.dev), torch.cuda.Stream(self.dev))
@@ -290,6 +297,15 @@ class Engine:
             _lib.check(self.lib.ocrvi_warp_perspective_pages(self.devi, base, base + dc * PE * 8, base + 2 * dc * PE * 8, hi - lo,
                                                              self.s_det.cuda_stream))
             self.stats["rectified"] += n_warp
+        for slot in range(lo, hi):                 # after the upload / the warp of the page, on the same stream
+            i = wave[slot]
+            if not self._enhance[i]:
+                continue
+            (h, w), off, nb = self._sizes[i], self._offs[slot], self._nbytes[slot]
+            _lib.check(self.lib.ocrvi_enhance_u8(self.devi, self.arena.data_ptr() + off, h, w, self.d_enh_out.data_ptr(), self.d_enh_ws.data_ptr(),
+                                                 self.d_enh_ws.numel(), self.s_det.cuda_stream))
+            self.arena[off:off + nb].copy_(self.d_enh_out[:nb], non_blocking=True)
+            self.stats["enhanced"] += 1
 
     # ------------------------------------------------------------------------------------------------ recogniser batches
     def _launch_rec(self, rows, tags):
@@ -421,21 +437,40 @@ class Engine:
         self._keep = []
 
     # ------------------------------------------------------------------------------------------------ public
-    def run(self, pages: Sequence, quads: Sequence = None) -> List[Tuple[list, list, list]]:
+    def run(self, pages: Sequence, quads: Sequence = None, enhance=None) -> List[Tuple[list, list, list]]:
         pages = list(pages)
         raw_sizes = [self._check_page(i, p) for i, p in enumerate(pages)]
         # (every ValueError -- pages, quads, sizes that round to 0 -- is raised here, before any GPU work)
         sizes, mats, shapes, scales, buckets = plan_rectified(raw_sizes, quads, self.det_size)
+        if enhance is None or isinstance(enhance, (bool, np.bool_)):
+            flags = [bool(enhance)] * len(pages)
+        else:
+            flags = [bool(e) for e in enhance]
+            if len(flags) != len(pages):
+                raise ValueError(f"enhance: {len(flags)} entries for {len(pages)} pages")
+        enh_ws = enh_out = 0
+        for i, ((h, w), e) in enumerate(zip(sizes, flags)):
+            if e:
+                if h < _lib.ENHANCE_MIN_SIDE or w < _lib.ENHANCE_MIN_SIDE:
+                    raise ValueError(f"page {i}: enhance needs both sides >= {_lib.ENHANCE_MIN_SIDE}, the page is {h}x{w}")
+                enh_ws, enh_out = max(enh_ws, enhance_workspace_bytes(h, w)), max(enh_out, h * w * 3)
         for i, (h, w) in enumerate(shapes):
             if h > self.L or w > self.L:
                 raise RuntimeError(f"page {i}: bucket {h}x{w} exceeds the {self.L}x{self.L} the workspace was sized for")
         self.stats = {"pages": len(pages), "buckets": {f"{h}x{w}": len(v) for (h, w), v in buckets.items()}, "crops": 0, "rec_batches": 0,
-                      "rectified": 0, "launch_s": 0.0, "det_wait_s": 0.0, "post_s": 0.0, "rec_wait_s": 0.0}
+                      "rectified": 0, "enhanced": 0, "launch_s": 0.0, "det_wait_s": 0.0, "post_s": 0.0, "rec_wait_s": 0.0}
         if not pages:
             return []
         t_start = time.perf_counter()
         self._sizes, self._shapes, self._scales = sizes, shapes, scales
         self._raw_sizes, self._mats, self._keep = raw_sizes, mats, []
+        self._enhance = flags
+        if enh_ws:                                 # (the previous run has drained: nothing uses the old buffers any more)
+            enhance_init(self.devi)
+            if self.d_enh_ws.numel() < enh_ws:
+                self.d_enh_ws = torch.empty(enh_ws, dtype=torch.uint8, device=self.dev)
+            if self.d_enh_out.numel() < enh_out:
+                self.d_enh_out = torch.empty(enh_out, dtype=torch.uint8, device=self.dev)
         self._boxes, self._scores, self._texts = [None] * len(pages), [None] * len(pages), [None] * len(pages)
         self._pend_rects, self._pend_tags = [], []
         self._rec_inflight, self._rec_slot = collections.deque(), 0

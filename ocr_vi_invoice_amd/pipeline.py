@@ -4,7 +4,8 @@ Same names and argument meaning as the reference for the pieces either side of t
 ``load_detection_model`` (:43), ``load_recognition_model`` (:72), ``preprocess_for_recognition`` (:92), ``recognize_text`` (:131),
 ``recognize_text_batch`` (:144), ``resize_image_for_det`` (:33), ``crop_image`` (src/det/test.py:123) plus ``normalize_for_det`` (the
 inline code at :312-314), ``rescale_boxes`` (:324-328) and ``detect_and_recognize`` (steps 2-3 of the per-image loop, :306-352), and the geometric half of step 1
-(``four_point_transform``, ``preprocess_image``: src/preprocess/scanner.py:29-53,168-196 with the corners supplied by the caller).
+(``four_point_transform``, ``preprocess_image``: src/preprocess/scanner.py:29-53,168-196 with the corners supplied by the caller) and
+its enhancement half (``enhance_document``, scanner.py:55-76).
 Image resizing and crop pre-processing run on the GPU (ocrvi_crop_resize_normalize / ocrvi_normalize_u8).
 
 ``DBPostProcessor`` (src/det/test.py:46-106) is the host C++ implementation behind ``ocrvi_db_postprocess``; like the reference's, it works on
@@ -452,20 +453,73 @@ def four_point_transform(image, pts, device: str = "cuda:0"):
     return out if isinstance(image, torch.Tensor) else out.numpy()
 
 
+_ENHANCE_READY = set()
+
+
+def enhance_init(devi: int) -> None:
+    """``ocrvi_enhance_init`` once per device index (it allocates and synchronises: never inside a capture)."""
+    if devi not in _ENHANCE_READY:
+        _lib.check(_lib.load().ocrvi_enhance_init(devi))
+        _ENHANCE_READY.add(devi)
+
+
+def enhance_workspace_bytes(h: int, w: int) -> int:
+    n = ctypes.c_size_t()
+    rc = _lib.load().ocrvi_enhance_workspace_bytes(int(h), int(w), ctypes.byref(n))
+    if rc == -1:
+        raise ValueError(f"enhance_document: {_lib.last_error()}")
+    _lib.check(rc)
+    return n.value
+
+
+def enhance_page(image: torch.Tensor) -> torch.Tensor:
+    """``ocrvi_enhance_u8`` on the current stream: uint8 HxWx3 RGB device tensor -> the enhanced page, a new tensor on the same device."""
+    assert image.is_cuda and image.dtype == torch.uint8 and image.dim() == 3 and image.shape[2] == 3
+    image = image.contiguous()
+    h, w = int(image.shape[0]), int(image.shape[1])
+    devi = _dev_index(image.device)
+    ws = torch.empty(enhance_workspace_bytes(h, w), dtype=torch.uint8, device=image.device)
+    enhance_init(devi)
+    out = torch.empty_like(image)
+    stream = torch.cuda.current_stream(image.device).cuda_stream
+    _lib.check(_lib.load().ocrvi_enhance_u8(devi, image.data_ptr(), h, w, out.data_ptr(), ws.data_ptr(), ws.numel(), stream))
+    return out
+
+
+def enhance_document(image, device: str = "cuda:0"):
+    """scanner.py:55-76, the reference's "Magic Color": Lab -> CLAHE(2.0, 8 x 8) on L -> RGB -> non-local-means denoising (10, 10, 7, 21)
+    -> 3 x 3 sharpening, all on the device (``ocrvi_enhance_u8``; the arithmetic is stated in include/ocrvi.h, parity with cv2 is
+    unpinned).  ``image``: RGB uint8 HxWx3 with both sides >= 16, a numpy array (the result is a numpy array) or a device tensor (the
+    result stays on its device).  ValueError for a smaller page."""
+    if isinstance(image, torch.Tensor) and image.is_cuda:
+        if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3:
+            raise ValueError(f"enhance_document: expected a uint8 HxWx3 image, got dtype {image.dtype} shape {tuple(image.shape)}")
+        return enhance_page(image)
+    img = image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image))
+    if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
+        raise ValueError(f"enhance_document: expected a uint8 HxWx3 image, got dtype {img.dtype} shape {tuple(img.shape)}")
+    enhance_workspace_bytes(img.shape[0], img.shape[1])       # the size check, before anything is uploaded
+    out = enhance_page(img.to(device)).cpu()
+    return out if isinstance(image, torch.Tensor) else out.numpy()
+
+
 def preprocess_image(image, quad, enhance: bool = False, device: str = "cuda:0"):
     """scanner.py:168-196 with the document's corners supplied by the caller instead of found by the rembg network (``quad`` is what
     ``screen_cnt.reshape(4, 2) * ratio`` is there, :187).  ``quad=None`` returns the image, as the reference does when no document is
-    found (:183-184).  ``enhance=True`` is not built: the pipeline calls this stage with enhance=False (pipeline2.py:296)."""
+    found (:183-184).  ``enhance=True`` still raises here (the pipeline calls this stage with enhance=False, pipeline2.py:296): the
+    enhancement is its own call, ``enhance_document(preprocess_image(image, quad))``, or ``enhance=True`` of ``detect_and_recognize``."""
     if enhance:
-        raise NotImplementedError("preprocess_image(enhance=True): enhance_document (scanner.py:55-76: CLAHE, non-local-means denoising, sharpening) "
-                                  "is outside this library; the reference's pipeline runs this stage with enhance=False")
+        raise NotImplementedError("preprocess_image(enhance=True): call pipeline.enhance_document(preprocess_image(image, quad)) instead "
+                                  "(enhance_document, scanner.py:55-76: CLAHE, non-local-means denoising, sharpening, runs on the device "
+                                  "as a stage of its own)")
     if quad is None:
         return image
     return four_point_transform(image, quad, device)
 
 
 def detect_and_recognize(original_image, det_model, rec_model, post_processor: DBPostProcessor, device: str = "cuda:0", det_size: int = 640,
-                         rec_size: Tuple[int, int] = (32, 256), rec_batch_size: int = 64, binary_head: bool = False, quad=None):
+                         rec_size: Tuple[int, int] = (32, 256), rec_batch_size: int = 64, binary_head: bool = False, quad=None,
+                         enhance: bool = False):
     """Steps 2 and 3 of the reference's per-image loop (pipeline2.py:306-352) with every stage on this library: resize + normalise on the
     device -> ``det_model`` -> ``post_processor`` on the host copy of the binary map -> boxes rescaled to the original image -> the
     bounding rectangle of each box cropped, resized and normalised on the device straight from the uploaded page -> ``rec_model`` greedy
@@ -473,11 +527,15 @@ def detect_and_recognize(original_image, det_model, rec_model, post_processor: D
     ``binary_head``: call ``det_model.forward_binary`` (the binarise branch alone; same map in f32 / f16x2) instead of ``det_model(...)``.
     ``quad``: the document's four corners in ``original_image`` (step 1, pipeline2.py:291-302): the page is rectified first
     (``four_point_transform``) and replaces the original, so the boxes are in the rectified page's coordinates (:297).
+    ``enhance``: ``enhance_document`` on the (rectified) page before the detector resize (scanner.py:190-191): boxes and crops come from
+    the enhanced page.
     Returns (rescaled_boxes [int32 (n_i, 2)], scores, texts); empty crops decode the all-zero tensor as pipeline2.py:154-156 does."""
     page = original_image if isinstance(original_image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(original_image))
     page = page.to(device).contiguous()
     if quad is not None:
         page = four_point_transform(page, quad)
+    if enhance:
+        page = enhance_document(page)
     h, w = page.shape[:2]
     resized, (scale_h, scale_w) = resize_image_for_det(page, det_size)
     det_preds = det_model.forward_binary(normalize_for_det(resized)) if binary_head else det_model(normalize_for_det(resized))
