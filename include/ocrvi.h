@@ -47,9 +47,10 @@ const char* ocrvi_last_error(void);
 int ocrvi_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
- * Detection: replaces DBNetPP(backbone='resnet50', dcn=True).eval() -- model/det/dbnet.py:6-17
- * (ResNet-50 + DCNv2 backbone model/det/backbone.py:8-60, dcn.py:41-59; FPN+ASF neck neck.py:26-79;
- * DB head head.py:32-48).
+ * Detection: replaces DBNetPP(backbone in {'resnet50', 'resnet18'}, dcn in {True, False}).eval() -- model/det/dbnet.py:6-17
+ * (ResNet-50 or ResNet-18 backbone model/det/backbone.py:8-60, the choice at backbone.py:12-15, torchvision's Bottleneck /
+ * BasicBlock; with dcn every block's conv2 in layers 2-4 is the DCNv2 module, backbone.py:28-31,39-53, dcn.py:41-59; FPN+ASF neck
+ * neck.py:26-79; DB head head.py:32-48).
  * ------------------------------------------------------------------------------------------------ */
 typedef struct ocrvi_det ocrvi_det;
 
@@ -57,7 +58,9 @@ typedef struct {
     int32_t dtype;   /* ocrvi_dtype */
     float k;         /* DB step-function steepness, head.py:6,28-30 (reference default 50) */
     int32_t max_batch;  /* largest N a forward call will see (sizes nothing; validated only) */
-    int32_t reserved[5];
+    int32_t backbone;   /* 0 = ResNet-50 (Bottleneck [3,4,6,3]), 1 = ResNet-18 (BasicBlock [2,2,2,2]) -- backbone.py:12-15; else OCRVI_EINVAL */
+    int32_t no_dcn;     /* 0 = DeformableConv2d as conv2 of every block of layer2..4 (backbone.py:28-31), 1 = plain 3x3; else OCRVI_EINVAL */
+    int32_t reserved[3];   /* a zeroed struct is ResNet-50 with DCN; the blob must be of the same architecture (OCRVI_EINVAL otherwise) */
 } ocrvi_det_cfg;
 
 /* `blob` = host bytes produced by ocr_vi_invoice_amd.weights.pack_blob(fold_det(state_dict)): BN already
@@ -86,6 +89,7 @@ int ocrvi_det_binary_workspace_bytes(const ocrvi_det* h, int N, int H, int W, si
 int ocrvi_det_forward_binary(ocrvi_det* h, const float* x, int N, int H, int W, float* binary,
                              void* workspace, size_t workspace_bytes, void* stream);
 /* Test hook: copies of intermediate features as float32 NCHW (c2..c5 backbone.py:56-60, fused neck.py:79).
+ * c2..c5 have 256 / 512 / 1024 / 2048 channels for ResNet-50 and 64 / 128 / 256 / 512 for ResNet-18, at H/4 .. H/32; fused has 256 at H/4.
  * Any pointer may be NULL.  Must follow a forward on the same workspace and stream. */
 /* OCRVI_F16X2 handles: OCRVI_OK, or OCRVI_ERANGE when an f16x2 kernel on this handle's device has met a value fp16's exponent cannot
  * carry since the last ocrvi_range_reset (the flag is per device and sticky; *_forward copies it to the handle asynchronously on the
@@ -442,6 +446,13 @@ int ocrvi_test_offset_conv(int device, int dtype, const float* x, const float* w
 int ocrvi_test_deform_conv(int device, int dtype, const float* x, const float* offset, const float* mask,
                            const float* weight_host, const float* bias_host, int N, int C, int H, int W, int Co,
                            int stride, int relu, float* out, int iters, float* avg_ms);
+/* The same with a residual in the epilogue, as conv2 of a BasicBlock in layers 2-4 of the ResNet-18 backbone has it
+ * (torchvision.models.resnet.BasicBlock with backbone.py:39-53): out = act(deform_conv2d(x) + bias + res).  res: float32 NCHW
+ * [N,Co,Ho,Wo] on the device, converted to NHWC in the compute type exactly as x is (so in the 16-bit modes the kernel reads res rounded
+ * to that type). */
+int ocrvi_test_deform_conv_res(int device, int dtype, const float* x, const float* offset, const float* mask,
+                               const float* weight_host, const float* bias_host, const float* res, int N, int C, int H, int W, int Co,
+                               int stride, int relu, float* out, int iters, float* avg_ms);
 /* Plain conv2d (groups, stride (sh,sw), square kernel 1 or 3, pad = k/2) + bias + activation
  * (0 none, 1 ReLU, 2 exact GELU).  Same conventions as above. */
 int ocrvi_test_conv(int device, int dtype, const float* x, const float* weight_host, const float* bias_host,

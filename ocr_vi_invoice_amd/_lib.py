@@ -31,6 +31,7 @@ EXPORTS = [
     "ocrvi_four_point_transform", "ocrvi_warp_perspective_u8", "ocrvi_warp_perspective_pages",
     "ocrvi_test_layernorm", "ocrvi_test_frm_vertical", "ocrvi_test_asf", "ocrvi_test_maxpool", "ocrvi_test_db_maps", "ocrvi_test_ctc_logsoftmax",
     "ocrvi_det_eval_workspace_bytes", "ocrvi_det_eval", "ocrvi_ctc_loss", "ocrvi_edit_distance",
+    "ocrvi_test_deform_conv_res",
     "ocrvi_enhance_init", "ocrvi_enhance_tables", "ocrvi_enhance_workspace_bytes", "ocrvi_enhance_u8",
     "ocrvi_rgb_to_lab_u8", "ocrvi_lab_to_rgb_u8", "ocrvi_clahe_lab_u8", "ocrvi_nlm_lab_u8", "ocrvi_sharpen_u8",
 ]
@@ -46,7 +47,9 @@ ENHANCE_MIN_SIDE = 16           # the smallest page side the enhance entries tak
 
 
 class DetCfg(C.Structure):
-    _fields_ = [("dtype", C.c_int32), ("k", C.c_float), ("max_batch", C.c_int32), ("reserved", C.c_int32 * 5)]
+    # backbone: 0 = ResNet-50, 1 = ResNet-18; no_dcn: 0 = DCN in layer2..4, 1 = plain 3x3 (a zeroed struct is ResNet-50 with DCN)
+    _fields_ = [("dtype", C.c_int32), ("k", C.c_float), ("max_batch", C.c_int32), ("backbone", C.c_int32), ("no_dcn", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
 
 
 class RecCfg(C.Structure):
@@ -109,6 +112,8 @@ def load() -> C.CDLL:
                                          vp, i32, vp, vp, vp, i32, vp, vp, i32]
     lib.ocrvi_test_deform_conv.argtypes = [i32, i32, f32p, f32p, f32p, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32p, i32,
                                            C.POINTER(C.c_float)]
+    lib.ocrvi_test_deform_conv_res.argtypes = [i32, i32, f32p, f32p, f32p, vp, vp, f32p, i32, i32, i32, i32, i32, i32, i32, f32p, i32,
+                                               C.POINTER(C.c_float)]
     lib.ocrvi_test_offset_conv.argtypes = [i32, i32, f32p, vp, vp, i32, i32, i32, i32, i32, f32p, i32, C.POINTER(C.c_float)]
     lib.ocrvi_test_conv.argtypes = [i32, i32, f32p, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32p, i32,
                                     C.POINTER(C.c_float)]

@@ -88,9 +88,10 @@ int timed(Scratch& sc, int iters, float* avg_ms, F&& launch) {
 }
 }  // namespace
 
-extern "C" int ocrvi_test_deform_conv(int device, int dtype, const float* x, const float* offset, const float* mask,
-                                      const float* weight_host, const float* bias_host, int N, int C, int H, int W, int Co, int stride,
-                                      int relu, float* out, int iters, float* avg_ms) {
+// res: null, or device float32 NCHW [N, Co, Ho, Wo] added in the epilogue before the activation (RES_SAME)
+static int test_deform_conv(int device, int dtype, const float* x, const float* offset, const float* mask, const float* weight_host,
+                            const float* bias_host, const float* res, int N, int C, int H, int W, int Co, int stride, int relu, float* out,
+                            int iters, float* avg_ms) {
     OCRVI_CHECK(x && offset && mask && weight_host && out && (stride == 1 || stride == 2), OCRVI_EINVAL, "test_deform_conv: bad argument");
     OCRVI_HIP(hipSetDevice(device));
     Scratch sc;
@@ -110,12 +111,33 @@ extern "C" int ocrvi_test_deform_conv(int device, int dtype, const float* x, con
     Runner r(dtype, sc.s, (void*)256, 0);
     Tensor tx; tx.p = xn; tx.n = N; tx.h = H; tx.w = W; tx.c = C;
     Tensor ty; ty.p = yn; ty.n = N; ty.h = Ho; ty.w = Wo; ty.c = Co;
+    Tensor tr = ty;
     ConvOpts o;
     o.sh = o.sw = stride; o.pad = 1; o.act = relu ? ACT_RELU : ACT_NONE; o.offs = (const float*)offs;
+    if (res) {   // the residual has the output's shape and element type
+        void* rn = nullptr;
+        OCRVI_TRY(sc.alloc((size_t)N * Ho * Wo * Co * dtype_size(dtype), &rn));
+        OCRVI_TRY(to_nhwc(dtype, res, rn, N, Co, Ho * Wo, sc.s));
+        tr.p = rn;
+        o.res = &tr; o.res_mode = RES_SAME;
+    }
     OCRVI_TRY(timed(sc, iters, avg_ms, [&]() { return conv(r, L, tx, ty, o); }));
     OCRVI_TRY(k_nhwc_to_nchw_f32(dtype, yn, out, N, Ho, Wo, Co, Co, 0, sc.s));
     OCRVI_HIP(hipStreamSynchronize(sc.s));
     return OCRVI_OK;
+}
+
+extern "C" int ocrvi_test_deform_conv(int device, int dtype, const float* x, const float* offset, const float* mask,
+                                      const float* weight_host, const float* bias_host, int N, int C, int H, int W, int Co, int stride,
+                                      int relu, float* out, int iters, float* avg_ms) {
+    return test_deform_conv(device, dtype, x, offset, mask, weight_host, bias_host, nullptr, N, C, H, W, Co, stride, relu, out, iters, avg_ms);
+}
+
+extern "C" int ocrvi_test_deform_conv_res(int device, int dtype, const float* x, const float* offset, const float* mask,
+                                          const float* weight_host, const float* bias_host, const float* res, int N, int C, int H, int W,
+                                          int Co, int stride, int relu, float* out, int iters, float* avg_ms) {
+    OCRVI_CHECK(res, OCRVI_EINVAL, "test_deform_conv_res: res is required");
+    return test_deform_conv(device, dtype, x, offset, mask, weight_host, bias_host, res, N, C, H, W, Co, stride, relu, out, iters, avg_ms);
 }
 
 extern "C" int ocrvi_test_stem_pool(int device, int dtype, const float* x, const float* weight_host, const float* bias_host, int N, int H, int W,

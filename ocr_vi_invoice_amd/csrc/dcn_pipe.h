@@ -22,7 +22,9 @@ namespace ocrvi {
 
 // PROF (development only, -DOCRVI_RING_PROF_BUILD + OCRVI_RING_PROF=1): per wave half (waves 0-3 / 4-7) the shader-clock cycles spent in the tile's
 // geometry pass / waiting for own VMEM / at the barrier / issuing gathers and weight DMA / blending / ds_read + MFMA / in the epilogue, summed into p.out2.
-template <typename T, int BN, bool PROF = false>
+// RES (a BasicBlock's conv2: relu(bn2(conv2(y)) + identity), torchvision.models.resnet.BasicBlock): the epilogue adds p.res, a tensor of the
+// output's element type and row count with p.ldr elements per pixel.  Compile time, so the builds without it are the code they were.
+template <typename T, int BN, bool RES = false, bool PROF = false>
 __global__ __launch_bounds__(512, 2) void dcn_pipe_kernel(const ConvParams p) {
     constexpr int EPC = TypeInfo<T>::EPC, BM = 128;     // elements per 16-byte chunk: 8 (16-bit types) or 4 (fp32)
     constexpr int CB = 8 * EPC;                         // channels per K-step (128 bytes): 64 or 32
@@ -289,11 +291,17 @@ __global__ __launch_bounds__(512, 2) void dcn_pipe_kernel(const ConvParams p) {
                 if (s + 1 < nk) step(s + 1, SA, SB);
             }
         }
-        // ---- epilogue: bias + activation; one 16-byte store per lane (16-bit: 8 consecutive channels thanks to the row permutation,
-        // fp32: the accumulator's 4), 64 contiguous bytes per pixel and instruction
+        // ---- epilogue: bias (+ residual) + activation; one 16-byte store per lane (16-bit: 8 consecutive channels thanks to the row
+        // permutation, fp32: the accumulator's 4), 64 contiguous bytes per pixel and instruction.  RES: every lane reads the 16 bytes of the
+        // residual that lie where its 16 bytes of output go, beside the bias and like it from clamped addresses (row max(m, 0), the bias's
+        // column) outside the per-block branches; only the stores are guarded.  Nothing hand-counted is in flight here (the last step waited
+        // for vmcnt(0)), so these are ordinary compiler-tracked loads.  A RES build also does the arithmetic of a lane whose store is
+        // guarded off: a load whose result a lane never reads stays pending in the compiler's books across the tile loop's back edge, and
+        // it then puts a vmcnt wait of its own between the next tile's first weight stage and first gathers.
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
             const int m = pixel_of(wm * 32 + 16 * b + lr);
+            const T* const rrow = RES ? (const T*)p.res + (size_t)max(m, 0) * p.ldr : nullptr;
             if constexpr (PERM) {
                 float4 bvs[NI / 2][2];   // (bias of all blocks first, clamped addresses, outside the per-block branches: see below)
 #pragma unroll
@@ -302,10 +310,16 @@ __global__ __launch_bounds__(512, 2) void dcn_pipe_kernel(const ConvParams p) {
                     bvs[hh][0] = p.bias ? *(const float4*)(p.bias + n) : make_float4(0.f, 0.f, 0.f, 0.f);
                     bvs[hh][1] = p.bias ? *(const float4*)(p.bias + n + 4) : make_float4(0.f, 0.f, 0.f, 0.f);
                 }
+                uint4 rvs[RES ? NI / 2 : 1];
+                if constexpr (RES) {
+#pragma unroll
+                    for (int hh = 0; hh < NI / 2; ++hh) rvs[hh] = *(const uint4*)(rrow + min(n0 + wn * (BN / 2) + 32 * hh + 8 * g, p.N_g - 8));
+                }
 #pragma unroll
                 for (int hh = 0; hh < NI / 2; ++hh) {
                     const int n = n0 + wn * (BN / 2) + 32 * hh + 8 * g;
-                    if (m >= 0 && n < p.N_g) {
+                    const bool ok = m >= 0 && n < p.N_g;
+                    if (RES || ok) {
                         float v[8];
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
@@ -316,11 +330,17 @@ __global__ __launch_bounds__(512, 2) void dcn_pipe_kernel(const ConvParams p) {
                             v[0] += bvs[hh][0].x; v[1] += bvs[hh][0].y; v[2] += bvs[hh][0].z; v[3] += bvs[hh][0].w;
                             v[4] += bvs[hh][1].x; v[5] += bvs[hh][1].y; v[6] += bvs[hh][1].z; v[7] += bvs[hh][1].w;
                         }
+                        if constexpr (RES) {
+                            float rf[8];
+                            Chunk<T>::unpack(rvs[hh], rf);
+#pragma unroll
+                            for (int r = 0; r < 8; ++r) v[r] += rf[r];
+                        }
                         if (p.act == ACT_RELU) {
 #pragma unroll
                             for (int r = 0; r < 8; ++r) v[r] = fmaxf(v[r], 0.f);
                         }
-                        *(uint4*)((T*)p.out + (size_t)m * p.ldo + p.out_coff + n) = Chunk<T>::pack(v);
+                        if (!RES || ok) *(uint4*)((T*)p.out + (size_t)m * p.ldo + p.out_coff + n) = Chunk<T>::pack(v);
                     }
                 }
             } else {
@@ -332,21 +352,36 @@ __global__ __launch_bounds__(512, 2) void dcn_pipe_kernel(const ConvParams p) {
                     const int n = min(n0 + wn * (BN / 2) + 16 * a + 4 * g, p.N_g - 4);
                     bvs[a] = p.bias ? *(const float4*)(p.bias + n) : make_float4(0.f, 0.f, 0.f, 0.f);
                 }
+                uint4 rvs[RES ? NI : 1];
+                if constexpr (RES) {
+#pragma unroll
+                    for (int a = 0; a < NI; ++a) rvs[a] = *(const uint4*)(rrow + min(n0 + wn * (BN / 2) + 16 * a + 4 * g, p.N_g - 4));
+                }
 #pragma unroll
                 for (int a = 0; a < NI; ++a) {
                     const int n = n0 + wn * (BN / 2) + 16 * a + 4 * g;
-                    if (m >= 0 && n < p.N_g) {
+                    const bool ok = m >= 0 && n < p.N_g;
+                    if (RES || ok) {
                         float v[4] = {unscale<T>(acc[a][b][0], p.wscale), unscale<T>(acc[a][b][1], p.wscale), unscale<T>(acc[a][b][2], p.wscale),
                                       unscale<T>(acc[a][b][3], p.wscale)};
                         {
                             v[0] += bvs[a].x; v[1] += bvs[a].y; v[2] += bvs[a].z; v[3] += bvs[a].w;
                         }
+                        if constexpr (RES) {
+                            float rf[4];
+                            Chunk<T>::unpack(rvs[a], rf);
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) v[r] += rf[r];
+                        }
                         if (p.act == ACT_RELU) {
 #pragma unroll
                             for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
                         }
-                        if constexpr (IsSplit<T>::value) f16x2_raise(f16x2_out_of_range(v));
-                        *(uint4*)((T*)p.out + (size_t)m * p.ldo + p.out_coff + n) = Chunk<T>::pack(v);
+                        if constexpr (IsSplit<T>::value) {   // (the stored values only)
+                            if constexpr (RES) f16x2_raise(f16x2_out_of_range(v) & __builtin_amdgcn_ballot_w64(ok));
+                            else f16x2_raise(f16x2_out_of_range(v));
+                        }
+                        if (!RES || ok) *(uint4*)((T*)p.out + (size_t)m * p.ldo + p.out_coff + n) = Chunk<T>::pack(v);
                     }
                 }
             }
@@ -359,10 +394,17 @@ __global__ __launch_bounds__(512, 2) void dcn_pipe_kernel(const ConvParams p) {
     }
 }
 
+// A residual of the output's own element type (RES_SAME, added before the activation) rides in the epilogue; RES_UP2 does not.
+static inline bool dcn_pipe_res_ok(const ConvParams& p, int dtype) {
+    if (p.res_mode == RES_NONE) return true;
+    return p.res_mode == RES_SAME && p.res != nullptr && !p.res_post && (!p.res_f32 || dtype == OCRVI_F32) && p.ldr % 8 == 0 && p.ldr >= p.N_g &&
+           ((uintptr_t)p.res & 15) == 0;
+}
+
 static inline bool dcn_pipe_eligible(const ConvParams& p, int dtype) {
     const size_t esz = dtype_size(dtype);
     return dcn_pipe_packing(dtype, p.Cin_g) && p.groups == 1 && p.Kp == 9 * p.Cin_g && p.Np % 128 == 0 && p.N_g % 8 == 0 &&
-           p.store_mode == ST_NHWC && p.res_mode == RES_NONE && (!p.out_f32 || dtype == OCRVI_F32) && (p.act == ACT_NONE || p.act == ACT_RELU) &&
+           p.store_mode == ST_NHWC && dcn_pipe_res_ok(p, dtype) && (!p.out_f32 || dtype == OCRVI_F32) && (p.act == ACT_NONE || p.act == ACT_RELU) &&
            p.ldo % 8 == 0 && p.out_coff % 8 == 0 && p.offs != nullptr && (size_t)p.n_img * p.H * p.W * p.Cin * esz < ((size_t)1 << 32);
 }
 
@@ -387,18 +429,19 @@ static int launch_dcn_pipe(const ConvParams& p_in, hipStream_t stream) {
     const int smem = 3 * bn * 128 + 2 * 128 * 128 + 9 * 128 * 20;
 #ifdef OCRVI_RING_PROF_BUILD
     static const bool prof = getenv("OCRVI_RING_PROF") && atoi(getenv("OCRVI_RING_PROF"));
-    if (prof) {  // development aid: cycle breakdown per phase and wave half, printed per launch (synchronises)
+    if (prof && p.res_mode == RES_NONE) {  // development aid: cycle breakdown per phase and wave half, printed per launch (synchronises); the
+                                           // stamped builds have no residual epilogue, so a RES_SAME call runs the plain RES build below
         static unsigned long long* dbuf = nullptr;
         if (!dbuf) OCRVI_HIP(hipMalloc((void**)&dbuf, 128));
         OCRVI_HIP(hipMemsetAsync(dbuf, 0, 128, stream));
         ConvParams q = p;
         q.out2 = dbuf;
         if (wide) {
-            auto k = dcn_pipe_kernel<T, 256, true>;
+            auto k = dcn_pipe_kernel<T, 256, false, true>;
             OCRVI_TRY(ensure_max_smem((const void*)k, smem));
             hipLaunchKernelGGL(k, dim3(grid), dim3(512), smem, stream, q);
         } else {
-            auto k = dcn_pipe_kernel<T, 128, true>;
+            auto k = dcn_pipe_kernel<T, 128, false, true>;
             OCRVI_TRY(ensure_max_smem((const void*)k, smem));
             hipLaunchKernelGGL(k, dim3(grid), dim3(512), smem, stream, q);
         }
@@ -419,15 +462,10 @@ static int launch_dcn_pipe(const ConvParams& p_in, hipStream_t stream) {
         return OCRVI_OK;
     }
 #endif
-    if (wide) {
-        auto k = dcn_pipe_kernel<T, 256>;
-        OCRVI_TRY(ensure_max_smem((const void*)k, smem));
-        hipLaunchKernelGGL(k, dim3(grid), dim3(512), smem, stream, p);
-    } else {
-        auto k = dcn_pipe_kernel<T, 128>;
-        OCRVI_TRY(ensure_max_smem((const void*)k, smem));
-        hipLaunchKernelGGL(k, dim3(grid), dim3(512), smem, stream, p);
-    }
+    auto k = p.res_mode == RES_SAME ? (wide ? dcn_pipe_kernel<T, 256, true> : dcn_pipe_kernel<T, 128, true>)
+                                    : (wide ? dcn_pipe_kernel<T, 256> : dcn_pipe_kernel<T, 128>);
+    OCRVI_TRY(ensure_max_smem((const void*)k, smem));
+    hipLaunchKernelGGL(k, dim3(grid), dim3(512), smem, stream, p);
     OCRVI_HIP(hipGetLastError());
     return OCRVI_OK;
 }

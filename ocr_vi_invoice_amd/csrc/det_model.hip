@@ -1,6 +1,7 @@
-// DBNet++ inference graph (model/det/dbnet.py:13-17): ResNet-50 with DCNv2 in layers 2-4 (backbone.py:39-60,
-// dcn.py:41-59), FPN + adaptive scale fusion (neck.py:26-79), DB head (head.py:32-48).  NHWC activations in the
-// handle's compute dtype; eval-mode BatchNorm is pre-folded into the conv weights by the Python packer.
+// DBNet++ inference graph (model/det/dbnet.py:13-17): ResNet-50 or ResNet-18 (backbone.py:12-31), with DCNv2 in layers 2-4
+// (backbone.py:39-60, dcn.py:41-59) or plain 3x3 convolutions there, FPN + adaptive scale fusion (neck.py:26-79), DB head
+// (head.py:32-48).  NHWC activations in the handle's compute dtype; eval-mode BatchNorm is pre-folded into the conv weights by
+// the Python packer.
 #include <algorithm>
 #include <memory>
 
@@ -10,8 +11,11 @@
 using namespace ocrvi;
 
 namespace {
-const int kBlocks[4] = {3, 4, 6, 3};
+const int kBlocks50[4] = {3, 4, 6, 3}, kBlocks18[4] = {2, 2, 2, 2};
 const int kWidth[4] = {64, 128, 256, 512};
+// One residual block.  Bottleneck (ResNet-50): conv1 1x1, conv2 3x3 (the stride; deformable in layers 2-4), conv3 1x1 + identity.
+// BasicBlock (ResNet-18, torchvision.models.resnet.BasicBlock): conv1 3x3 (the stride), conv2 3x3 stride 1 (deformable in layers 2-4,
+// backbone.py:39-53 replaces every block's conv2) + identity; no conv3.
 struct Bottleneck {
     ConvLayer conv1, conv2, off, conv3, down;
     bool dcn = false, has_down = false;
@@ -30,12 +34,16 @@ struct ocrvi_det {
     ConvLayer head_conv, head_dc1;
     float* dc2_wb = nullptr;  // [2][64][4] second-deconv weights followed by the 2 biases
     Tensor tap_c[4], tap_fused;
+    bool basic = false;   // ResNet-18: BasicBlocks, no channel expansion
+    int expansion = 4;    // block output channels / block width
     RangeWatch range;     // f16x2 only: the device's range flag as of the end of the last forward
 };
 
 extern "C" int ocrvi_det_create(int device, const void* blob_p, size_t blob_bytes, const ocrvi_det_cfg* cfg, ocrvi_det** out) {
     OCRVI_CHECK(cfg && out, OCRVI_EINVAL, "det_create: null argument");
     OCRVI_CHECK(dtype_valid(cfg->dtype), OCRVI_EINVAL, "det_create: bad dtype %d", cfg->dtype);
+    OCRVI_CHECK(cfg->backbone == 0 || cfg->backbone == 1, OCRVI_EINVAL, "det_create: backbone %d (0 = ResNet-50, 1 = ResNet-18)", cfg->backbone);
+    OCRVI_CHECK(cfg->no_dcn == 0 || cfg->no_dcn == 1, OCRVI_EINVAL, "det_create: no_dcn %d (0 or 1)", cfg->no_dcn);
     DeviceGuard dg(device);  // the caller's current device is restored on return
     OCRVI_HIP(dg.err);
     Blob blob;
@@ -44,29 +52,43 @@ extern "C" int ocrvi_det_create(int device, const void* blob_p, size_t blob_byte
     h->device = device;
     h->cfg = *cfg;
     const int dt = cfg->dtype;
+    const bool basic = cfg->backbone == 1, use_dcn = cfg->no_dcn == 0;
+    h->basic = basic;
+    h->expansion = basic ? 1 : 4;
+    {   // the blob must be of the architecture the cfg names: a Bottleneck has a conv3, a deformable conv2 its offset / mask conv
+        const bool has3 = blob.find("layer1.0.conv3.w") != nullptr, has_off = blob.find("layer2.0.conv2.off.w") != nullptr;
+        OCRVI_CHECK(basic || has3, OCRVI_EINVAL, "det_create: cfg.backbone = 0 (ResNet-50) but the blob has no tensor 'layer1.0.conv3.w'");
+        OCRVI_CHECK(!basic || !has3, OCRVI_EINVAL,
+                    "det_create: cfg.backbone = 1 (ResNet-18) but the blob holds the Bottleneck tensor 'layer1.0.conv3.w'");
+        OCRVI_CHECK(!use_dcn || has_off, OCRVI_EINVAL, "det_create: cfg.no_dcn = 0 but the blob has no tensor 'layer2.0.conv2.off.w'");
+        OCRVI_CHECK(use_dcn || !has_off, OCRVI_EINVAL,
+                    "det_create: cfg.no_dcn = 1 but the blob holds the offset / mask tensor 'layer2.0.conv2.off.w'");
+    }
     DeviceStore& st = h->store;
     OCRVI_TRY(load_conv(st, blob, "stem", 64, 3, 7, 1, AM_ROWS, dt, true, &h->stem));
     int inpl = 64;
+    const int ex = h->expansion;
     for (int li = 0; li < 4; ++li) {
         const int w = kWidth[li];
-        h->layers[li].resize(kBlocks[li]);
-        for (int b = 0; b < kBlocks[li]; ++b) {
+        const int nblk = basic ? kBlocks18[li] : kBlocks50[li];
+        h->layers[li].resize(nblk);
+        for (int b = 0; b < nblk; ++b) {
             Bottleneck& bk = h->layers[li][b];
             const std::string p = "layer" + std::to_string(li + 1) + "." + std::to_string(b);
-            bk.dcn = li >= 1;                          // backbone.py:28-31: DCN in layer2..4
-            bk.stride = (b == 0 && li >= 1) ? 2 : 1;   // torchvision Bottleneck v1.5: stride on the 3x3
-            bk.has_down = b == 0;
-            OCRVI_TRY(load_conv(st, blob, p + ".conv1", w, inpl, 1, 1, AM_CONV1, dt, true, &bk.conv1));
+            bk.dcn = use_dcn && li >= 1;               // backbone.py:28-31: DCN in layer2..4
+            bk.stride = (b == 0 && li >= 1) ? 2 : 1;   // torchvision Bottleneck v1.5: stride on the 3x3 (BasicBlock: on conv1)
+            bk.has_down = b == 0 && (!basic || li >= 1);   // (ResNet-18's layer1 keeps 64 channels at stride 1: no downsample)
+            if (basic) OCRVI_TRY(load_conv(st, blob, p + ".conv1", w, inpl, 3, 1, AM_CONV3, dt, true, &bk.conv1));
+            else OCRVI_TRY(load_conv(st, blob, p + ".conv1", w, inpl, 1, 1, AM_CONV1, dt, true, &bk.conv1));
             OCRVI_TRY(load_conv(st, blob, p + ".conv2", w, w, 3, 1, bk.dcn ? AM_DCN : AM_CONV3, dt, true, &bk.conv2));
             if (bk.dcn) OCRVI_TRY(load_conv(st, blob, p + ".conv2.off", 27, w, 3, 1, AM_CONV3, dt, true, &bk.off));
-            OCRVI_TRY(load_conv(st, blob, p + ".conv3", 4 * w, w, 1, 1, AM_CONV1, dt, true, &bk.conv3));
-            if (bk.has_down) OCRVI_TRY(load_conv(st, blob, p + ".down", 4 * w, inpl, 1, 1, AM_CONV1, dt, true, &bk.down));
-            inpl = 4 * w;
+            if (!basic) OCRVI_TRY(load_conv(st, blob, p + ".conv3", 4 * w, w, 1, 1, AM_CONV1, dt, true, &bk.conv3));
+            if (bk.has_down) OCRVI_TRY(load_conv(st, blob, p + ".down", ex * w, inpl, 1, 1, AM_CONV1, dt, true, &bk.down));
+            inpl = ex * w;
         }
     }
-    const int cin[4] = {256, 512, 1024, 2048};
     for (int i = 0; i < 4; ++i) {
-        OCRVI_TRY(load_conv(st, blob, "neck.lat" + std::to_string(i), 256, cin[i], 1, 1, AM_CONV1, dt, true, &h->lat[i]));
+        OCRVI_TRY(load_conv(st, blob, "neck.lat" + std::to_string(i), 256, ex * kWidth[i], 1, 1, AM_CONV1, dt, true, &h->lat[i]));
         OCRVI_TRY(load_conv(st, blob, "neck.fpn" + std::to_string(i), 256, 256, 3, 1, AM_CONV3, dt, true, &h->fpn[i]));
     }
     {
@@ -152,17 +174,48 @@ static int det_run(ocrvi_det* h, Runner& r, const float* x, int N, int H, int W,
     // when it ends, so a chunk of 16 pages keeps ~4 GB less live than with one buffer per block.
     Tensor feats[4];
     for (int li = 0; li < 4; ++li) {
-        const int w = kWidth[li];
+        const int w = kWidth[li], cw = h->expansion * w;
         const int nb = (int)h->layers[li].size();
         const int lh = cur.h / h->layers[li][0].stride, lw = cur.w / h->layers[li][0].stride;
-        Tensor tap = r.alloc(N, lh, lw, 4 * w);                       // the layer's final output
+        Tensor tap = r.alloc(N, lh, lw, cw);                          // the layer's final output
         const size_t slot_mark = r.arena.mark();
-        Tensor slot[2] = {r.alloc(N, lh, lw, 4 * w), r.alloc(N, lh, lw, 4 * w)};
+        Tensor slot[2] = {r.alloc(N, lh, lw, cw), r.alloc(N, lh, lw, cw)};
         for (int b = 0; b < nb; ++b) {
             const Bottleneck& bk = h->layers[li][b];
             const int oh = cur.h / bk.stride, ow = cur.w / bk.stride;
             Tensor y = b == nb - 1 ? tap : slot[b & 1];               // never the buffer `cur` lives in (slot[(b-1)&1] or the previous tap)
             const size_t mark2 = r.arena.mark();
+            if (h->basic) {
+                // BasicBlock: relu(bn2(conv2(relu(bn1(conv1(x))))) + identity); conv1 carries the stride and is never deformable, the
+                // residual and the final ReLU sit in conv2's epilogue (the pipelined deformable kernel's RES build in the 16-bit / f16x2 modes)
+                Tensor t1 = r.alloc(N, oh, ow, w);
+                {
+                    ConvOpts o;
+                    o.sh = o.sw = bk.stride; o.pad = 1; o.act = ACT_RELU;
+                    OCRVI_TRY(conv(r, bk.conv1, cur, t1, o));
+                }
+                Tensor idn = cur;
+                if (bk.has_down) {
+                    idn = r.alloc(N, oh, ow, w);
+                    ConvOpts o;
+                    o.sh = o.sw = bk.stride;
+                    OCRVI_TRY(conv(r, bk.down, cur, idn, o));
+                }
+                ConvOpts o;
+                o.pad = 1; o.act = ACT_RELU; o.res = &idn; o.res_mode = RES_SAME;
+                if (bk.dcn) {   // DeformableConv2d.forward (dcn.py:41-59) at stride 1
+                    float* offs = (float*)r.arena.alloc((size_t)N * oh * ow * 32 * 4);
+                    Tensor ot; ot.p = offs; ot.n = N; ot.h = oh; ot.w = ow; ot.c = 32; ot.f32 = true;
+                    ConvOpts oo;
+                    oo.pad = 1; oo.store_mode = ST_DCN_OFFS;
+                    OCRVI_TRY(conv(r, bk.off, t1, ot, oo));
+                    o.offs = offs;
+                }
+                OCRVI_TRY(conv(r, bk.conv2, t1, y, o));
+                r.arena.release(mark2);
+                cur = y;
+                continue;
+            }
             Tensor t1 = r.alloc(N, cur.h, cur.w, w);
             Tensor t2 = r.alloc(N, oh, ow, w);
             {

@@ -14,14 +14,16 @@ class DBNetPP:
     def __init__(self, backbone: str = "resnet50", pretrained: bool = False, in_channels: int = 3, inner_channels: int = 256,
                  k: float = 50, dcn: bool = True, *, state_dict=None, blob: bytes = None, seed: int = 1234, dtype="f32",
                  device="cuda:0"):
-        if backbone != "resnet50":
-            # the reference also offers resnet18 (backbone.py:12-15); the pipeline only uses resnet50 (pipeline2.py:45)
+        if backbone not in weights.DET_BACKBONES:
+            # backbone.py:12-15 offers resnet50 and resnet18 and raises the same for anything else
             raise NotImplementedError(f"Backbone {backbone} not implemented")
         if pretrained:
             raise RuntimeError("pretrained=True downloads torchvision ImageNet weights (backbone.py:17); there is no network -- "
                                "pass state_dict= (inference callers use pretrained=False, pipeline2.py:45)")
-        if in_channels != 3 or inner_channels != 256 or not dcn:
-            raise ValueError("only the pipeline configuration (in_channels=3, inner_channels=256, dcn=True) is built")
+        if in_channels != 3 or inner_channels != 256:
+            raise ValueError("only in_channels=3 and inner_channels=256 (the reference's defaults, dbnet.py:7) are built")
+        self.backbone = backbone
+        self.dcn = bool(dcn)
         self.k = float(k)
         self.device = torch.device(device)
         self.dtype = _lib.dtype_code(dtype)
@@ -33,7 +35,7 @@ class DBNetPP:
         if blob is not None:        # already folded + packed (weights.pack_blob): what rank 0 broadcasts to the other ranks
             self.load_blob(blob)
         else:
-            self.load_state_dict(state_dict if state_dict is not None else weights.make_det_state_dict(seed))
+            self.load_state_dict(state_dict if state_dict is not None else weights.make_det_state_dict(seed, backbone=self.backbone, dcn=self.dcn))
 
     def load_state_dict(self, state_dict, strict: bool = True):
         """nn.Module.load_state_dict semantics for the keys the inference graph uses: with ``strict`` (default) a missing tensor
@@ -50,7 +52,10 @@ class DBNetPP:
             base.update(weights.unwrap_checkpoint(state_dict))
             state_dict = base
         try:
-            folded = weights.fold_det(state_dict)
+            folded = weights.fold_det(state_dict, backbone=self.backbone, dcn=self.dcn)
+        except weights.UnexpectedKeyError as e:
+            raise RuntimeError(f"Error(s) in loading state_dict for DBNetPP(backbone={self.backbone!r}, dcn={self.dcn}): unexpected key {e} "
+                               "(the state_dict is of another architecture)") from None
         except KeyError as e:
             raise RuntimeError(f"Error(s) in loading state_dict for DBNetPP: missing key {e}") from None
         self._state = {k: (v.detach().clone() if isinstance(v, torch.Tensor) else v) for k, v in weights.unwrap_checkpoint(state_dict).items()}
@@ -69,6 +74,8 @@ class DBNetPP:
         cfg.dtype = self.dtype
         cfg.k = self.k
         cfg.max_batch = 0
+        cfg.backbone = weights.DET_BACKBONES.index(self.backbone)
+        cfg.no_dcn = 0 if self.dcn else 1
         h = C.c_void_p()
         _lib.check(_lib.load().ocrvi_det_create(self._dev_index(), blob, len(blob), C.byref(cfg), C.byref(h)))
         self._free()
@@ -182,7 +189,8 @@ class DBNetPP:
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
         N, _, H, W = x.shape
         self.forward(x, binary_only=True)
-        shapes = {"c2": (256, 4), "c3": (512, 8), "c4": (1024, 16), "c5": (2048, 32), "fused": (256, 4)}
+        ex = 1 if self.backbone == "resnet18" else 4     # BasicBlocks do not expand
+        shapes = {"c2": (64 * ex, 4), "c3": (128 * ex, 8), "c4": (256 * ex, 16), "c5": (512 * ex, 32), "fused": (256, 4)}
         out = {k: torch.empty((N, c, H // s, W // s), dtype=torch.float32, device=self.device) for k, (c, s) in shapes.items()}
         ws = self._workspace(N, H, W)
         stream = torch.cuda.current_stream(self.device).cuda_stream

@@ -36,6 +36,9 @@ NUM_CLASSES = 232  # 230 chars + blank + pad (tokenizer.py:21)
 # torchvision resnet50: Bottleneck counts and widths per layer
 R50_BLOCKS = [3, 4, 6, 3]
 R50_WIDTH = [64, 128, 256, 512]
+# torchvision resnet18: BasicBlock counts per layer; same widths, no channel expansion
+R18_BLOCKS = [2, 2, 2, 2]
+DET_BACKBONES = ("resnet50", "resnet18")
 
 
 # ----------------------------------------------------------------------------- generators
@@ -132,38 +135,54 @@ def make_rec_state_dict(variant: str = "base", seed: int = 1234) -> "OrderedDict
     return sd
 
 
-def make_det_state_dict(seed: int = 1234, dcn_offset_std: float = 1.5) -> "OrderedDict[str, torch.Tensor]":
-    """Seeded DBNet++ (ResNet-50-DCN) weights in the reference key schema.
+def make_det_state_dict(seed: int = 1234, dcn_offset_std: float = 1.5, backbone: str = "resnet50",
+                        dcn: bool = True) -> "OrderedDict[str, torch.Tensor]":
+    """Seeded DBNet++ weights in the reference key schema, for either backbone of backbone.py:12-15 and with or
+    without DCN (the defaults, ResNet-50-DCN, draw the random stream they always drew).
 
-    Backbone keys follow torchvision's resnet50 naming under ``backbone.model.`` (backbone.py:16-37);
-    the aliases ``backbone.layerN.*`` the reference's ``state_dict()`` also carries are not emitted
-    (``fold_det`` accepts either).  ``dcn_offset_std`` sets the scale of the offset conv so offsets are
-    a few pixels (the reference zero-inits it, dcn.py:28-29, which would hide sampling bugs).
+    Backbone keys follow torchvision's resnet50 / resnet18 naming under ``backbone.model.`` (backbone.py:16-37):
+    Bottlenecks ``layerL.B.{conv1,bn1,conv2,bn2,conv3,bn3}``, BasicBlocks ``layerL.B.{conv1,bn1,conv2,bn2}``,
+    ``downsample.{0,1}`` where the shape changes, and ``conv2.offset_mask_conv.{weight,bias}`` in layers 2-4 when
+    ``dcn`` (backbone.py:39-53 replaces every block's conv2).  The aliases ``backbone.layerN.*`` the reference's
+    ``state_dict()`` also carries are not emitted (``fold_det`` accepts either).  ``dcn_offset_std`` sets the scale
+    of the offset conv so offsets are a few pixels (the reference zero-inits it, dcn.py:28-29, which would hide
+    sampling bugs).
     """
+    if backbone not in DET_BACKBONES:
+        raise NotImplementedError(f"Backbone {backbone} not implemented")
+    basic = backbone == "resnet18"
+    ex = 1 if basic else 4
     g = _Gen(seed)
     sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
     bb = "backbone.model."
     _conv(sd, g, bb + "conv1", 64, 3, 7, 7, False)
     _bn(sd, g, bb + "bn1", 64)
     inpl = 64
-    for li, (nblk, w) in enumerate(zip(R50_BLOCKS, R50_WIDTH), start=1):
+    for li, (nblk, w) in enumerate(zip(R18_BLOCKS if basic else R50_BLOCKS, R50_WIDTH), start=1):
         for b in range(nblk):
             p = f"{bb}layer{li}.{b}"
-            _conv(sd, g, p + ".conv1", w, inpl, 1, 1, False)
+            if basic:
+                _conv(sd, g, p + ".conv1", w, inpl, 3, 3, False)
+            else:
+                _conv(sd, g, p + ".conv1", w, inpl, 1, 1, False)
             _bn(sd, g, p + ".bn1", w)
-            _conv(sd, g, p + ".conv2", w, w, 3, 3, False)
-            if li >= 2:  # DeformableConv2d (backbone.py:28-31, dcn.py:17-32)
+            # (a BasicBlock's conv2 feeds the residual sum directly: damped like the Bottleneck's conv3 so that activations stay O(1))
+            _conv(sd, g, p + ".conv2", w, w, 3, 3, False, **({"gain": 1.0} if basic else {}))
+            if dcn and li >= 2:  # DeformableConv2d (backbone.py:28-31, dcn.py:17-32)
                 fan_in = w * 9
                 sd[p + ".conv2.offset_mask_conv.weight"] = g.normal((27, w, 3, 3), dcn_offset_std / math.sqrt(fan_in))
                 sd[p + ".conv2.offset_mask_conv.bias"] = g.normal((27,), 0.5)
-            _bn(sd, g, p + ".bn2", w)
-            _conv(sd, g, p + ".conv3", 4 * w, w, 1, 1, False, gain=1.0)
-            _bn(sd, g, p + ".bn3", 4 * w, gamma=(0.2, 0.6))
-            if b == 0:
-                _conv(sd, g, p + ".downsample.0", 4 * w, inpl, 1, 1, False, gain=1.0)
-                _bn(sd, g, p + ".downsample.1", 4 * w, gamma=(0.4, 0.8))
-            inpl = 4 * w
-    for i, c in enumerate([256, 512, 1024, 2048]):
+            if basic:
+                _bn(sd, g, p + ".bn2", w, gamma=(0.2, 0.6))
+            else:
+                _bn(sd, g, p + ".bn2", w)
+                _conv(sd, g, p + ".conv3", 4 * w, w, 1, 1, False, gain=1.0)
+                _bn(sd, g, p + ".bn3", 4 * w, gamma=(0.2, 0.6))
+            if b == 0 and (not basic or li >= 2):   # (ResNet-18's layer1 keeps 64 channels at stride 1)
+                _conv(sd, g, p + ".downsample.0", ex * w, inpl, 1, 1, False, gain=1.0)
+                _bn(sd, g, p + ".downsample.1", ex * w, gamma=(0.4, 0.8))
+            inpl = ex * w
+    for i, c in enumerate([ex * w for w in R50_WIDTH]):
         _conv(sd, g, f"neck.lateral_convs.{i}", 256, c, 1, 1, True, gain=1.0)
         _conv(sd, g, f"neck.fpn_convs.{i}.conv", 256, 256, 3, 3, False)
         _bn(sd, g, f"neck.fpn_convs.{i}.bn", 256)
@@ -271,13 +290,44 @@ def _bb_key(sd, li, b, rest):
     raise KeyError(k)
 
 
-def fold_det(state_dict) -> "OrderedDict[str, np.ndarray]":
+def _has_bb(sd, li, b, rest) -> bool:
+    try:
+        _bb_key(sd, li, b, rest)
+        return True
+    except KeyError:
+        return False
+
+
+class UnexpectedKeyError(KeyError):
+    """A key that is present but belongs to another architecture than the caller named (``fold_det(..., backbone=, dcn=)``)."""
+
+
+def det_arch(state_dict) -> Tuple[str, bool]:
+    """(backbone, dcn) of a detector state_dict, read off its keys: a ``layer1.0.conv3.weight`` means Bottlenecks
+    (ResNet-50), a ``layer2.0.conv2.offset_mask_conv.weight`` means DCN in layers 2-4."""
     sd = unwrap_checkpoint(state_dict)
+    return ("resnet50" if _has_bb(sd, 1, 0, "conv3.weight") else "resnet18"), _has_bb(sd, 2, 0, "conv2.offset_mask_conv.weight")
+
+
+def fold_det(state_dict, backbone: str = None, dcn: bool = None) -> "OrderedDict[str, np.ndarray]":
+    """BN-folded tensors of either backbone, with or without DCN; both choices are inferred from the keys (``det_arch``).
+    ``backbone=`` / ``dcn=`` state what the caller expects: a state_dict of another architecture then raises a ``KeyError``
+    naming the key that decides it -- plain when that key is missing, ``UnexpectedKeyError`` when it is there and should not be."""
+    sd = unwrap_checkpoint(state_dict)
+    got_bb, got_dcn = det_arch(sd)
+    if backbone is not None:
+        if backbone not in DET_BACKBONES:
+            raise NotImplementedError(f"Backbone {backbone} not implemented")
+        if backbone != got_bb:   # (resnet50 wanted: conv3 is missing; resnet18 wanted: conv3 is there and a BasicBlock has none)
+            raise (KeyError if backbone == "resnet50" else UnexpectedKeyError)("backbone.model.layer1.0.conv3.weight")
+    if dcn is not None and bool(dcn) != got_dcn:
+        raise (KeyError if dcn else UnexpectedKeyError)("backbone.model.layer2.0.conv2.offset_mask_conv.weight")
+    basic = got_bb == "resnet18"
     out: "OrderedDict[str, np.ndarray]" = OrderedDict()
     c1 = "backbone.model.conv1.weight" if "backbone.model.conv1.weight" in sd else "backbone.layer1.0.weight"
     b1 = "backbone.model.bn1" if "backbone.model.bn1.weight" in sd else "backbone.layer1.1"
     out["stem.w"], out["stem.b"] = _fold_bn(sd[c1], None, sd, b1)
-    for li, nblk in enumerate(R50_BLOCKS, start=1):
+    for li, nblk in enumerate(R18_BLOCKS if basic else R50_BLOCKS, start=1):
         for b in range(nblk):
             p = f"layer{li}.{b}"
 
@@ -286,11 +336,12 @@ def fold_det(state_dict) -> "OrderedDict[str, np.ndarray]":
 
             out[p + ".conv1.w"], out[p + ".conv1.b"] = _fold_bn(sd[_bb_key(sd, li, b, "conv1.weight")], None, sd, bnp("bn1"))
             out[p + ".conv2.w"], out[p + ".conv2.b"] = _fold_bn(sd[_bb_key(sd, li, b, "conv2.weight")], None, sd, bnp("bn2"))
-            if li >= 2:
+            if got_dcn and li >= 2:
                 out[p + ".conv2.off.w"] = _plain(sd, _bb_key(sd, li, b, "conv2.offset_mask_conv.weight"))
                 out[p + ".conv2.off.b"] = _plain(sd, _bb_key(sd, li, b, "conv2.offset_mask_conv.bias"))
-            out[p + ".conv3.w"], out[p + ".conv3.b"] = _fold_bn(sd[_bb_key(sd, li, b, "conv3.weight")], None, sd, bnp("bn3"))
-            if b == 0:
+            if not basic:
+                out[p + ".conv3.w"], out[p + ".conv3.b"] = _fold_bn(sd[_bb_key(sd, li, b, "conv3.weight")], None, sd, bnp("bn3"))
+            if b == 0 and (not basic or li >= 2):
                 out[p + ".down.w"], out[p + ".down.b"] = _fold_bn(
                     sd[_bb_key(sd, li, b, "downsample.0.weight")], None, sd, bnp("downsample.1"))
     for i in range(4):

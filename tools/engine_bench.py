@@ -197,6 +197,8 @@ def main():
                     help="run the uniform / mixed sets a second time with Engine(binary_head=True); results under 'runs_binary_head'")
     ap.add_argument("--quads", action="store_true",
                     help="time the perspective warp ('warp') and run the uniform / mixed sets with a quad on every page ('runs_quads')")
+    ap.add_argument("--backbone", default="resnet50", choices=["resnet50", "resnet18"], help="the detector's backbone (backbone.py:12-15)")
+    ap.add_argument("--no-dcn", action="store_true", help="plain 3x3 convolutions in layers 2-4 instead of the deformable ones (dcn=False)")
     args = ap.parse_args()
     import torch
     from ocr_vi_invoice_amd import DBNetPP, SVTRv2, weights
@@ -204,13 +206,15 @@ def main():
     assert torch.cuda.is_available(), "engine_bench needs a GPU"
     torch.cuda.set_device(0)
     sets = args.sets.split(",")
-    res = {"tool": "engine_bench", "dtype": args.dtype, "steps": args.steps, "warmup": args.warmup}
+    res = {"tool": "engine_bench", "dtype": args.dtype, "steps": args.steps, "warmup": args.warmup, "backbone": args.backbone,
+           "dcn": not args.no_dcn}
     if "preproc" in sets:
         res["preproc"] = time_preproc()
     if args.quads:
         res["warp"] = time_warp()
     if "uniform" in sets or "mixed" in sets:
-        det = DBNetPP(pretrained=False, state_dict=weights.make_det_state_dict(seed=1234), dtype=args.dtype)
+        det = DBNetPP(backbone=args.backbone, pretrained=False, dcn=not args.no_dcn, dtype=args.dtype,
+                      state_dict=weights.make_det_state_dict(seed=1234, backbone=args.backbone, dcn=not args.no_dcn))
         rec = SVTRv2("base", state_dict=weights.make_rec_state_dict("base", seed=1234), dtype=args.dtype)
         pp = DBPostProcessor(thresh=0.3, box_thresh=0.5, max_candidates=1000, unclip_ratio=1.6)
         kw = dict(rec_size=(48, 320), det_chunk=16, rec_batch=256)
