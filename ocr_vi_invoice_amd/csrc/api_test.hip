@@ -184,11 +184,13 @@ extern "C" int ocrvi_test_conv(int device, int dtype, const float* x, const floa
     const int amode = ksize == 1 ? AM_CONV1 : AM_CONV3;
     DeviceStore st;
     ConvLayer L;
-    PackedConv pc = pack_conv(weight_host, bias_host, Co, C / groups, ksize, ksize, groups, amode, dtype);
-    OCRVI_TRY(upload_packed(st, pc, amode, &L));
-    void *xn = nullptr, *yn = nullptr;
     // OCRVI_TEST_PADC=n (timing experiments only; the result is then meaningless): give the activation rows a channel stride of C + n
     const int padc = getenv("OCRVI_TEST_PADC") ? atoi(getenv("OCRVI_TEST_PADC")) : 0;
+    // (as a model's loader would: a stride-1 3x3 with a bias + ReLU / none epilogue asks for conv3_halo's weight form)
+    const bool halo = ksize == 3 && sh == 1 && sw == 1 && (act == ACT_NONE || act == ACT_RELU) && padc % 4 == 0;
+    PackedConv pc = pack_conv(weight_host, bias_host, Co, C / groups, ksize, ksize, groups, amode, dtype, halo);
+    OCRVI_TRY(upload_packed(st, pc, amode, &L));
+    void *xn = nullptr, *yn = nullptr;
     OCRVI_TRY(sc.alloc((size_t)N * H * W * (C + padc) * dtype_size(dtype), &xn));
     OCRVI_TRY(sc.alloc((size_t)N * Ho * Wo * Co * dtype_size(dtype), &yn));
     OCRVI_TRY(to_nhwc(dtype, x, xn, N, C, H * W, sc.s));

@@ -10,7 +10,14 @@
 // pixels (y + dy) * 18 + dx + 0..15).  The weights stream per (channel block, tap) unit -- Np rows x 128 B, `sc1` (a layer's weights stay
 // resident in L2) -- through a ring of NWS units (64 KiB in all: 4 / 8 units for 128 / 64 columns), NWS - 1 units ahead.  One counted
 // vmcnt wait + barrier per unit.  The waves split the tile as WP pixel groups x WC column groups of 64 channels (RW output rows x four
-// 16-channel blocks each: 4 x 4 or 2 x 4 accumulator blocks), in two passes of two blocks (16 weight registers).
+// 16-channel blocks each: 4 x 4 or 2 x 4 accumulator blocks), in ONE pass per unit with the four blocks' weight fragments in registers.
+//
+// Fragment reads run one stage ahead of the MFMAs that use them: a row's pixel fragment goes out under the MFMAs of the row before, and a
+// unit's four weight fragments and first pixel row go out under the LAST row of the unit before -- across the unit's barrier, the
+// patch-stage switch behind tap 8 and the tile boundary (ahead of the epilogue's stores).  Both waves of a SIMD pass a unit's barrier
+// together, so an LDS round trip left between the barrier and the first MFMA stalls the matrix pipe outright.  The weights are packed on
+// the host as (hi, lo) quartets (pack_conv / conv3_halo_packing: the layer's loader asks for it), so a weight fragment is two
+// ds_read_b128 and no register regrouping; the pixel fragments (activations, chunk form) are regrouped once per unit and row.
 //
 // Patch (and weight) rows are XOR-swizzled by bits 1 and 2 of the pixel (row) index (swz_halo): fragment reads that start at ANY pixel are
 // conflict-free under the gfx950 ds_read_b128 lane groups (each group reads chunks {c, c ^ 2} of 8 consecutive pixels mod 8; the swizzle
@@ -18,13 +25,25 @@
 //
 // f16x2 arithmetic as everywhere: Mma<f16x2_t>::regroup / three, fp32 accumulation.  The K order is (channel block, tap, channel) instead
 // of the implicit GEMM's (tap, channel): results differ from conv_gemm by fp32 rounding only.  Neither the kernel choice nor the K order
-// depends on n_img or M (a page alone and inside a batch give the same bits).  OCRVI_CONV3_HALO=0 falls back to conv_gemm.
+// depends on n_img or M (a page alone and inside a batch give the same bits).  OCRVI_CONV3_HALO=0 falls back to conv_gemm (read by the
+// weight packer, which then keeps the chunk form that conv_gemm reads).
 //
-// vmcnt protocol (per wave, VMEM ops retire in issue order): at step s the wait must cover weight unit s.  Younger than it are the NWS - 2
-// later units (WPW pieces each), the patch of the next stage when it was issued at tap 0 of this stage after unit s (taps 1 .. NWS - 2:
-// at least PPW_MIN pieces per wave), and the previous tile's epilogue stores when they came after unit s (STORES per wave, unconditional:
-// out-of-range lanes store to the dump page).  Past the last step the stream keeps issuing (harmless units into free slots, a zero patch),
-// so these counts never change; the range flag's store can only add younger operations (a longer wait, never a shorter one).
+// vmcnt protocol (per wave, VMEM ops retire in issue order): at step s the wait must cover weight unit s + 1, not only unit s -- each wave
+// waits for its own pieces of unit s + 1 BEFORE barrier s, so behind barrier s unit s + 1 is readable by every wave and the last row of
+// step s may request its fragments.  (A prologue wait + barrier does the same for unit 0 and the first patch.)  issue_w at step s still
+// refills the slot of unit s - 1, which nobody reads any more: its last readers were the MFMAs of step s - 1, in front of barrier s.
+// Younger than unit s + 1 at the wait of step s are
+//   * the NWS - 3 later units, WPW pieces each (one unit at 128 columns, five at 64);
+//   * the patch of the next stage, issued at tap 0 of this stage between units s0 + NWS - 2 and s0 + NWS - 1 (s0 = the stage's first step):
+//     younger than unit s + 1 at taps 1 .. NWS - 3 (at least PPW_MIN pieces per wave), older -- hence covered -- from tap NWS - 2 on.
+//     Tap 8 >= NWS - 2 for every ring depth, so the patch has landed for every wave behind barrier (tap 8), where the look-ahead of the
+//     next stage's tap 0 first reads it; with one channel block per tile (Cin = 32) that is the next TILE's patch, same count;
+//   * the previous tile's epilogue stores, issued between the last step of a tile and step s0 of the next, i.e. behind unit s0 + NWS - 2:
+//     younger than unit s + 1 at taps 0 .. NWS - 3 of the tile's first stage (STORES per wave, unconditional: out-of-range lanes store to
+//     the dump page), older from tap NWS - 2 on.
+// Past the last step the stream keeps issuing (harmless units into free slots, a zero patch), so these counts never change and the
+// look-ahead behind the last unit of the last tile reads a landed, harmless unit; the range flag's store can only add younger operations
+// (a longer wait, never a shorter one).
 #pragma once
 #include "gemm_ring.h"
 
@@ -135,6 +154,8 @@ __global__ __launch_bounds__(512, 2) void conv3_halo_kernel(const ConvParams p, 
     for (int u = 0; u < NWS - 1; ++u) issue_w();
 
     typedef typename Mma<T>::u4v U;
+    static_assert(NWS >= 4, "the wait of step s covers unit s + 1 and leaves NWS - 3 units in flight");
+    static_assert(RW >= 2, "a unit's last row fetches the next unit's fragments, the rows before it the next row");
     f32x4 acc[RW][4];
     const int row0 = wp * RW;                                          // first output row of this wave in the tile
     const int ncol0 = wc * 64;
@@ -153,20 +174,34 @@ __global__ __launch_bounds__(512, 2) void conv3_halo_kernel(const ConvParams p, 
 #pragma unroll
     for (int h = 0; h < 2; ++h) woff[h] = (ncol0 + lr) * 128 + (((2 * g + h) ^ swz_halo(lr)) << 4);
     int s = 0;                                                         // step (= weight unit) index
-    int pcur = 0;                                                      // patch buffer offset xoff holds
+    int pbuf = 0;                                                      // patch buffer (0 / 1) whose offset xoff holds
+    // The unit's four weight fragments and its first pixel row, requested one unit ahead (by `ahead`, under the last row of MFMAs of the
+    // unit before) so that no LDS round trip stands between a unit's barrier and its first MFMA.
+    U wH[4], wL[4];
+    uint4 x0[2];
+    auto ahead = [&](auto tn) {   // fragments of the unit with tap TN in ring slot (s + 1): legal once barrier s is passed (see the protocol)
+        constexpr int TN = decltype(tn)::value, k = (TN / 3) * PW + TN % 3;
+        const char* const Wn = smem + 2 * C::PATCH + ((s + 1) & (NWS - 1)) * C::WU;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            wH[a] = Mma<T>::as_u4v(lds16(Wn + woff[0] + a * 16 * 128));   // (hi, lo) quartets: packed that way (pack_conv)
+            wL[a] = Mma<T>::as_u4v(lds16(Wn + woff[1] + a * 16 * 128));
+        }
+        x0[0] = lds16(smem + xoff[k & 7][0] + k * 128);
+        x0[1] = lds16(smem + xoff[k & 7][1] + k * 128);
+    };
+    // unit 0 and the first patch have landed (younger: units 1 .. NWS - 2), for every wave: its fragments
+    wait_vm_barrier<(NWS - 2) * WPW>();
+    --s;
+    ahead(IC<0>());
+    ++s;
     for (int t = 0; t < my_tiles; ++t) {
         for (int cb = 0; cb < ncb; ++cb) {
             const bool after_epi = cb == 0 && t > 0;
-            {   // this stage's patch buffer, folded into the per-lane offsets (in place: no second set of 16 registers)
-                const int want = ((t * ncb + cb) & 1) * C::PATCH, d = want - pcur;
-                pcur = want;
-#pragma unroll
-                for (int m = 0; m < 8; ++m) { xoff[m][0] += d; xoff[m][1] += d; }
-            }
             auto step = [&](auto tc) {
                 constexpr int TAP = decltype(tc)::value, DY = TAP / 3, DX = TAP % 3;
-                constexpr int NB = (NWS - 2) * WPW + ((TAP >= 1 && TAP <= NWS - 2) ? C::PPW_MIN : 0);
-                constexpr int NA = NB + (TAP <= NWS - 2 ? C::STORES : 0);
+                constexpr int NB = (NWS - 3) * WPW + ((TAP >= 1 && TAP <= NWS - 3) ? C::PPW_MIN : 0);
+                constexpr int NA = NB + (TAP <= NWS - 3 ? C::STORES : 0);
                 if (after_epi) wait_vm_barrier<NA>(); else wait_vm_barrier<NB>();
                 if constexpr (TAP == 0) issue_patch();   // next stage into the patch buffer every wave is done reading
                 issue_w();                            // unit s + NWS - 1 into the slot of unit s - 1
@@ -176,35 +211,44 @@ __global__ __launch_bounds__(512, 2) void conv3_halo_kernel(const ConvParams p, 
 #pragma unroll
                         for (int a = 0; a < 4; ++a) acc[r][a] = (f32x4){0.f, 0.f, 0.f, 0.f};
                 }
-                const char* const Ws = smem + 2 * C::PATCH + (s & (NWS - 1)) * C::WU;
-                // two passes over the wave's rows, one per pair of 16-channel blocks: 16 weight registers instead of 32 (the pixel fragments
-                // are read twice; LDS bandwidth has room for it, the register file does not)
+                // one pass over the wave's rows with all four 16-channel blocks' weights in registers; pixel rows one row ahead
+                U cH[4], cL[4];
 #pragma unroll
-                for (int ap = 0; ap < 2; ++ap) {
-                    if (ap) asm volatile("" ::: "memory");   // (re-read: left alone hipcc keeps the first pass's fragments live)
-                    U wH[2], wL[2];
+                for (int a = 0; a < 4; ++a) {
+                    cH[a] = wH[a]; cL[a] = wL[a];
+                    asm volatile("" : "+v"(cH[a]), "+v"(cL[a]));   // (waited for here, ahead of the row reads below, not at the first MFMA behind them)
+                }
+                uint4 xf[RW][2];                   // (one name per row: each dies with its row's MFMAs, so two rows are live at a time)
+                xf[0][0] = x0[0]; xf[0][1] = x0[1];
+                auto rdx = [&](int r) {   // (r, DY, DX compile-time: the pixel offset is the ds_read's immediate)
+                    const int k = (r + DY) * PW + DX;
+                    xf[r][0] = lds16(smem + xoff[k & 7][0] + k * 128);
+                    xf[r][1] = lds16(smem + xoff[k & 7][1] + k * 128);
+                };
 #pragma unroll
-                    for (int a = 0; a < 2; ++a)
-                        Mma<T>::regroup(lds16(Ws + woff[0] + (2 * ap + a) * 16 * 128), lds16(Ws + woff[1] + (2 * ap + a) * 16 * 128), wH[a], wL[a]);
-                    uint4 xf[2][2];
-                    auto rdx = [&](int r, int set) {   // (r, DY, DX compile-time: the pixel offset is the ds_read's immediate)
-                        const int k = (r + DY) * PW + DX;
-                        xf[set][0] = lds16(smem + xoff[k & 7][0] + k * 128);
-                        xf[set][1] = lds16(smem + xoff[k & 7][1] + k * 128);
-                    };
-                    rdx(0, 0);
-                    // (fenced: hipcc otherwise sinks each fragment read to its first MFMA behind an lgkmcnt(0))
+                for (int r = 0; r < RW; ++r) {
+                    // This row's fragment (requested a row of MFMAs ago: it has landed) is regrouped first, then the next row's reads go out,
+                    // then the MFMAs -- each part fenced: left alone hipcc sinks every read to its first use behind an lgkmcnt(0), and a read
+                    // issued ahead of the regrouping gets a full wait directly behind it.
+                    U xH, xL;
+                    Mma<T>::regroup(xf[r][0], xf[r][1], xH, xL);
+                    asm volatile("" : "+v"(xH), "+v"(xL));   // (the regrouping's moves are made here, not behind the reads below)
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (r + 1 < RW) {
+                        rdx(r + 1);
+                    } else {   // the next unit's fragments; behind tap 8 they come from the other patch buffer, folded into the per-lane offsets
+                        if constexpr (TAP == 8) {
+                            const int d = pbuf ? -C::PATCH : C::PATCH;
+                            pbuf ^= 1;
+#pragma unroll
+                            for (int m = 0; m < 8; ++m) { xoff[m][0] += d; xoff[m][1] += d; }
+                        }
+                        ahead(IC<(TAP + 1) % 9>());
+                    }
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                    for (int r = 0; r < RW; ++r) {
-                        if (r + 1 < RW) rdx(r + 1, (r + 1) & 1);
-                        __builtin_amdgcn_sched_barrier(0);
-                        U xH, xL;
-                        Mma<T>::regroup(xf[r & 1][0], xf[r & 1][1], xH, xL);
-#pragma unroll
-                        for (int a = 0; a < 2; ++a) Mma<T>::three(wH[a], wL[a], xH, xL, acc[r][2 * ap + a]);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
+                    for (int a = 0; a < 4; ++a) Mma<T>::three(cH[a], cL[a], xH, xL, acc[r][a]);
+                    __builtin_amdgcn_sched_barrier(0);
                 }
                 ++s;
             };

@@ -57,6 +57,7 @@ struct ConvParams {
     int res_in_store = 0;  // fp32 out + fp32 residual, no activation: add the residual in the coalesced store phase
     int patch_lw = 7;      // dcn_pipe: a tile is a (128 >> patch_lw) x (1 << patch_lw) patch of output pixels
     unsigned out_bytes = 0;   // gemm_ring: bytes of the output tensor the stores may touch (buffer descriptor range; filled by launch_gemm_ring)
+    int w_quartets = 0;    // f16x2: the weights are packed as (hi, lo) quartets for conv3_halo (PackedConv::quartets); no other 3x3 kernel reads that form
     float wscale = 1.f;    // f16x2: the weights are stored multiplied by 2^s (one power of two per layer, chosen by the packer so that their
                            // lo halves are normal fp16 numbers); every epilogue multiplies the accumulator by wscale = 2^-s (exact)
 };
@@ -557,6 +558,15 @@ static inline bool dcn_pipe_packing(int dtype, int cin_g) {
     return on && (dtype != OCRVI_F32 || on32) && cin_g % dcn_pipe_block(dtype) == 0;
 }
 
+// Dense 3x3 layers that their loader runs at stride 1 / pad 1 with a bias + ReLU / none epilogue go to conv3_halo.h in the f16x2 mode, which
+// reads its weight fragments as (hi, lo) quartets without regrouping them in registers: the packer stores them that way, so packer and
+// launcher must agree, and both ask this.  (The stride is not the packer's to know -- the recogniser's stride-2 merge convolutions have the
+// same Np -- hence `halo` is the loader's request; OCRVI_CONV3_HALO=0 keeps the chunk form and conv_gemm.)
+static inline bool conv3_halo_packing(bool halo, int dtype, int cin_g, int n_g, int kh, int groups, int Np) {
+    static const bool on = !(getenv("OCRVI_CONV3_HALO") && atoi(getenv("OCRVI_CONV3_HALO")) == 0);   // A/B switch (0: conv_gemm)
+    return on && halo && dtype == OCRVI_F16X2 && groups == 1 && kh == 3 && cin_g % 32 == 0 && n_g % 4 == 0 && (Np == 64 || Np == 128 || Np == 256);
+}
+
 template <typename T> int launch_conv(const ConvParams& p, int amode, hipStream_t stream);
 int launch_conv_dt(int dtype, const ConvParams& p, int amode, hipStream_t stream);
 
@@ -565,10 +575,12 @@ struct PackedConv {
     std::vector<char> bytes;
     std::vector<float> bias;  // expanded (ST_SHUFFLE2: 4x)
     int Np = 0, Kp = 0, N_g = 0, Cin_g = 0, groups = 1, KH = 1;
+    bool quartets = false;    // f16x2: (hi, lo) quartet form for conv3_halo (conv3_halo_packing)
     float wscale = 1.f;       // f16x2: what the epilogue multiplies the accumulator by (the stored weights are w / wscale)
 };
 // w: [Cout][Cin_g][KH][KW] fp32 (conv) -- amode AM_CONV1/AM_CONV3/AM_DCN/AM_ROWS
-PackedConv pack_conv(const float* w, const float* bias, int cout, int cin_g, int kh, int kw, int groups, int amode, int dtype);
+// `halo`: the caller runs this AM_CONV3 layer at stride 1 / pad 1 without a residual (conv3_halo_packing)
+PackedConv pack_conv(const float* w, const float* bias, int cout, int cin_g, int kh, int kw, int groups, int amode, int dtype, bool halo = false);
 // `groups` ConvTranspose2d(k=2,s=2) weights [Cin][Cout][2][2] -> grouped GEMM [group][n=(a*2+b)*Cout+co][k=ci]
 PackedConv pack_deconv2(const float* const* w, const float* const* bias, int groups, int cin, int cout, int dtype);
 

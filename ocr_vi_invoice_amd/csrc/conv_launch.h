@@ -221,6 +221,8 @@ int launch_conv(const ConvParams& p_in, int amode, hipStream_t stream) {
     if constexpr (IsSplit<T>::value) {
         if (conv3_halo_eligible(p, amode, TypeInfo<T>::dtype)) return launch_conv3_halo<T>(p, stream);
     }
+    OCRVI_CHECK(!p.w_quartets, OCRVI_EINVAL,
+                "conv3x3: weights are packed for the halo kernel but this call is not eligible for it (stride / epilogue / alignment)");
     if (gemm_ring_eligible(p, amode, TypeInfo<T>::dtype)) return launch_gemm_ring<T>(p, amode, stream);
     switch (amode) {
         case AM_CONV1: return launch_mode<T, AM_CONV1>(p, stream);

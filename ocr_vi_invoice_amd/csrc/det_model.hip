@@ -78,9 +78,10 @@ extern "C" int ocrvi_det_create(int device, const void* blob_p, size_t blob_byte
             bk.dcn = use_dcn && li >= 1;               // backbone.py:28-31: DCN in layer2..4
             bk.stride = (b == 0 && li >= 1) ? 2 : 1;   // torchvision Bottleneck v1.5: stride on the 3x3 (BasicBlock: on conv1)
             bk.has_down = b == 0 && (!basic || li >= 1);   // (ResNet-18's layer1 keeps 64 channels at stride 1: no downsample)
-            if (basic) OCRVI_TRY(load_conv(st, blob, p + ".conv1", w, inpl, 3, 1, AM_CONV3, dt, true, &bk.conv1));
+            // (the dense 3x3 layers that run at stride 1 without a residual ask for conv3_halo's weight form)
+            if (basic) OCRVI_TRY(load_conv(st, blob, p + ".conv1", w, inpl, 3, 1, AM_CONV3, dt, true, &bk.conv1, nullptr, bk.stride == 1));
             else OCRVI_TRY(load_conv(st, blob, p + ".conv1", w, inpl, 1, 1, AM_CONV1, dt, true, &bk.conv1));
-            OCRVI_TRY(load_conv(st, blob, p + ".conv2", w, w, 3, 1, bk.dcn ? AM_DCN : AM_CONV3, dt, true, &bk.conv2));
+            OCRVI_TRY(load_conv(st, blob, p + ".conv2", w, w, 3, 1, bk.dcn ? AM_DCN : AM_CONV3, dt, true, &bk.conv2, nullptr, !basic && !bk.dcn && bk.stride == 1));
             if (bk.dcn) OCRVI_TRY(load_conv(st, blob, p + ".conv2.off", 27, w, 3, 1, AM_CONV3, dt, true, &bk.off));
             if (!basic) OCRVI_TRY(load_conv(st, blob, p + ".conv3", 4 * w, w, 1, 1, AM_CONV1, dt, true, &bk.conv3));
             if (bk.has_down) OCRVI_TRY(load_conv(st, blob, p + ".down", ex * w, inpl, 1, 1, AM_CONV1, dt, true, &bk.down));
@@ -89,7 +90,7 @@ extern "C" int ocrvi_det_create(int device, const void* blob_p, size_t blob_byte
     }
     for (int i = 0; i < 4; ++i) {
         OCRVI_TRY(load_conv(st, blob, "neck.lat" + std::to_string(i), 256, ex * kWidth[i], 1, 1, AM_CONV1, dt, true, &h->lat[i]));
-        OCRVI_TRY(load_conv(st, blob, "neck.fpn" + std::to_string(i), 256, 256, 3, 1, AM_CONV3, dt, true, &h->fpn[i]));
+        OCRVI_TRY(load_conv(st, blob, "neck.fpn" + std::to_string(i), 256, 256, 3, 1, AM_CONV3, dt, true, &h->fpn[i], nullptr, true));
     }
     {
         const BlobTensor *w = nullptr, *b = nullptr;
@@ -98,7 +99,7 @@ extern "C" int ocrvi_det_create(int device, const void* blob_p, size_t blob_byte
         OCRVI_TRY(st.upload(w->data, 4096 * 4, (void**)&h->asf_w));
         OCRVI_TRY(st.upload(b->data, 16, (void**)&h->asf_b));
     }
-    OCRVI_TRY(load_conv(st, blob, "head.conv", 128, 256, 3, 1, AM_CONV3, dt, true, &h->head_conv));
+    OCRVI_TRY(load_conv(st, blob, "head.conv", 128, 256, 3, 1, AM_CONV3, dt, true, &h->head_conv, nullptr, true));
     {   // two ConvTranspose2d(64,64,2,2)+BN+ReLU as ONE grouped pixel-shuffle GEMM (group 0 = binarise, 1 = threshold branch)
         std::vector<float> w2(2 * 64 * 4), b2(2);
         const char* names[2] = {"head.bin", "head.thr"};

@@ -128,7 +128,7 @@ static PackedConv finish_pack(const std::vector<float>& wt, int groups, int Np, 
     convert_to_dtype(wt.data(), wt.size(), dtype, pc.bytes.data(), scale);
     if (quartets && dtype == OCRVI_F16X2) {
         // (hi, lo) quartet form for kernels that read a lane's 8 k-slots as two 16-byte operands without regrouping them in registers
-        // (dcn_pipe.h): every 32-byte group of 8 consecutive k-slots [hi4 lo4 | hi4' lo4'] becomes [hi4 hi4' | lo4 lo4']
+        // (dcn_pipe.h, conv3_halo.h): every 32-byte group of 8 consecutive k-slots [hi4 lo4 | hi4' lo4'] becomes [hi4 hi4' | lo4 lo4']
         uint64_t* q = (uint64_t*)pc.bytes.data();
         for (size_t i = 0; i + 3 < pc.bytes.size() / 8; i += 4) std::swap(q[i + 1], q[i + 2]);
     }
@@ -138,7 +138,7 @@ static PackedConv finish_pack(const std::vector<float>& wt, int groups, int Np, 
     return pc;
 }
 
-PackedConv pack_conv(const float* w, const float* bias, int cout, int cin_g, int kh, int kw, int groups, int amode, int dtype) {
+PackedConv pack_conv(const float* w, const float* bias, int cout, int cin_g, int kh, int kw, int groups, int amode, int dtype, bool halo) {
     const int bke = conv_bke(dtype);
     const int n_g = cout / groups;
     const int bn = conv_bn_for(n_g);
@@ -163,7 +163,9 @@ PackedConv pack_conv(const float* w, const float* bias, int cout, int cin_g, int
                         else dst[(r * kw + s) * cin_g + c] = v;                      // [tap][cin]
                     }
         }
-    PackedConv pc = finish_pack(wt, groups, Np, Kp, dtype, amode == AM_DCN && dcn_pipe_packing(dtype, cin_g));
+    const bool halo_q = amode == AM_CONV3 && kw == 3 && Kp == 9 * cin_g && conv3_halo_packing(halo, dtype, cin_g, n_g, kh, groups, Np);
+    PackedConv pc = finish_pack(wt, groups, Np, Kp, dtype, halo_q || (amode == AM_DCN && dcn_pipe_packing(dtype, cin_g)));
+    pc.quartets = halo_q;
     pc.N_g = n_g;
     pc.Cin_g = cin_g;
     pc.KH = kh;
@@ -266,10 +268,9 @@ bool gemm_ring_eligible(const ConvParams& p, int amode, int dtype) {
 }
 
 // The direct halo-tile 3x3 convolution (conv3_halo.h): f16x2, dense, stride 1, pad 1, whole 32-channel blocks, 64 / 128 / 256 columns, plain NHWC
-// output with bias + ReLU / none.  Independent of M and n_img (a page alone and inside a batch take the same kernel and the same K order).
+// output with bias + ReLU / none, weights packed as (hi, lo) quartets (the loader asked pack_conv for them; OCRVI_CONV3_HALO=0 is read there).  Independent of M and n_img (a page alone and inside a batch take the same kernel and the same K order).
 bool conv3_halo_eligible(const ConvParams& p, int amode, int dtype) {
-    static const bool on = !(getenv("OCRVI_CONV3_HALO") && atoi(getenv("OCRVI_CONV3_HALO")) == 0);   // A/B switch (0: conv_gemm)
-    if (!on || dtype != OCRVI_F16X2 || amode != AM_CONV3 || p.groups != 1 || p.store_mode != ST_NHWC || p.res_mode != RES_NONE || p.out_f32) return false;
+    if (!p.w_quartets || dtype != OCRVI_F16X2 || amode != AM_CONV3 || p.groups != 1 || p.store_mode != ST_NHWC || p.res_mode != RES_NONE || p.out_f32) return false;
     if (p.KH != 3 || p.SH != 1 || p.SW != 1 || p.PH != 1 || p.PW != 1 || p.H != p.OH || p.W != p.OW) return false;
     if (p.Cin_g % 32 != 0 || p.Kp != 9 * p.Cin_g || !(p.Np == 64 || p.Np == 128 || p.Np == 256) || p.N_g > p.Np) return false;
     if (p.act != ACT_NONE && p.act != ACT_RELU) return false;

@@ -28,12 +28,14 @@ struct ConvLayer {
     int Np = 0, Kp = 0, N_g = 0, Cin_g = 0, groups = 1, KH = 1, amode = AM_CONV1;
     int shuffle_co = 0;
     float wscale = 1.f;   // f16x2 weight scale (PackedConv::wscale)
+    bool quartets = false;   // PackedConv::quartets
 };
 
 int upload_packed(DeviceStore& st, const PackedConv& pc, int amode, ConvLayer* L);
-// conv weight `name`.w [cout][cin_g][k][k] (+ `name`.b [cout] if has_bias) from the blob
+// conv weight `name`.w [cout][cin_g][k][k] (+ `name`.b [cout] if has_bias) from the blob; `halo`: a 3x3 layer that only ever runs at
+// stride 1 / pad 1 with a bias + ReLU / none epilogue (pack_conv)
 int load_conv(DeviceStore& st, const Blob& blob, const std::string& name, int cout, int cin_g, int k, int groups, int amode, int dtype,
-              bool has_bias, ConvLayer* L, const float* extra_bias = nullptr);
+              bool has_bias, ConvLayer* L, const float* extra_bias = nullptr, bool halo = false);
 int load_vec(DeviceStore& st, const Blob& blob, const std::string& name, int n, float** out);
 
 struct Tensor {  // NHWC view

@@ -9,11 +9,12 @@ int upload_packed(DeviceStore& st, const PackedConv& pc, int amode, ConvLayer* L
     L->Np = pc.Np; L->Kp = pc.Kp; L->N_g = pc.N_g; L->Cin_g = pc.Cin_g; L->groups = pc.groups; L->KH = pc.KH;
     L->amode = amode;
     L->wscale = pc.wscale;
+    L->quartets = pc.quartets;
     return OCRVI_OK;
 }
 
 int load_conv(DeviceStore& st, const Blob& blob, const std::string& name, int cout, int cin_g, int k, int groups, int amode, int dtype,
-              bool has_bias, ConvLayer* L, const float* extra_bias) {
+              bool has_bias, ConvLayer* L, const float* extra_bias, bool halo) {
     const BlobTensor *w = nullptr, *b = nullptr;
     OCRVI_TRY(blob.get(name + ".w", cout, cin_g, k, k, &w));
     if (has_bias) OCRVI_TRY(blob.get(name + ".b", cout, 0, 0, 0, &b));
@@ -24,7 +25,7 @@ int load_conv(DeviceStore& st, const Blob& blob, const std::string& name, int co
         for (int i = 0; i < cout; ++i) bias[i] += extra_bias[i];
     }
     const int kk = k == 0 ? 1 : k;  // k == 0: a 2-D nn.Linear weight (out, in)
-    PackedConv pc = pack_conv(w->data, bias.empty() ? nullptr : bias.data(), cout, cin_g, kk, kk, groups, amode, dtype);
+    PackedConv pc = pack_conv(w->data, bias.empty() ? nullptr : bias.data(), cout, cin_g, kk, kk, groups, amode, dtype, halo);
     return upload_packed(st, pc, amode, L);
 }
 
@@ -43,6 +44,7 @@ int conv(Runner& r, const ConvLayer& L, const Tensor& x, const Tensor& y, const 
     p.N_g = L.N_g; p.Np = L.Np; p.Kp = L.Kp; p.groups = L.groups;
     p.store_mode = o.store_mode;
     p.wscale = L.wscale;
+    p.w_quartets = L.quartets ? 1 : 0;
     if (o.store_mode == ST_SHUFFLE2) {
         p.OH = y.h / 2; p.OW = y.w / 2; p.shuffle_co = L.shuffle_co;
     } else if (o.store_mode == ST_DB_TAIL) {  // y is the fp32 logit map [n, 4*OH, 4*OW, 1]

@@ -159,6 +159,33 @@ def check_scratch(src):
     return rep
 
 
+def check_halo(src="conv_f16x2.hip"):
+    """The direct 3x3 convolution (conv3_halo.h) reads a unit's fragments one stage ahead of the MFMAs that use them.  name -> dict for every
+    `conv3_halo_kernel` build in the translation unit:
+      scratch          scratch (spill) instructions in the whole kernel: an uncounted VMEM operation in the hand-counted vmcnt protocol;
+      exposed_waits    `s_waitcnt lgkmcnt(0)` whose preceding instruction is a `ds_read`, between the first and the last `s_barrier` of the
+                       unit loop (the barriers of the nine unrolled steps): an LDS round trip with nothing to hide it;
+      barriers, mfma, ds_read, v_mov, s_nop, waits   instruction counts of that same span;  vgprs  the kernel's register count.
+    (What it cannot see: a wait placed one instruction behind its read is as exposed as one directly behind it.)"""
+    txt = asm_of(src)
+    rep = {}
+    for name, body in kernel_bodies(txt, "_ZN5ocrvi17conv3_halo_kernel").items():
+        ins = [(t, a) for t, a in body if not t.endswith(":")]
+        # the counted wait + barrier of every unit is one inline-asm statement (the bias prologue's __syncthreads is the compiler's own); the
+        # first of them belongs to the pipeline's prologue, the others to the nine unrolled units
+        bars = [i for i, (t, a) in enumerate(ins) if a and t.startswith("s_barrier")]
+        ins = [t for t, _ in ins]
+        loop = ins[bars[1]:bars[-1] + 1] if len(bars) > 9 else []
+        exposed = sum(1 for a, b in zip(loop, loop[1:]) if a.startswith("ds_read") and re.match(r"s_waitcnt lgkmcnt\(0\)\s*$", b))
+        v = re.search(r"\.name:\s+" + re.escape(name) + r"\n(?:(?!\.name:).*\n)*?\s*\.vgpr_count:\s*(\d+)", txt)
+        rep[name] = dict(scratch=sum("scratch_" in t for t in ins), exposed_waits=exposed, barriers=len(bars),
+                         mfma=sum(t.startswith("v_mfma") for t in loop), ds_read=sum(t.startswith("ds_read") for t in loop),
+                         v_mov=sum(t.startswith("v_mov_b32") for t in loop), s_nop=sum(t.startswith("s_nop") for t in loop),
+                         waits=sum(t.startswith("s_waitcnt") for t in loop), v_add=sum(t.startswith("v_add_u32") for t in loop),
+                         vgprs=int(v.group(1)) if v else -1)
+    return rep
+
+
 if __name__ == "__main__":
     ok = True
     for src in sys.argv[1:] or ["conv_bf16.hip"]:
