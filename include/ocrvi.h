@@ -224,6 +224,57 @@ int ocrvi_warp_perspective_pages(int device, const int64_t* src_pages, const int
                                  void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Oriented text crops (opt-in; the default stays the reference's rectangle crop, crop_image, src/det/test.py:123-130): the minimum-area
+ * rectangle of each DB polygon, warped and resized into the recogniser's batch in one launch.  The reference carries only the left-overs
+ * of this path (DBPostProcessor.min_size, is_output_polygon, src/det/test.py:52,55).  The definitions below are the library's own and
+ * exact; parity with cv2.minAreaRect / PaddleOCR unpinned (cv2 absent).  tests/quad_ref.py restates them in Python integers.
+ * ------------------------------------------------------------------------------------------------ */
+/* Host only, needs no GPU.  points int32 [total][2]; offs int32 [n+1]: polygon i = points[offs[i] .. offs[i+1]); quads float64 [n][4][2];
+ * flags int32 [n].  Coordinates lie in [-32768, 32767], anything else is OCRVI_EINVAL.
+ *   hull       the distinct points sorted by (x, y); the strictly convex hull by the monotone chain, lower chain then upper chain: a point is
+ *              kept only while every integer cross product is > 0, so collinear points are dropped; hull[0] is the smallest (x, y).
+ *              Fewer than three hull vertices: flags[i] = 1 (degenerate) and the quad is the four corners (x0,y0) (x1,y0) (x1,y1) (x0,y1) of
+ *              the polygon's inclusive bounding box (all zero for a polygon without points).  Otherwise flags[i] = 0.
+ *   rectangle  for hull edge k = hull[k] -> hull[k+1]: d = (dx, dy), n = (-dy, dx); s_min, s_max = the extremes of p.d and t_min, t_max of
+ *              p.n over the hull vertices (int64); area = (s_max - s_min)(t_max - t_min) / |d|^2, compared as exact rationals (128-bit cross
+ *              multiplication).  The smallest area wins, the smallest k on a tie.
+ *   corners    in the order (s_min, t_min), (s_max, t_min), (s_max, t_max), (s_min, t_max): x = (s dx - t dy) / |d|^2, y = (s dy + t dx) /
+ *              |d|^2; each numerator is an exact integer below 2^53, converted to double and divided once. */
+int ocrvi_min_area_quads(const int32_t* points, const int32_t* offs, int n, double* quads /*[n][4][2]*/, int32_t* flags /*[n]*/);
+/* Host only.  The crop descriptors of n quads: crops int32 [n][4] = (page_ids[i], w, h, 0), m_inv float64 [n][9] destination -> source;
+ * page_ids int32 [n] (the page table index of each quad's page), page_hw int32 [n][2] = that page's (height, width).
+ * Quad i goes through the geometry of ocrvi_four_point_transform (corner order, float32 side lengths truncated to w and h, the 8 x 8
+ * solve); w, h and its m_inv are stored.  When that geometry refuses the quad (w < 1 or h < 1, a singular system, the ordering picking one
+ * corner twice -- a rectangle tilted by exactly 45 degrees --) or flags[i] != 0, the descriptor falls back to the reference's crop: with
+ * x0 = floor(min x), y0 = floor(min y), bw = ceil(max x) - x0 + 1, bh = ceil(max y) - y0 + 1 over the four corners (for a flagged quad:
+ * cv2.boundingRect of the polygon), x = max(0, x0), y = max(0, y0), w = min(bw, page_w - x), h = min(bh, page_h - y) (src/det/test.py:
+ * 126-129) and m_inv = [1,0,x, 0,1,y, 0,0,1]; a rectangle that is empty after clamping gets w = h = 0.  Under the warp below an integer
+ * translation reads the page's pixels unchanged, so a fallback crop is that rectangle of the page bit for bit.  For a flagged polygon the
+ * rectangle is the reference's (crop_rect of the polygon).  For a refused quad it is the bounding box of the quad's corners, which contains
+ * the polygon's bounding rectangle and can be larger than it (the entry sees the quad, not the polygon): no parity with the rectangle
+ * mode is claimed there.  A refused quad leaves ocrvi_last_error empty.  Corners must be finite and within +-2^20 (OCRVI_EINVAL).  No 90-degree turn: a quad that comes out taller than wide stays so. */
+int ocrvi_quad_crops(const double* quads, const int32_t* flags, int n, const int32_t* page_ids, const int32_t* page_hw /*[n][2]*/,
+                     int32_t* crops /*[n][4]*/, double* m_inv /*[n][9]*/);
+/* The oriented analogue of ocrvi_crop_resize_normalize_pages.  pages: a page table (OCRVI_PAGE_ENTRY); crops int32 [B][4] and m_inv float64
+ * [B][9] as above, both in DEVICE memory; out float32 [B,3,out_h,out_w].  Enqueue-only on `stream`: no allocation, no synchronisation;
+ * tables, descriptors and pages are read when the kernel runs, so a captured graph survives rewritten descriptors.
+ * Output b is the composition of two definitions above.  First the intermediate crop C_b, uint8 [h, w, 3]: the warp of
+ * ocrvi_warp_perspective_u8 under m_inv[b] -- the same 1/32-pixel coordinates, IEEE double arithmetic in the stated order without fused
+ * multiply-add, 15-bit weights and (sum + 16384) >> 15 -- with one difference: a tap's row and column are clamped to the page (replicate
+ * border) instead of contributing 0, so a crop that overhangs the page edge gains no black rim.  Then the rest of
+ * ocrvi_crop_resize_normalize applied to the whole of C_b: new_w = int(w * (out_h / h)) squashed to out_w and at least 1, the exact-2x box
+ * filter, the fixed-point bilinear resize, right padding with 255, the float32 normalisation.  C_b is never written to memory.  When out_w
+ * is a multiple of 4, out is 16-byte aligned, B <= 65535 and out_h <= 62, a workgroup per out_h x 64 tile warps the pixels of C_b the tile
+ * reads once into LDS and resizes from there (16-byte stores); otherwise a thread per output pixel forms the at most 2 x 2 pixels of C_b it
+ * reads.  Both forms write the same bits.  w <= 0, h <= 0, an index outside [0, n_pages) or an invalid table entry yields the all-zero
+ * tensor. */
+int ocrvi_crop_quad_resize_normalize_pages(int device, const int64_t* pages, int n_pages, const int32_t* crops, const double* m_inv, int B,
+                                           int out_h, int out_w, float* out, void* stream);
+/* The same for crops of one uint8 [n_img,H,W,3] array (the analogue of ocrvi_crop_resize_normalize): crops[b][0] is the image index. */
+int ocrvi_crop_quad_resize_normalize(int device, const uint8_t* images, int n_img, int H, int W, const int32_t* crops, const double* m_inv,
+                                     int B, int out_h, int out_w, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * enhance_document, the reference's "Magic Color" (src/preprocess/scanner.py:55-76): COLOR_BGR2LAB (:60), CLAHE(clipLimit 2.0, 8 x 8 tiles)
  * on L (:63-64), COLOR_LAB2BGR (:67), fastNlMeansDenoisingColored(h 10, hColor 10, template 7, search 21) (:70), filter2D with the 3 x 3
  * sharpen kernel (:73-74).  The reference's constants are fixed: none is a parameter.

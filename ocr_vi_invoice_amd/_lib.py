@@ -34,6 +34,7 @@ EXPORTS = [
     "ocrvi_test_deform_conv_res",
     "ocrvi_enhance_init", "ocrvi_enhance_tables", "ocrvi_enhance_workspace_bytes", "ocrvi_enhance_u8",
     "ocrvi_rgb_to_lab_u8", "ocrvi_lab_to_rgb_u8", "ocrvi_clahe_lab_u8", "ocrvi_nlm_lab_u8", "ocrvi_sharpen_u8",
+    "ocrvi_min_area_quads", "ocrvi_quad_crops", "ocrvi_crop_quad_resize_normalize_pages", "ocrvi_crop_quad_resize_normalize",
 ]
 PAGE_ENTRY = 4          # int64 fields of one page-table entry: (device address, height, width, 0) -- OCRVI_PAGE_ENTRY
 # ocrvi_det_eval's record: 13 slots of 8 bytes (OCRVI_DET_EVAL_*), the first six int64, the rest float64
@@ -139,6 +140,10 @@ def load() -> C.CDLL:
     for name in ("ocrvi_rgb_to_lab_u8", "ocrvi_lab_to_rgb_u8", "ocrvi_nlm_lab_u8", "ocrvi_sharpen_u8"):
         getattr(lib, name).argtypes = [i32, vp, i32, i32, vp, vp]
     lib.ocrvi_clahe_lab_u8.argtypes = [i32, vp, i32, i32, vp, vp, sz, vp]
+    lib.ocrvi_min_area_quads.argtypes = [vp, vp, i32, vp, vp]
+    lib.ocrvi_quad_crops.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    lib.ocrvi_crop_quad_resize_normalize_pages.argtypes = [i32, vp, i32, i32p, vp, i32, i32, i32, f32p, vp]
+    lib.ocrvi_crop_quad_resize_normalize.argtypes = [i32, vp, i32, i32, i32, i32p, vp, i32, i32, i32, f32p, vp]
     lib.ocrvi_det_status.argtypes = [vp]
     lib.ocrvi_rec_status.argtypes = [vp]
     lib.ocrvi_range_reset.argtypes = [i32, vp]

@@ -347,6 +347,228 @@ __global__ void warp_perspective_pages_kernel(const int64_t* __restrict__ src_ta
     warp_page(s.p, s.h, s.w, M, (uint8_t*)d.p, d.h, d.w, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x);
 }
 
+// ---------------------------------------------------------------- oriented text crops (include/ocrvi.h, "Oriented text crops")
+// Pixel (x, y) of the intermediate crop C_b: warp_px under the crop's matrix with a replicate border -- a tap's row and column are clamped
+// to the page instead of contributing 0, so a crop that overhangs the page edge gains no black rim.  Same coordinates, weights and rounding.
+__device__ __forceinline__ void warp_px_replicate(const uint8_t* __restrict__ src, int sh, int sw, const double* __restrict__ m, int x, int y, int v[3]) {
+#pragma clang fp contract(off)
+    const double dx = (double)x, dy = (double)y;
+    const double X0 = (m[0] * dx + m[1] * dy) + m[2];
+    const double Y0 = (m[3] * dx + m[4] * dy) + m[5];
+    const double W0 = (m[6] * dx + m[7] * dy) + m[8];
+    const double s = (W0 != 0.0) ? 32.0 / W0 : 0.0;
+    const int X = warp_coord(X0, s), Y = warp_coord(Y0, s);
+    const int sx = X >> 5, sy = Y >> 5, ax = X & 31, ay = Y & 31;
+    // clamped on the integers before any address is formed (sx is up to +-2^26: sx + 1 cannot overflow)
+    const int x0 = min(max(sx, 0), sw - 1), x1 = min(max(sx + 1, 0), sw - 1);
+    const int y0 = min(max(sy, 0), sh - 1), y1 = min(max(sy + 1, 0), sh - 1);
+    const int w00 = (32 - ax) * (32 - ay) * 32, w01 = ax * (32 - ay) * 32, w10 = (32 - ax) * ay * 32, w11 = ax * ay * 32;
+    const uint8_t *r0 = src + (size_t)y0 * sw * 3, *r1 = src + (size_t)y1 * sw * 3;
+    const uint8_t *p00 = r0 + (size_t)x0 * 3, *p01 = r0 + (size_t)x1 * 3, *p10 = r1 + (size_t)x0 * 3, *p11 = r1 + (size_t)x1 * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = (16384 + w00 * p00[c] + w01 * p01[c] + w10 * p10[c] + w11 * p11[c]) >> 15;
+}
+
+// where a crop's page comes from: a page table read when the kernel runs, or one [n,H,W,3] array
+struct TablePages {
+    const int64_t* table; int n;
+    __device__ __forceinline__ PageRef get(int i) const { return (i >= 0 && i < n) ? load_page(table, i) : PageRef{nullptr, 0, 0}; }
+};
+struct ArrayPages {
+    const uint8_t* images; int n, H, W;
+    __device__ __forceinline__ PageRef get(int i) const {
+        return (i >= 0 && i < n) ? PageRef{images + (size_t)i * H * W * 3, H, W} : PageRef{nullptr, 0, 0};
+    }
+};
+
+// The direct form: one thread per output pixel forms the (at most) 2 x 2 pixels of C_b its resize reads, each from 2 x 2 page pixels; C_b
+// is never stored.  A resize tap of weight 0 (identity rows or columns, the clamped last row / column) is not formed: it contributes 0
+// whatever its value.  crops int32 [B,4] = (page, w, h, 0), m_inv float64 [B,9]; the rest is crop_resize_normalize_kernel on all of C_b.
+template <class Pages>
+__global__ void crop_quad_resize_normalize_kernel(Pages pages, const int32_t* __restrict__ crops, const double* __restrict__ m_inv, int B, int oh,
+                                                  int ow, float* __restrict__ out) {
+    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
+    const size_t total = (size_t)B * oh * ow;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int x = (int)(i % ow);
+        const size_t t = i / ow;
+        const int y = (int)(t % oh), b = (int)(t / oh);
+        const int32_t* cr = crops + (size_t)b * 4;
+        const int cw = cr[1], ch = cr[2];
+        float* o = out + ((size_t)b * 3 * oh + y) * ow + x;
+        const size_t plane = (size_t)oh * ow;
+        const PageRef pr = pages.get(cr[0]);
+        if (cw <= 0 || ch <= 0 || pr.h == 0) {  // empty crop, index out of range or invalid entry -> zeros tensor (pipeline2.py:154-156)
+            o[0] = o[plane] = o[2 * plane] = 0.f;
+            continue;
+        }
+        int new_w = (int)((double)cw * ((double)oh / (double)ch));
+        if (new_w > ow) new_w = ow;   // squash (pipeline2.py:104-105)
+        if (new_w < 1) new_w = 1;
+        int v[3] = {255, 255, 255};
+        if (x < new_w) {
+            const double* m = m_inv + (size_t)b * 9;
+            int p00[3], p01[3], p10[3], p11[3];
+            if (cw == 2 * new_w && ch == 2 * oh) {  // exact 2x decimation: the 2x2 area filter
+                warp_px_replicate(pr.p, pr.h, pr.w, m, 2 * x, 2 * y, p00);
+                warp_px_replicate(pr.p, pr.h, pr.w, m, 2 * x + 1, 2 * y, p01);
+                warp_px_replicate(pr.p, pr.h, pr.w, m, 2 * x, 2 * y + 1, p10);
+                warp_px_replicate(pr.p, pr.h, pr.w, m, 2 * x + 1, 2 * y + 1, p11);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) v[c] = (p00[c] + p01[c] + p10[c] + p11[c] + 2) >> 2;
+            } else {
+                const AxisCoef ax = axis_coef(x, cw, new_w), ay = axis_coef(y, ch, oh);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) p01[c] = p10[c] = p11[c] = 0;
+                warp_px_replicate(pr.p, pr.h, pr.w, m, ax.s0, ay.s0, p00);
+                if (ax.a1 != 0) warp_px_replicate(pr.p, pr.h, pr.w, m, ax.s1, ay.s0, p01);
+                if (ay.a1 != 0) {
+                    warp_px_replicate(pr.p, pr.h, pr.w, m, ax.s0, ay.s1, p10);
+                    if (ax.a1 != 0) warp_px_replicate(pr.p, pr.h, pr.w, m, ax.s1, ay.s1, p11);
+                }
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const int h0 = p00[c] * ax.a0 + p01[c] * ax.a1;
+                    const int h1 = p10[c] * ax.a0 + p11[c] * ax.a1;
+                    v[c] = (((ay.a0 * (h0 >> 4)) >> 16) + ((ay.a1 * (h1 >> 4)) >> 16) + 2) >> 2;
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[c * plane] = ((float)v[c] / 255.0f - mean[c]) / stdv[c];
+    }
+}
+
+// The tile form: a workgroup owns an oh x QT_TW tile of one crop's output.  It warps every pixel of C_b the tile's resize reads once into
+// LDS -- the double-precision division included --, then resizes from LDS and writes 16-byte stores per plane.  Enlarged crops (text lines
+// under oh pixels high: the common case) share those pixels between neighbouring output pixels, which the direct form forms again per
+// thread.  Per axis the LDS slots are either dense (slot = source index - first index, when the tile's source range fits the 2 oh rows /
+// 2 QT_TW columns) or compact (slot = 2 * output index + tap, for a crop that is shrunk).  Pixels are packed r | g << 8 | b << 16; rows are
+// QT_CS = 2 QT_TW + 1 words apart so that consecutive rows start on consecutive banks.
+constexpr int QT_TW = 64;
+constexpr int QT_CS = 2 * QT_TW + 1;
+static inline size_t quad_tile_lds_bytes(int oh) { return ((size_t)2 * oh * QT_CS + 2 * oh + 2 * QT_TW) * 4; }
+
+template <class Pages>
+__global__ __launch_bounds__(256) void crop_quad_tile_kernel(Pages pages, const int32_t* __restrict__ crops, const double* __restrict__ m_inv, int oh,
+                                                             int ow, float* __restrict__ out) {
+    extern __shared__ uint32_t qt_lds[];
+    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
+    uint32_t* pix = qt_lds;                               // [2 oh][QT_CS]
+    int* rowsrc = (int*)(qt_lds + (size_t)2 * oh * QT_CS);   // [2 oh]    row of C_b held by each row slot
+    int* colsrc = rowsrc + 2 * oh;                        // [2 QT_TW] column of C_b held by each column slot
+    const int tid = threadIdx.x, b = blockIdx.y, x0 = blockIdx.x * QT_TW;
+    const int tw = min(QT_TW, ow - x0), tw4 = tw >> 2;    // ow % 4 == 0
+    const int32_t* cr = crops + (size_t)b * 4;
+    const int cw = cr[1], ch = cr[2];
+    const size_t plane = (size_t)oh * ow;
+    float* ob = out + (size_t)b * 3 * plane + x0;
+    const PageRef pr = pages.get(cr[0]);
+    const bool zero = cw <= 0 || ch <= 0 || pr.h == 0;    // empty crop, index out of range or invalid entry -> zeros tensor
+    int new_w = 1;
+    if (!zero) {
+        new_w = (int)((double)cw * ((double)oh / (double)ch));
+        if (new_w > ow) new_w = ow;   // squash (pipeline2.py:104-105)
+        if (new_w < 1) new_w = 1;
+    }
+    const int nx = min(tw, new_w - x0);                   // the tile's columns left of the padding
+    if (zero || nx <= 0) {                                // one value per plane: zeros, or the normalised 255 of the padding
+        for (int q = tid; q < oh * tw4; q += 256) {
+            const int y = q / tw4, xq = (q - y * tw4) * 4;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float f = zero ? 0.f : (255.0f / 255.0f - mean[c]) / stdv[c];
+                *(float4*)(ob + (size_t)c * plane + (size_t)y * ow + xq) = make_float4(f, f, f, f);
+            }
+        }
+        return;
+    }
+    const bool box = (cw == 2 * new_w && ch == 2 * oh);   // exact 2x decimation: the 2x2 area filter reads rows 2y, 2y+1, columns 2x, 2x+1
+    bool rdense, cdense;
+    int nrs, ncs, cmin;
+    if (box) {
+        rdense = cdense = true;
+        nrs = ch; cmin = 2 * x0; ncs = 2 * nx;
+    } else {
+        rdense = ch <= 2 * oh;
+        nrs = rdense ? ch : 2 * oh;
+        const int c_lo = axis_coef(x0, cw, new_w).s0, c_hi = axis_coef(x0 + nx - 1, cw, new_w).s1;   // s0 and s1 never decrease with x
+        cdense = c_hi - c_lo + 1 <= 2 * QT_TW;
+        cmin = cdense ? c_lo : 0;
+        ncs = cdense ? c_hi - c_lo + 1 : 2 * nx;
+    }
+    for (int i = tid; i < nrs; i += 256) {
+        int r = i;
+        if (!rdense) { const AxisCoef a = axis_coef(i >> 1, ch, oh); r = (i & 1) ? a.s1 : a.s0; }
+        rowsrc[i] = r;
+    }
+    for (int j = tid; j < ncs; j += 256) {
+        int c = cmin + j;
+        if (!cdense) { const AxisCoef a = axis_coef(x0 + (j >> 1), cw, new_w); c = (j & 1) ? a.s1 : a.s0; }
+        colsrc[j] = c;
+    }
+    __syncthreads();
+    double m[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) m[k] = m_inv[(size_t)b * 9 + k];
+    for (int s = tid; s < nrs * ncs; s += 256) {
+        const int i = s / ncs, j = s - i * ncs;
+        int v[3];
+        warp_px_replicate(pr.p, pr.h, pr.w, m, colsrc[j], rowsrc[i], v);
+        pix[i * QT_CS + j] = (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16);
+    }
+    __syncthreads();
+    for (int q = tid; q < oh * tw4; q += 256) {
+        const int y = q / tw4, xq = (q - y * tw4) * 4;
+        const AxisCoef ay = axis_coef(y, ch, oh);
+        const int i0 = box ? 2 * y : (rdense ? ay.s0 : 2 * y), i1 = box ? 2 * y + 1 : (rdense ? ay.s1 : 2 * y + 1);
+        const uint32_t *r0 = pix + i0 * QT_CS, *r1 = pix + i1 * QT_CS;
+        float f[3][4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int xl = xq + k, x = x0 + xl;
+            int v[3] = {255, 255, 255};
+            if (x < new_w) {
+                if (box) {
+                    const uint32_t a = r0[2 * xl], bb = r0[2 * xl + 1], c2 = r1[2 * xl], d = r1[2 * xl + 1];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c)
+                        v[c] = (int)(((a >> (8 * c)) & 255) + ((bb >> (8 * c)) & 255) + ((c2 >> (8 * c)) & 255) + ((d >> (8 * c)) & 255) + 2) >> 2;
+                } else {
+                    const AxisCoef ax = axis_coef(x, cw, new_w);
+                    const int j0 = cdense ? ax.s0 - cmin : 2 * xl, j1 = cdense ? ax.s1 - cmin : 2 * xl + 1;
+                    const uint32_t p00 = r0[j0], p01 = r0[j1], p10 = r1[j0], p11 = r1[j1];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const int h0 = (int)((p00 >> (8 * c)) & 255) * ax.a0 + (int)((p01 >> (8 * c)) & 255) * ax.a1;
+                        const int h1 = (int)((p10 >> (8 * c)) & 255) * ax.a0 + (int)((p11 >> (8 * c)) & 255) * ax.a1;
+                        v[c] = (((ay.a0 * (h0 >> 4)) >> 16) + ((ay.a1 * (h1 >> 4)) >> 16) + 2) >> 2;
+                    }
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) f[c][k] = ((float)v[c] / 255.0f - mean[c]) / stdv[c];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) *(float4*)(ob + (size_t)c * plane + (size_t)y * ow + xq) = make_float4(f[c][0], f[c][1], f[c][2], f[c][3]);
+    }
+}
+
+// the tile form needs 16-byte stores (out_w % 4 == 0, out 16-byte aligned), one grid row per crop and its LDS; anything else takes the direct form
+template <class Pages>
+static int launch_crop_quad(Pages pages, const int32_t* crops, const double* m_inv, int B, int oh, int ow, float* out, hipStream_t stream) {
+    const size_t lds = quad_tile_lds_bytes(oh);
+    if (ow % 4 == 0 && (((uintptr_t)out) & 15) == 0 && B <= 65535 && lds <= 65536) {
+        hipLaunchKernelGGL(crop_quad_tile_kernel<Pages>, dim3((ow + QT_TW - 1) / QT_TW, B), dim3(256), lds, stream, pages, crops, m_inv, oh, ow, out);
+    } else {
+        const size_t total = (size_t)B * oh * ow;
+        const int grid = (int)std::min<size_t>((total + 255) / 256, 16384);
+        hipLaunchKernelGGL(crop_quad_resize_normalize_kernel<Pages>, dim3(grid), dim3(256), 0, stream, pages, crops, m_inv, B, oh, ow, out);
+    }
+    OCRVI_HIP(hipGetLastError());
+    return OCRVI_OK;
+}
+
 }  // namespace ocrvi
 
 using namespace ocrvi;
@@ -528,4 +750,23 @@ extern "C" int ocrvi_warp_perspective_pages(int device, const int64_t* src_pages
     hipLaunchKernelGGL(warp_perspective_pages_kernel, dim3(1024, n), dim3(256), 0, (hipStream_t)stream, src_pages, dst_pages, m_inv);
     OCRVI_HIP(hipGetLastError());
     return OCRVI_OK;
+}
+
+// ---------------------------------------------------------------- oriented text crops: the two device entries (the host half is quads.hip)
+extern "C" int ocrvi_crop_quad_resize_normalize_pages(int device, const int64_t* pages, int n_pages, const int32_t* crops, const double* m_inv, int B,
+                                                      int out_h, int out_w, float* out, void* stream) {
+    OCRVI_CHECK(pages && crops && m_inv && out && n_pages > 0 && B > 0 && out_h > 0 && out_w > 0, OCRVI_EINVAL,
+                "crop_quad_resize_normalize_pages: bad argument");
+    DeviceGuard dg(device);  // the caller's current device is restored on return
+    OCRVI_HIP(dg.err);
+    return launch_crop_quad(TablePages{pages, n_pages}, crops, m_inv, B, out_h, out_w, out, (hipStream_t)stream);
+}
+
+extern "C" int ocrvi_crop_quad_resize_normalize(int device, const uint8_t* images, int n_img, int H, int W, const int32_t* crops, const double* m_inv,
+                                                int B, int out_h, int out_w, float* out, void* stream) {
+    OCRVI_CHECK(images && crops && m_inv && out && n_img > 0 && H > 0 && W > 0 && B > 0 && out_h > 0 && out_w > 0, OCRVI_EINVAL,
+                "crop_quad_resize_normalize: bad argument");
+    DeviceGuard dg(device);  // the caller's current device is restored on return
+    OCRVI_HIP(dg.err);
+    return launch_crop_quad(ArrayPages{images, n_img, H, W}, crops, m_inv, B, out_h, out_w, out, (hipStream_t)stream);
 }

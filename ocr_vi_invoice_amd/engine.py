@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .pipeline import DBPostProcessor, db_boxes_pages, enhance_init, enhance_workspace_bytes, four_point_geometry
+from .pipeline import DBPostProcessor, _check_crop, db_boxes_pages, enhance_init, enhance_workspace_bytes, four_point_geometry, quad_crops
 
 _ARENA_ALIGN = 256
 _STREAMS: Dict[int, Tuple[torch.cuda.Stream, torch.cuda.Stream]] = {}
@@ -103,11 +103,14 @@ class Engine:
     ``run(pages, quads, enhance)``: ``enhance`` is a bool for all pages or one bool per page; such a page goes through
     ``ocrvi_enhance_u8`` (``pipeline.enhance_document``, src/preprocess/scanner.py:55-76) in its arena slot, after its rectification and
     ahead of its chunk's detector launch, eagerly on the detector stream, as ``detect_and_recognize(page, ..., enhance=True)`` does.
+    ``crop="quad"``: the recogniser sees each box's minimum-area rectangle warped upright (``ocrvi_min_area_quads`` / ``ocrvi_quad_crops`` on
+    the host after the box stage, ``ocrvi_crop_quad_resize_normalize_pages`` in the recogniser graph) instead of its bounding rectangle, as
+    ``detect_and_recognize(page, ..., crop="quad")`` does; ``"rect"`` (the default) is the reference's crop.
     The captured graphs hold the models' weights as they were: after reloading a model's weights, build a new Engine."""
 
     def __init__(self, det_model, rec_model, post_processor: DBPostProcessor, det_size: int = 960, rec_size: Tuple[int, int] = (32, 256),
                  det_chunk: int = 16, rec_batch: int = 256, max_pages: int = 256, graphs: bool = True, graph_cache: int = 16,
-                 post_threads: int = 0, prob_hook=None, binary_head: bool = False):
+                 post_threads: int = 0, prob_hook=None, binary_head: bool = False, crop: str = "rect"):
         rh, rw = int(rec_size[0]), int(rec_size[1])
         if rh <= 0 or rw <= 0 or rh % 16 or rw % 4:
             raise ValueError(f"rec_size {rec_size}: the height must be a multiple of 16 and the width of 4")
@@ -122,6 +125,7 @@ class Engine:
         self.det_chunk, self.rec_batch, self.max_pages = int(det_chunk), int(rec_batch), int(max_pages)
         self.graphs, self.graph_cache, self.prob_hook = bool(graphs), int(graph_cache), prob_hook
         self.binary_head = bool(binary_head)
+        self.crop = _check_crop(crop)
         self.post_threads = int(post_threads) or _usable_cores()
         self.lib = _lib.load()
         # every bucket det_size can produce fits in L x L (the longer side rounds to 32 round(det_size / 32); ceil covers a tie)
@@ -160,6 +164,11 @@ class Engine:
         self.h_ids = [torch.empty((self.rec_batch, T), dtype=torch.int32).pin_memory() for _ in range(nslots)]
         self.h_lens = [torch.empty((self.rec_batch,), dtype=torch.int32).pin_memory() for _ in range(nslots)]
         self.ev_rec = [torch.cuda.Event() for _ in range(nslots)]
+        if self.crop == "quad":                    # oriented crops: a descriptor row (page, w, h, 0) and a matrix per crop instead of a rectangle
+            self.d_qcrops = torch.zeros((self.rec_batch, 4), dtype=torch.int32, **d)
+            self.d_qmat = torch.zeros((self.rec_batch, 9), dtype=torch.float64, **d)
+            self.h_qcrops = [torch.zeros((self.rec_batch, 4), dtype=torch.int32).pin_memory() for _ in range(nslots)]
+            self.h_qmat = [torch.zeros((self.rec_batch, 9), dtype=torch.float64).pin_memory() for _ in range(nslots)]
         # ---- pages: one device arena per wave, filled through pinned staging; the wave's page table (pinned, arena order)
         self.arena = torch.empty(0, dtype=torch.uint8, **d)
         self.h_stage = torch.empty(0, dtype=torch.uint8)
@@ -204,8 +213,13 @@ class Engine:
     def _rec_calls(self):
         st = self.s_rec.cuda_stream
         rh, rw = self.rec_size
-        _lib.check(self.lib.ocrvi_crop_resize_normalize_pages(self.devi, self.d_rec_table.data_ptr(), self.max_pages, self.d_rects.data_ptr(),
-                                                              self.rec_batch, rh, rw, self.d_crops.data_ptr(), st))
+        if self.crop == "quad":
+            _lib.check(self.lib.ocrvi_crop_quad_resize_normalize_pages(self.devi, self.d_rec_table.data_ptr(), self.max_pages,
+                                                                       self.d_qcrops.data_ptr(), self.d_qmat.data_ptr(), self.rec_batch, rh, rw,
+                                                                       self.d_crops.data_ptr(), st))
+        else:
+            _lib.check(self.lib.ocrvi_crop_resize_normalize_pages(self.devi, self.d_rec_table.data_ptr(), self.max_pages, self.d_rects.data_ptr(),
+                                                                  self.rec_batch, rh, rw, self.d_crops.data_ptr(), st))
         _lib.check(self.lib.ocrvi_rec_forward(self.rec._handle, self.d_crops.data_ptr(), self.rec_batch, rh, rw, None, self.d_am.data_ptr(),
                                               self.d_ids.data_ptr(), self.d_lens.data_ptr(), self.rec_ws.data_ptr(), self.rec_ws.numel(), st))
 
@@ -313,11 +327,22 @@ class Engine:
             self._decode_oldest()
         k = self._rec_slot
         self._rec_slot = (k + 1) % len(self.h_rects)
-        hr = self.h_rects[k].numpy()
-        hr[:len(rows)] = rows
-        hr[len(rows):] = 0                        # w = h = 0: the all-zero tensor; its string is dropped
+        if self.crop == "quad":                    # rows = (descriptor row, matrix) pairs
+            hc, hm = self.h_qcrops[k].numpy(), self.h_qmat[k].numpy()
+            hc[:len(rows)] = [r[0] for r in rows]
+            hm[:len(rows)] = [r[1] for r in rows]
+            hc[len(rows):] = 0                    # w = h = 0: the all-zero tensor; its string is dropped
+            hm[len(rows):] = 0
+        else:
+            hr = self.h_rects[k].numpy()
+            hr[:len(rows)] = rows
+            hr[len(rows):] = 0                    # w = h = 0: the all-zero tensor; its string is dropped
         with torch.cuda.stream(self.s_rec):
-            self.d_rects.copy_(self.h_rects[k], non_blocking=True)
+            if self.crop == "quad":
+                self.d_qcrops.copy_(self.h_qcrops[k], non_blocking=True)
+                self.d_qmat.copy_(self.h_qmat[k], non_blocking=True)
+            else:
+                self.d_rects.copy_(self.h_rects[k], non_blocking=True)
             self._run_rec()
             self.h_ids[k].copy_(self.d_ids, non_blocking=True)
             self.h_lens[k].copy_(self.d_lens, non_blocking=True)
@@ -357,10 +382,16 @@ class Engine:
         self.stats["det_wait_s"] += t1 - t0
         self.stats["post_s"] += time.perf_counter() - t1
         rects, tags = [], []
-        for i, (polys, r, sc) in zip(idx, res):
+        for i, slot, (polys, r, sc) in zip(idx, slots, res):
             self._boxes[i], self._scores[i] = polys, [float(v) for v in sc]
             self._texts[i] = [None] * len(polys)
-            rects.extend(r.tolist())
+            if self.crop == "quad":                # the page's polygons -> quads -> descriptors, one batch call each
+                tq = time.perf_counter()
+                qc, qm = quad_crops(polys, self._sizes[i], page_id=slot)
+                rects.extend(zip(qc.tolist(), qm))
+                self.stats["quad_s"] += time.perf_counter() - tq
+            else:
+                rects.extend(r.tolist())
             tags.extend((i, b) for b in range(len(polys)))
         self.stats["crops"] += len(rects)
         self._feed(rects, tags)
@@ -459,6 +490,8 @@ class Engine:
                 raise RuntimeError(f"page {i}: bucket {h}x{w} exceeds the {self.L}x{self.L} the workspace was sized for")
         self.stats = {"pages": len(pages), "buckets": {f"{h}x{w}": len(v) for (h, w), v in buckets.items()}, "crops": 0, "rec_batches": 0,
                       "rectified": 0, "enhanced": 0, "launch_s": 0.0, "det_wait_s": 0.0, "post_s": 0.0, "rec_wait_s": 0.0}
+        if self.crop == "quad":
+            self.stats["quad_s"] = 0.0             # host time of ocrvi_min_area_quads + ocrvi_quad_crops (not part of post_s)
         if not pages:
             return []
         t_start = time.perf_counter()

@@ -367,6 +367,70 @@ def preprocess_crops(images_u8: torch.Tensor, rects: Sequence[Sequence[int]], im
     return out
 
 
+def _polygons_flat(boxes):
+    """A list of (n_i, 2) integer polygons -> (points int32 [total, 2], offsets int32 [n + 1])."""
+    polys = [np.asarray(b).reshape(-1, 2) for b in boxes]
+    offs = np.zeros(len(polys) + 1, np.int32)
+    if polys:
+        offs[1:] = np.cumsum([len(p) for p in polys])
+    pts = np.concatenate(polys, 0) if polys else np.empty((0, 2), np.int64)
+    if pts.size and (pts.min() < -32768 or pts.max() > 32767):
+        raise ValueError("min_area_quads: polygon coordinates must lie in [-32768, 32767]")
+    return np.ascontiguousarray(pts, np.int32).reshape(-1, 2), offs
+
+
+def min_area_quads(boxes):
+    """The minimum-area rectangle of each polygon of ``boxes`` (``ocrvi_min_area_quads``: exact integer arithmetic, include/ocrvi.h).
+    Returns (quads float64 [n, 4, 2], flags int32 [n]); ``flags[i] = 1`` marks a polygon without three hull vertices, whose quad is
+    its bounding box.  Needs no GPU."""
+    pts, offs = _polygons_flat(boxes)
+    n = len(offs) - 1
+    quads, flags = np.empty((n, 4, 2), np.float64), np.empty(n, np.int32)
+    _lib.check(_lib.load().ocrvi_min_area_quads(pts.ctypes.data, offs.ctypes.data, n, quads.ctypes.data, flags.ctypes.data))
+    return quads, flags
+
+
+def quad_crops(boxes, img_hw: Tuple[int, int], page_id: int = 0):
+    """The oriented crop descriptors of the polygons ``boxes`` of an ``img_hw = (h, w)`` page (``ocrvi_min_area_quads`` then
+    ``ocrvi_quad_crops``): (crops int32 [n, 4] = (page_id, w, h, 0), m_inv float64 [n, 9]).  A quad the four-point geometry refuses (shorter
+    than a pixel, tilted by exactly 45 degrees) and a degenerate polygon fall back to the ``crop_rect`` rectangle under a translation.
+    Needs no GPU."""
+    quads, flags = min_area_quads(boxes)
+    n = len(flags)
+    ids = np.full(n, int(page_id), np.int32)
+    hw = np.empty((n, 2), np.int32)
+    hw[:] = (int(img_hw[0]), int(img_hw[1]))
+    crops, m_inv = np.empty((n, 4), np.int32), np.empty((n, 9), np.float64)
+    _lib.check(_lib.load().ocrvi_quad_crops(quads.ctypes.data, flags.ctypes.data, n, ids.ctypes.data, hw.ctypes.data, crops.ctypes.data,
+                                            m_inv.ctypes.data))
+    return crops, m_inv
+
+
+def preprocess_crops_quad(images_u8: torch.Tensor, crops, m_inv, img_size: Tuple[int, int] = (32, 256)) -> torch.Tensor:
+    """``preprocess_crops`` for oriented crops (``ocrvi_crop_quad_resize_normalize``): images_u8 [N,H,W,3] uint8 on the device; crops
+    int32 [B, 4] = (image index, w, h, 0) and m_inv float64 [B, 9] as ``quad_crops`` returns them -> float32 [B,3,h,w]."""
+    images_u8 = images_u8.contiguous()
+    N, H, W, _ = images_u8.shape
+    c = torch.as_tensor(np.ascontiguousarray(np.asarray(crops, dtype=np.int32).reshape(-1, 4)), device=images_u8.device)
+    m = torch.as_tensor(np.ascontiguousarray(np.asarray(m_inv, dtype=np.float64).reshape(-1, 9)), device=images_u8.device)
+    if m.shape[0] != c.shape[0]:
+        raise ValueError(f"preprocess_crops_quad: {c.shape[0]} crops but {m.shape[0]} matrices")
+    out = torch.empty((c.shape[0], 3, img_size[0], img_size[1]), dtype=torch.float32, device=images_u8.device)
+    stream = torch.cuda.current_stream(images_u8.device).cuda_stream
+    _lib.check(_lib.load().ocrvi_crop_quad_resize_normalize(_dev_index(images_u8.device), images_u8.data_ptr(), N, H, W, c.data_ptr(), m.data_ptr(),
+                                                            c.shape[0], img_size[0], img_size[1], out.data_ptr(), stream))
+    return out
+
+
+CROP_MODES = ("rect", "quad")
+
+
+def _check_crop(crop) -> str:
+    if crop not in CROP_MODES:
+        raise ValueError(f"crop: expected 'rect' or 'quad', got {crop!r}")
+    return crop
+
+
 def preprocess_for_recognition(crop: np.ndarray, img_size: Tuple[int, int] = (32, 256), device: str = "cuda:0") -> torch.Tensor:
     """pipeline2.py:92-128 for one crop (HxWx3 uint8, or HxW grey which is replicated as cv2.COLOR_GRAY2RGB does) -> [3,h,w]."""
     if crop.ndim == 2:
@@ -519,7 +583,7 @@ def preprocess_image(image, quad, enhance: bool = False, device: str = "cuda:0")
 
 def detect_and_recognize(original_image, det_model, rec_model, post_processor: DBPostProcessor, device: str = "cuda:0", det_size: int = 640,
                          rec_size: Tuple[int, int] = (32, 256), rec_batch_size: int = 64, binary_head: bool = False, quad=None,
-                         enhance: bool = False):
+                         enhance: bool = False, crop: str = "rect"):
     """Steps 2 and 3 of the reference's per-image loop (pipeline2.py:306-352) with every stage on this library: resize + normalise on the
     device -> ``det_model`` -> ``post_processor`` on the host copy of the binary map -> boxes rescaled to the original image -> the
     bounding rectangle of each box cropped, resized and normalised on the device straight from the uploaded page -> ``rec_model`` greedy
@@ -529,7 +593,10 @@ def detect_and_recognize(original_image, det_model, rec_model, post_processor: D
     (``four_point_transform``) and replaces the original, so the boxes are in the rectified page's coordinates (:297).
     ``enhance``: ``enhance_document`` on the (rectified) page before the detector resize (scanner.py:190-191): boxes and crops come from
     the enhanced page.
+    ``crop``: ``"rect"`` (the reference's crop, the default) or ``"quad"``: each box's minimum-area rectangle is warped upright into the
+    recogniser instead of its bounding rectangle (``quad_crops``, ``preprocess_crops_quad``); boxes and scores do not change.
     Returns (rescaled_boxes [int32 (n_i, 2)], scores, texts); empty crops decode the all-zero tensor as pipeline2.py:154-156 does."""
+    _check_crop(crop)
     page = original_image if isinstance(original_image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(original_image))
     page = page.to(device).contiguous()
     if quad is not None:
@@ -544,8 +611,13 @@ def detect_and_recognize(original_image, det_model, rec_model, post_processor: D
     if hasattr(det_model, "check_range"):
         det_model.check_range()                           # f16x2 only: OverflowError if an activation left fp16's range
     rescaled = rescale_boxes(boxes, scale_w, scale_h)
-    rects = [(0,) + crop_rect((h, w), b) for b in rescaled]
     texts: List[str] = []
+    if crop == "quad":
+        qc, qm = quad_crops(rescaled, (h, w))
+        for i in range(0, len(qc), rec_batch_size):
+            texts.extend(rec_model.decode_greedy(preprocess_crops_quad(page[None], qc[i:i + rec_batch_size], qm[i:i + rec_batch_size], rec_size)))
+        return rescaled, scores, texts
+    rects = [(0,) + crop_rect((h, w), b) for b in rescaled]
     for i in range(0, len(rects), rec_batch_size):
         chunk = rects[i:i + rec_batch_size]
         live = [r for r in chunk if r[3] > 0 and r[4] > 0]
@@ -558,12 +630,14 @@ def detect_and_recognize(original_image, det_model, rec_model, post_processor: D
 
 
 def detect_and_recognize_pages(images, det_model, rec_model, post_processor: DBPostProcessor, device: str = "cuda:0", det_size: int = 640,
-                               rec_size: Tuple[int, int] = (32, 256), rec_batch_size: int = 64, binary_head: bool = False):
+                               rec_size: Tuple[int, int] = (32, 256), rec_batch_size: int = 64, binary_head: bool = False, crop: str = "rect"):
     """``detect_and_recognize`` for a list of pages of any sizes in one call: a one-shot ``engine.Engine`` (pages bucketed by detector
     shape, detector chunks and recogniser batches across pages).  ``det_model`` / ``rec_model`` are the library's DBNetPP / SVTRv2 on
     ``device``.  Returns [(rescaled_boxes, scores, texts) per page, in input order], each what ``detect_and_recognize`` returns for that
-    page alone (``binary_head`` as there)."""
+    page alone (``binary_head`` and ``crop`` as there)."""
     from .engine import Engine
+    _check_crop(crop)
     if torch.device(device).type != "cuda" or _dev_index(device) != det_model._dev_index():
         raise ValueError(f"models live on cuda:{det_model._dev_index()}, not {device}")
-    return Engine(det_model, rec_model, post_processor, det_size=det_size, rec_size=rec_size, rec_batch=rec_batch_size, binary_head=binary_head).run(images)
+    return Engine(det_model, rec_model, post_processor, det_size=det_size, rec_size=rec_size, rec_batch=rec_batch_size, binary_head=binary_head,
+                  crop=crop).run(images)
