@@ -338,6 +338,80 @@ int ocrvi_nlm_lab_u8(int device, const uint8_t* src, int h, int w, uint8_t* dst,
 /* cv2.filter2D(img, -1, [[-1,-1,-1],[-1,9,-1],[-1,-1,-1]]) (scanner.py:73-74) on any 3-channel page. */
 int ocrvi_sharpen_u8(int device, const uint8_t* src, int h, int w, uint8_t* dst, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * JPEG decode: replaces the cv2.imread at the head of the reference's loop (src/pipeline/pipeline2.py:284-288; its data are JPEG files,
+ * src/det/dataloader.py:307).  The host half is one serial pass per file (markers, EXIF orientation, Huffman decoding); dequantisation,
+ * inverse DCT, chroma upsampling, colour conversion and the orientation run on the device, batched over pages.
+ * Supported: SOF0 / SOF1 (Huffman, 8-bit precision), one interleaved scan; 1 component (grey, written to all three channels as
+ * IMREAD_COLOR does) or 3 (YCbCr) with chroma sampling 1 x 1 and luma sampling 1 x 1, 2 x 1 or 2 x 2 (4:4:4, 4:2:2, 4:2:0); 8- or 16-bit
+ * quantisation tables; restart intervals; APPn / COM skipped except APP1-EXIF, of which tag 0x0112 of IFD0 is read (both byte orders).
+ * Refused with OCRVI_EINVAL and a message naming the feature, never guessed and never decoded on the host instead: progressive,
+ * arithmetic, lossless, hierarchical and 12-bit files, 4 components, an Adobe marker with transform 0 or component ids R, G, B without
+ * JFIF (RGB-coded files), other sampling factors, several scans.  The bytes are untrusted: a truncated or corrupt file (bad marker
+ * length, a code that is not in its table, a run past coefficient 63, a missing or misnumbered RSTn, data left over at an RSTn or after
+ * the last MCU, no EOI, a side of 0 or above 65500, a missing table, a DC value outside 16 bits, fewer than two bits of scan data per
+ * block) is OCRVI_EINVAL.
+ * The arithmetic is the library's own definition, stated here; tests/jpeg_ref.py restates it in NumPy.  For files a conforming encoder
+ * produced from 8-bit images it equals libjpeg-turbo's default decode (PIL's Image.open().convert("RGB")) bit for bit -- pinned by
+ * tests/golden/jpeg_cases.npz; parity with cv2.imread is UNPINNED (cv2 absent).  For coefficients no encoder produces the two saturating
+ * steps below are the definition (libjpeg-turbo's SIMD code saturates differently): there the claim is device == tests/jpeg_ref.py.
+ *   dequantise  c = coefficient (int16) * table entry (<= 65535) in 32 bits, saturated to [-16384, 16383]
+ *   IDCT        the 8 x 8 "slow integer" inverse DCT, 13-bit constants 2446 3196 4433 6270 7373 9633 12299 15137 16069 16819 20995 25172,
+ *               the LL&M factorisation: even part from inputs 0, 2, 4, 6 (z1 = (i2 + i6) 4433, t2 = z1 - i6 15137, t3 = z1 + i2 6270,
+ *               t0 = (i0 + i4) << 13, t1 = (i0 - i4) << 13), odd part from 1, 3, 5, 7.  Pass 1 down the columns, (x + 2^10) >> 11,
+ *               saturated to [-16384, 16383]; pass 2 along the rows, (x + 2^17) >> 18, + 128, clamped to [0, 255].  Shifts are
+ *               arithmetic.  With both saturations every true value is below 2^31, so 32-bit wrap-around arithmetic is exact.
+ *   planes      component c is ceil(W h_c / hmax) x ceil(H v_c / vmax) samples; the block padding beyond them is never read
+ *   4:2:2 rows  out[2i] = (3 c[i] + c[i-1] + 1) >> 2, out[2i+1] = (3 c[i] + c[i+1] + 2) >> 2, the first output c[0], the last c[last]
+ *   4:2:0       t = 3 near_row + far_row (the row above the first / below the last real row is that row itself); out[2i] = (3 t[i] +
+ *               t[i-1] + 8) >> 4, out[2i+1] = (3 t[i] + t[i+1] + 7) >> 4, (4 t[0] + 8) >> 4 and (4 t[last] + 7) >> 4 at the ends
+ *   narrow      a chroma plane of one or two columns is replicated (each sample twice, in 4:2:0 in both directions) instead of filtered
+ *   colour      cb = Cb - 128, cr = Cr - 128: R = Y + ((91881 cr + 32768) >> 16), G = Y + ((-22554 cb - 46802 cr + 32768) >> 16),
+ *               B = Y + ((116130 cb + 32768) >> 16), each clamped to [0, 255]
+ *   orientation EXIF value k as PIL.ImageOps.exif_transpose applies it (2 mirror, 3 rotate 180, 4 flip, 5 transpose, 6 rotate 90
+ *               clockwise, 7 transverse, 8 rotate 90 counter-clockwise); 5..8 swap height and width
+ * Coefficient stream (what ocrvi_jpeg_parse writes, little-endian 32-bit words): [blocks + 1] record offsets, then the records.  Block
+ * d, in the order the scan codes the blocks (MCU by MCU; inside an MCU the luma blocks row by row, then Cb, then Cr; a grey file block
+ * by block in raster order), owns records off[d] .. off[d+1]; off[0] = 0 and off[blocks] = the number of records.  A record is
+ * (position << 16) | (value & 0xffff): position = row * 8 + column of a NON-ZERO quantised coefficient (the DC value after prediction),
+ * value its int16; within a block DC first, then zigzag order.  Zero coefficients have no record: a page costs its entropy, not 3 H W.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t width, height, components;      /* of the coded frame (before orientation) */
+    int32_t h_samp[3], v_samp[3];           /* sampling factors per component (1 x 1 for a grey file; 0 for absent components) */
+    int32_t restart_interval;               /* MCUs, 0 = none */
+    int32_t orientation;                    /* EXIF 0x0112, 1..8; 1 when absent or malformed */
+    int32_t out_height, out_width;          /* of the decoded page, after orientation */
+    int32_t reserved;
+    int64_t blocks;                         /* 8 x 8 blocks of the scan */
+    uint64_t stream_bytes;                  /* a `cap` that ocrvi_jpeg_parse never exceeds: 4 (blocks + 1 + min(64 blocks, 4 x scan bytes + blocks)) */
+    uint64_t workspace_bytes;               /* device bytes of the page's component planes, padded to whole MCUs, a multiple of 256 */
+    uint16_t quant[3][64];                  /* the quantisation table of each component, natural (row-major) order */
+    char reason[160];                       /* the message when the call fails (also ocrvi_last_error) */
+} ocrvi_jpeg_info_t;
+/* Host only, needs no GPU.  Parses the markers up to the scan.  On OCRVI_EINVAL the geometry fields are filled when the frame header was
+ * reached.  Takes no lock and no interpreter state, like ocrvi_jpeg_parse: calls from a thread pool run in parallel. */
+int ocrvi_jpeg_info(const void* data, size_t n, ocrvi_jpeg_info_t* info);
+/* Host only.  Huffman-decodes the scan into the coefficient stream at out[0 .. cap) (4-byte aligned; pinned memory when it is to be
+ * uploaded); *used = its bytes.  OCRVI_ENOMEM when cap is too small (never with cap >= info.stream_bytes). */
+int ocrvi_jpeg_parse(const void* data, size_t n, void* out, size_t cap, size_t* used);
+/* Host only.  Fills one entry of the table ocrvi_jpeg_decode_pages reads, int64 [OCRVI_JPEG_ENTRY]: (0 stream offset, 1 blocks, 2 records,
+ * 3 width, 4 height, 5 components, 6 luma h, 7 luma v, 8 orientation, 9 destination offset, 10 destination row stride, 11 workspace
+ * offset, 12..15 zero, 16..63 the three quantisation tables as uint16 [3][64]).  Offsets are in bytes from records_dev (a multiple of
+ * 4), dst_base (signed: pages of one launch may lie in different buffers either side of dst_base) and workspace (a multiple of 8);
+ * dst_stride >= 3 out_width. */
+#define OCRVI_JPEG_ENTRY 64
+int ocrvi_jpeg_table_entry(const ocrvi_jpeg_info_t* info, size_t used, int64_t stream_offset, int64_t dst_offset, int64_t dst_stride,
+                           int64_t workspace_offset, int64_t* entry);
+/* Decodes n_pages pages in two launches (jpeg_idct_kernel: records -> planes in the workspace; jpeg_rgb_kernel: planes -> uint8 HWC RGB
+ * [out_height, out_width, 3] at dst_base + destination offset, rows dst_stride bytes apart; bytes between rows are not written).
+ * records_dev: the pages' streams, table_dev: int64 [n_pages][OCRVI_JPEG_ENTRY], both DEVICE memory and read when the kernels run, so a
+ * captured graph survives rewritten tables and streams.  Enqueue-only on `stream`: no allocation, no synchronisation.  The pages'
+ * workspace regions must not overlap; an entry whose fields are out of range, or whose planes do not fit workspace_bytes, is skipped and
+ * never dereferenced.  A destination that is 4-byte aligned with a 4-byte aligned stride is written in words. */
+int ocrvi_jpeg_decode_pages(int device, const void* records_dev, const int64_t* table_dev, int n_pages, void* dst_base, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 /* Replaces DBPostProcessor(thresh, box_thresh, max_candidates, unclip_ratio).__call__ with .min_area (src/det/test.py:46-106) on a HOST
  * probability map prob[H*W] (the reference also runs this stage on the CPU after `.cpu().numpy()`, pipeline2.py:320-321).
  * Output: the unclipped polygons as int32 (x, y) pairs in points[2*cap_points]; box i owns points box_offsets[i] .. box_offsets[i+1]

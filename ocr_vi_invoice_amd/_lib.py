@@ -35,6 +35,7 @@ EXPORTS = [
     "ocrvi_enhance_init", "ocrvi_enhance_tables", "ocrvi_enhance_workspace_bytes", "ocrvi_enhance_u8",
     "ocrvi_rgb_to_lab_u8", "ocrvi_lab_to_rgb_u8", "ocrvi_clahe_lab_u8", "ocrvi_nlm_lab_u8", "ocrvi_sharpen_u8",
     "ocrvi_min_area_quads", "ocrvi_quad_crops", "ocrvi_crop_quad_resize_normalize_pages", "ocrvi_crop_quad_resize_normalize",
+    "ocrvi_jpeg_info", "ocrvi_jpeg_parse", "ocrvi_jpeg_table_entry", "ocrvi_jpeg_decode_pages",
 ]
 PAGE_ENTRY = 4          # int64 fields of one page-table entry: (device address, height, width, 0) -- OCRVI_PAGE_ENTRY
 # ocrvi_det_eval's record: 13 slots of 8 bytes (OCRVI_DET_EVAL_*), the first six int64, the rest float64
@@ -45,6 +46,7 @@ CTC_LOSS_MAX_TARGET = 1024      # OCRVI_CTC_LOSS_MAX_TARGET
 EDIT_DISTANCE_MAX_LEN = 2048    # OCRVI_EDIT_DISTANCE_MAX_LEN
 CLAHE_WORKSPACE_BYTES = 16384   # OCRVI_CLAHE_WORKSPACE_BYTES
 ENHANCE_MIN_SIDE = 16           # the smallest page side the enhance entries take
+JPEG_ENTRY = 64                 # int64 fields of one ocrvi_jpeg_decode_pages table entry -- OCRVI_JPEG_ENTRY
 
 
 class DetCfg(C.Structure):
@@ -56,6 +58,14 @@ class DetCfg(C.Structure):
 class RecCfg(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("dims", C.c_int32 * 3), ("num_blocks", C.c_int32 * 3), ("num_local", C.c_int32 * 3),
                 ("num_classes", C.c_int32), ("blank_id", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class JpegInfo(C.Structure):
+    """ocrvi_jpeg_info_t"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32), ("h_samp", C.c_int32 * 3), ("v_samp", C.c_int32 * 3),
+                ("restart_interval", C.c_int32), ("orientation", C.c_int32), ("out_height", C.c_int32), ("out_width", C.c_int32),
+                ("reserved", C.c_int32), ("blocks", C.c_int64), ("stream_bytes", C.c_uint64), ("workspace_bytes", C.c_uint64),
+                ("quant", (C.c_uint16 * 64) * 3), ("reason", C.c_char * 160)]
 
 
 _lib: Optional[C.CDLL] = None
@@ -144,6 +154,10 @@ def load() -> C.CDLL:
     lib.ocrvi_quad_crops.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     lib.ocrvi_crop_quad_resize_normalize_pages.argtypes = [i32, vp, i32, i32p, vp, i32, i32, i32, f32p, vp]
     lib.ocrvi_crop_quad_resize_normalize.argtypes = [i32, vp, i32, i32, i32, i32p, vp, i32, i32, i32, f32p, vp]
+    lib.ocrvi_jpeg_info.argtypes = [vp, sz, C.POINTER(JpegInfo)]
+    lib.ocrvi_jpeg_parse.argtypes = [vp, sz, vp, sz, C.POINTER(sz)]
+    lib.ocrvi_jpeg_table_entry.argtypes = [C.POINTER(JpegInfo), sz, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp]
+    lib.ocrvi_jpeg_decode_pages.argtypes = [i32, vp, vp, i32, vp, vp, sz, vp]
     lib.ocrvi_det_status.argtypes = [vp]
     lib.ocrvi_rec_status.argtypes = [vp]
     lib.ocrvi_range_reset.argtypes = [i32, vp]

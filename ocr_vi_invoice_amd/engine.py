@@ -27,7 +27,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .pipeline import DBPostProcessor, _check_crop, db_boxes_pages, enhance_init, enhance_workspace_bytes, four_point_geometry, quad_crops
+from .pipeline import (JPEG_BYTES, DBPostProcessor, _check_crop, db_boxes_pages, enhance_init, enhance_workspace_bytes, four_point_geometry,
+                       jpeg_info_struct, jpeg_parse_into, jpeg_table_entry, quad_crops)
 
 _ARENA_ALIGN = 256
 _STREAMS: Dict[int, Tuple[torch.cuda.Stream, torch.cuda.Stream]] = {}
@@ -106,6 +107,12 @@ class Engine:
     ``crop="quad"``: the recogniser sees each box's minimum-area rectangle warped upright (``ocrvi_min_area_quads`` / ``ocrvi_quad_crops`` on
     the host after the box stage, ``ocrvi_crop_quad_resize_normalize_pages`` in the recogniser graph) instead of its bounding rectangle, as
     ``detect_and_recognize(page, ..., crop="quad")`` does; ``"rect"`` (the default) is the reference's crop.
+    A page may also be the bytes of a baseline JPEG file (``bytes`` / ``bytearray`` / ``memoryview``; arrays and files mix freely): its
+    size, after the EXIF orientation, comes from ``ocrvi_jpeg_info``; every file of the call is entropy-decoded on the host pool
+    (``ocrvi_jpeg_parse``) before any device work, so a bad file raises ValueError naming its page and leaves nothing in flight; its
+    coefficient stream goes through pinned staging with its chunk and ``ocrvi_jpeg_decode_pages`` decodes it straight into its arena
+    slot (into the raw region when it has a quad), ahead of the chunk's warp and enhancement.  The results are those of the same page
+    passed as the array ``pipeline.imdecode`` returns.
     The captured graphs hold the models' weights as they were: after reloading a model's weights, build a new Engine."""
 
     def __init__(self, det_model, rec_model, post_processor: DBPostProcessor, det_size: int = 960, rec_size: Tuple[int, int] = (32, 256),
@@ -184,6 +191,13 @@ class Engine:
         #      refuses to work in place), grown per run
         self.d_enh_ws = torch.empty(0, dtype=torch.uint8, **d)
         self.d_enh_out = torch.empty(0, dtype=torch.uint8, **d)
+        # ---- JPEG pages: per detector chunk, the coefficient streams (device region + two pinned slots, grown on demand), the component
+        #      planes of the chunk's files and the decode table
+        self.d_jrec = torch.empty(0, dtype=torch.uint8, **d)
+        self.h_jrec = [torch.empty(0, dtype=torch.uint8), torch.empty(0, dtype=torch.uint8)]
+        self.d_jws = torch.empty(0, dtype=torch.uint8, **d)
+        self.d_jtab = torch.zeros((self.det_chunk, _lib.JPEG_ENTRY), dtype=torch.int64, **d)
+        self.h_jtab = [torch.zeros((self.det_chunk, _lib.JPEG_ENTRY), dtype=torch.int64).pin_memory() for _ in range(2)]
         # one stream pair per device for every engine of the process: each new HIP stream takes the next hardware queue round-robin
         if self.devi not in _STREAMS:
             _STREAMS[self.devi] = (torch.cuda.Stream(self.dev), torch.cuda.Stream(self.dev))
@@ -191,6 +205,7 @@ class Engine:
         self._det_graphs: "collections.OrderedDict[tuple, torch.cuda.CUDAGraph]" = collections.OrderedDict()
         self._rec_graph = None
         self._rec_warm = False
+        self._pool = None                          # host threads of the JPEG entropy decoder, started with the first file
         self.stats = {}
 
     # ------------------------------------------------------------------------------------------------ device work (enqueue-only)
@@ -256,16 +271,72 @@ class Engine:
 
     # ------------------------------------------------------------------------------------------------ input
     @staticmethod
-    def _check_page(i, p):
+    def _check_page(i, p, info=None):
+        if isinstance(p, JPEG_BYTES):             # a JPEG file: its size after orientation (ValueError naming the page for a bad header)
+            info = jpeg_info_struct(p, f"page {i}") if info is None else info
+            return int(info.out_height), int(info.out_width)
         if isinstance(p, np.ndarray):
             ok = p.dtype == np.uint8
         elif isinstance(p, torch.Tensor):
             ok = p.dtype == torch.uint8
         else:
-            raise ValueError(f"page {i}: expected an RGB uint8 HxWx3 numpy array or tensor, got {type(p).__name__}")
+            raise ValueError(f"page {i}: expected an RGB uint8 HxWx3 numpy array or tensor, or JPEG bytes, got {type(p).__name__}")
         if not ok or p.ndim != 3 or p.shape[2] != 3:
             raise ValueError(f"page {i}: expected an RGB uint8 HxWx3 array, got dtype {p.dtype} shape {tuple(p.shape)}")
         return int(p.shape[0]), int(p.shape[1])
+
+    def _parse_jpegs(self, pages, infos):
+        """Entropy-decodes every JPEG page of the call on the engine's host pool (``post_threads`` threads, the budget of the box stage,
+        which never runs at the same time): {page index: (info, uint32 stream, bytes used)}.  ValueError naming the first bad page;
+        nothing has touched the device by then.
+        A stream waits in pageable memory until its chunk is staged and is dropped there.  It cannot be decoded into the pinned slot it
+        is uploaded from: the two slots belong to the chunks in flight, while a corrupt scan must be found, for every file of the call,
+        before the first chunk is launched; pinned room for a whole call would be hundreds of megabytes for a folder of pages.  The
+        buffer is sized by the bound ``ocrvi_jpeg_info`` gives; only the pages the stream's words touch ever become resident."""
+        if not infos:
+            return {}
+        t0 = time.perf_counter()
+
+        def one(i):
+            buf = np.empty(infos[i].stream_bytes // 4, np.uint32)
+            return infos[i], buf, jpeg_parse_into(pages[i], buf.ctypes.data, buf.nbytes, f"page {i}")
+
+        if self._pool is None:
+            import concurrent.futures
+            self._pool = concurrent.futures.ThreadPoolExecutor(self.post_threads, thread_name_prefix="ocrvi-jpeg")
+        futs = [(i, self._pool.submit(one, i)) for i in sorted(infos)]
+        out, err = {}, None
+        for i, f in futs:                         # every job is waited for, the first failure in page order is raised
+            try:
+                out[i] = f.result()
+            except Exception as e:               # noqa: BLE001
+                err = err or e
+        if err is not None:
+            raise err
+        self.stats["jpeg_parse_s"] = time.perf_counter() - t0
+        return out
+
+    def _decode_jpegs(self, wave, lo, hi, s, targets):
+        """The JPEG pages of chunk wave[lo:hi] -> ``targets`` [(page index, destination address)], one ``ocrvi_jpeg_decode_pages`` launch
+        on the detector stream: streams and table through pinned slot ``s``."""
+        tab = self.h_jtab[s].numpy()
+        stage = self.h_jrec[s].numpy()
+        base = self.arena.data_ptr()
+        soff = woff = 0
+        for k, (i, dst_ptr) in enumerate(targets):
+            info, buf, used = self._jpeg[i]
+            stage[soff:soff + used].view(np.uint32)[:] = buf[:used // 4]
+            self._jpeg[i] = (info, None, used)     # the host copy has served: only its sizes are still read
+            jpeg_table_entry(info, used, soff, dst_ptr - base, 3 * info.out_width, woff, tab[k])
+            soff += (used + _ARENA_ALIGN - 1) // _ARENA_ALIGN * _ARENA_ALIGN
+            woff += info.workspace_bytes
+        n = len(targets)
+        self.d_jrec[:soff].copy_(self.h_jrec[s][:soff], non_blocking=True)
+        self.d_jtab[:n].copy_(self.h_jtab[s][:n], non_blocking=True)
+        _lib.check(self.lib.ocrvi_jpeg_decode_pages(self.devi, self.d_jrec.data_ptr(), self.d_jtab.data_ptr(), n, base, self.d_jws.data_ptr(),
+                                                    self.d_jws.numel(), self.s_det.cuda_stream))
+        self.stats["jpeg"] += n
+        self.stats["jpeg_stream_bytes"] += sum(self._jpeg[i][2] for i, _ in targets)
 
     def _stage(self, pages, wave, lo, hi, s=0):
         """Pages wave[lo:hi] (consecutive arena slots) -> the arena, on the detector stream.  A page with a quad is warped into its slot
@@ -273,6 +344,7 @@ class Engine:
         pinned slot ``s`` and the raw region (chunk c - 2, the previous user of slot ``s``, has been waited for by now)."""
         PE, dc = _lib.PAGE_ENTRY, self.det_chunk
         tabs, roff, n_warp = None, 0, 0
+        jpegs = []                                 # (page, destination address): the arena slot, or the raw region for a page with a quad
         for slot in range(lo, hi):
             i = wave[slot]
             p, off, nb = pages[i], self._offs[slot], self._nbytes[slot]
@@ -286,6 +358,10 @@ class Engine:
                     src = p if p.is_contiguous() else p.contiguous()
                     self._keep.append(src)         # alive until the wave has drained
                     src_ptr = src.data_ptr()
+                elif i in self._jpeg:
+                    src_ptr = self.d_raw.data_ptr() + roff
+                    jpegs.append((i, src_ptr))
+                    roff += (rh * rw * 3 + _ARENA_ALIGN - 1) // _ARENA_ALIGN * _ARENA_ALIGN
                 else:
                     src = p.numpy() if isinstance(p, torch.Tensor) else p
                     rb = rh * rw * 3
@@ -300,11 +376,15 @@ class Engine:
                 n_warp += 1
             elif isinstance(p, torch.Tensor) and p.is_cuda:
                 dst.copy_(p.contiguous().view(-1), non_blocking=True)
+            elif i in self._jpeg:
+                jpegs.append((i, dst.data_ptr()))
             else:
                 src = p.numpy() if isinstance(p, torch.Tensor) else p
                 stage = self.h_stage[off:off + nb].numpy()
                 np.copyto(stage.reshape(src.shape), src)
                 dst.copy_(self.h_stage[off:off + nb], non_blocking=True)
+        if jpegs:                                  # ahead of the warp and the enhancement that read these pages
+            self._decode_jpegs(wave, lo, hi, s, jpegs)
         if n_warp:
             self.d_warp.copy_(self.h_warp[s], non_blocking=True)
             base = self.d_warp.data_ptr()
@@ -424,7 +504,7 @@ class Engine:
         if self.arena.numel() < off:               # (the previous wave has drained: nothing reads the old arena any more)
             self.arena = torch.empty(off, dtype=torch.uint8, device=self.dev)
         on_host = [not (isinstance(pages[i], torch.Tensor) and pages[i].is_cuda) for i in wave]
-        if any(h and self._mats[i] is None for h, i in zip(on_host, wave)) and self.h_stage.numel() < off:
+        if any(h and self._mats[i] is None and i not in self._jpeg for h, i in zip(on_host, wave)) and self.h_stage.numel() < off:
             self.h_stage = torch.empty(off, dtype=torch.uint8).pin_memory()
         tab = self.h_table.numpy()
         tab[:] = 0
@@ -450,6 +530,17 @@ class Engine:
         if self.d_raw.numel() < raw:               # (the previous wave has drained)
             self.d_raw = torch.empty(raw, dtype=torch.uint8, device=self.dev)
             self.h_raw = [torch.empty(raw, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        # the JPEG regions: the largest chunk's streams and component planes
+        jrec = jws = 0
+        for lo, hi, _ in chunks:
+            js = [self._jpeg[wave[k]] for k in range(lo, hi) if wave[k] in self._jpeg]
+            jrec = max(jrec, sum((u + _ARENA_ALIGN - 1) // _ARENA_ALIGN * _ARENA_ALIGN for _, _, u in js))
+            jws = max(jws, sum(info.workspace_bytes for info, _, _ in js))
+        if self.d_jrec.numel() < jrec:             # (the previous wave has drained)
+            self.d_jrec = torch.empty(jrec, dtype=torch.uint8, device=self.dev)
+            self.h_jrec = [torch.empty(jrec, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        if self.d_jws.numel() < jws:
+            self.d_jws = torch.empty(jws, dtype=torch.uint8, device=self.dev)
         pending = collections.deque()
         for c, (lo, hi, shape) in enumerate(chunks):
             if len(pending) == 2:                  # its pinned map slot is the one chunk c reuses
@@ -470,7 +561,9 @@ class Engine:
     # ------------------------------------------------------------------------------------------------ public
     def run(self, pages: Sequence, quads: Sequence = None, enhance=None) -> List[Tuple[list, list, list]]:
         pages = list(pages)
-        raw_sizes = [self._check_page(i, p) for i, p in enumerate(pages)]
+        t_start = time.perf_counter()              # (total_s includes the host entropy decode of JPEG pages)
+        infos = {i: jpeg_info_struct(p, f"page {i}") for i, p in enumerate(pages) if isinstance(p, JPEG_BYTES)}
+        raw_sizes = [self._check_page(i, p, infos.get(i)) for i, p in enumerate(pages)]
         # (every ValueError -- pages, quads, sizes that round to 0 -- is raised here, before any GPU work)
         sizes, mats, shapes, scales, buckets = plan_rectified(raw_sizes, quads, self.det_size)
         if enhance is None or isinstance(enhance, (bool, np.bool_)):
@@ -494,7 +587,8 @@ class Engine:
             self.stats["quad_s"] = 0.0             # host time of ocrvi_min_area_quads + ocrvi_quad_crops (not part of post_s)
         if not pages:
             return []
-        t_start = time.perf_counter()
+        self.stats.update(jpeg=0, jpeg_stream_bytes=0, jpeg_parse_s=0.0)
+        self._jpeg = self._parse_jpegs(pages, infos)      # (a corrupt scan raises here: still before any GPU work)
         self._sizes, self._shapes, self._scales = sizes, shapes, scales
         self._raw_sizes, self._mats, self._keep = raw_sizes, mats, []
         self._enhance = flags

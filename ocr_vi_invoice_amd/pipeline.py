@@ -581,13 +581,143 @@ def preprocess_image(image, quad, enhance: bool = False, device: str = "cuda:0")
     return four_point_transform(image, quad, device)
 
 
+JPEG_BYTES = (bytes, bytearray, memoryview)
+_JPEG_POOL = None
+
+
+def jpeg_pool():
+    """The host thread pool of the entropy decoder (``ocrvi_jpeg_parse`` holds no lock and ctypes releases the interpreter lock)."""
+    global _JPEG_POOL
+    if _JPEG_POOL is None:
+        import concurrent.futures
+        import os
+        try:
+            n = len(os.sched_getaffinity(0))
+        except AttributeError:
+            n = os.cpu_count() or 1
+        _JPEG_POOL = concurrent.futures.ThreadPoolExecutor(max(1, min(n, 16)), thread_name_prefix="ocrvi-jpeg")
+    return _JPEG_POOL
+
+
+def _jpeg_view(data) -> np.ndarray:
+    """The file's bytes as a uint8 array, without a copy."""
+    if not isinstance(data, JPEG_BYTES):
+        raise ValueError(f"expected JPEG bytes (bytes, bytearray or memoryview), got {type(data).__name__}")
+    return np.frombuffer(data, dtype=np.uint8)
+
+
+def jpeg_info_struct(data, what: str = "jpeg") -> "_lib.JpegInfo":
+    """``ocrvi_jpeg_info`` (host only); ValueError ``what: message`` for a file the library refuses or cannot read."""
+    a = _jpeg_view(data)
+    info = _lib.JpegInfo()
+    rc = _lib.load().ocrvi_jpeg_info(a.ctypes.data if a.size else None, a.size, ctypes.byref(info))
+    if rc == -1:
+        raise ValueError(f"{what}: {info.reason.decode('utf-8', 'replace')}")
+    _lib.check(rc)
+    return info
+
+
+def jpeg_info(data) -> dict:
+    """What ``ocrvi_jpeg_info`` reports about a JPEG file (host only, needs no GPU): the coded width, height, components, sampling factors,
+    restart interval, EXIF orientation, the decoded page's ``out_height`` / ``out_width`` (after orientation), the number of blocks and the
+    two sizes ``stream_bytes`` / ``workspace_bytes``.  ValueError naming the feature for an unsupported file, or the fault of a corrupt one."""
+    info = jpeg_info_struct(data)
+    n = info.components
+    return {"width": info.width, "height": info.height, "components": n, "h_samp": list(info.h_samp)[:n], "v_samp": list(info.v_samp)[:n],
+            "restart_interval": info.restart_interval, "orientation": info.orientation, "out_height": info.out_height,
+            "out_width": info.out_width, "blocks": info.blocks, "stream_bytes": info.stream_bytes, "workspace_bytes": info.workspace_bytes,
+            "quant": np.ctypeslib.as_array(info.quant).copy()[:n]}
+
+
+def jpeg_parse_into(data, out_ptr: int, cap: int, what: str = "jpeg") -> int:
+    """``ocrvi_jpeg_parse`` into ``cap`` bytes at ``out_ptr``; returns the bytes used.  The error is read on the calling thread (it is
+    thread-local): ValueError for a corrupt file, MemoryError for a short buffer."""
+    a = _jpeg_view(data)
+    used = ctypes.c_size_t()
+    rc = _lib.load().ocrvi_jpeg_parse(a.ctypes.data if a.size else None, a.size, out_ptr, cap, ctypes.byref(used))
+    if rc == -1:
+        raise ValueError(f"{what}: {_lib.last_error()}")
+    _lib.check(rc)
+    return used.value
+
+
+def jpeg_parse(data) -> np.ndarray:
+    """The sparse coefficient stream of a file as uint32 words (host only; include/ocrvi.h states the format)."""
+    info = jpeg_info_struct(data)
+    buf = np.empty(info.stream_bytes // 4, np.uint32)
+    return buf[:jpeg_parse_into(data, buf.ctypes.data, buf.nbytes) // 4].copy()
+
+
+def jpeg_table_entry(info, used: int, stream_offset: int, dst_offset: int, dst_stride: int, workspace_offset: int, entry: np.ndarray) -> None:
+    """``ocrvi_jpeg_table_entry`` into ``entry`` (int64 [JPEG_ENTRY], contiguous)."""
+    assert entry.dtype == np.int64 and entry.size == _lib.JPEG_ENTRY and entry.flags.c_contiguous
+    _lib.check(_lib.load().ocrvi_jpeg_table_entry(ctypes.byref(info), used, stream_offset, dst_offset, dst_stride, workspace_offset,
+                                                  entry.ctypes.data))
+
+
+def _align(v: int, a: int = 256) -> int:
+    return (v + a - 1) // a * a
+
+
+def imdecode(data, device: str = "cuda:0"):
+    """cv2.imdecode / cv2.imread + cvtColor(BGR2RGB) (src/pipeline/pipeline2.py:284-288) for baseline JPEG: ``data`` is the bytes of one file
+    (-> one uint8 [h, w, 3] RGB tensor on ``device``) or a list of them (-> a list of tensors, decoded in one batched launch).  Entropy
+    decoding runs on the host (a thread per file), everything else in ``ocrvi_jpeg_decode_pages`` on the current stream; the EXIF
+    orientation is applied.  ValueError for an unsupported or corrupt file (naming its index in a list); there is no host decoder behind
+    this one.  The arithmetic is stated in include/ocrvi.h: PIL / libjpeg-turbo's output for encoder-produced files, cv2 parity unpinned."""
+    single = isinstance(data, JPEG_BYTES)
+    files = [data] if single else list(data)
+    if not files:
+        return []
+    names = ["imdecode" if single else f"imdecode: file {i}" for i in range(len(files))]
+    infos = [jpeg_info_struct(f, w) for f, w in zip(files, names)]
+    dev = torch.device(device)
+    devi = _dev_index(dev)
+    s_off, w_off, d_off = [0], [0], [0]
+    for info in infos:
+        s_off.append(s_off[-1] + _align(info.stream_bytes))
+        w_off.append(w_off[-1] + info.workspace_bytes)
+        d_off.append(d_off[-1] + _align(info.out_height * info.out_width * 3))
+    h_rec = torch.empty(s_off[-1], dtype=torch.uint8).pin_memory()
+    base = h_rec.data_ptr()
+    jobs = [(f, base + s_off[i], infos[i].stream_bytes, names[i]) for i, f in enumerate(files)]
+    if len(files) > 1:
+        used = list(jpeg_pool().map(lambda j: jpeg_parse_into(*j), jobs))
+    else:
+        used = [jpeg_parse_into(*jobs[0])]
+    table = np.zeros((len(files), _lib.JPEG_ENTRY), np.int64)
+    for i, info in enumerate(infos):
+        jpeg_table_entry(info, used[i], s_off[i], d_off[i], 3 * info.out_width, w_off[i], table[i])
+    with torch.cuda.device(dev):
+        d_rec = torch.empty(s_off[-1], dtype=torch.uint8, device=dev)
+        for i in range(len(files)):            # only the bytes each stream uses cross the bus
+            d_rec[s_off[i]:s_off[i] + used[i]].copy_(h_rec[s_off[i]:s_off[i] + used[i]], non_blocking=True)
+        d_tab = torch.from_numpy(table).pin_memory().to(dev, non_blocking=True)
+        ws = torch.empty(max(w_off[-1], 8), dtype=torch.uint8, device=dev)
+        out = torch.empty(d_off[-1], dtype=torch.uint8, device=dev)
+        _lib.check(_lib.load().ocrvi_jpeg_decode_pages(devi, d_rec.data_ptr(), d_tab.data_ptr(), len(files), out.data_ptr(), ws.data_ptr(),
+                                                       ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
+    pages = [out[d_off[i]:d_off[i] + info.out_height * info.out_width * 3].view(info.out_height, info.out_width, 3)
+             for i, info in enumerate(infos)]
+    return pages[0] if single else pages
+
+
+def imread(path: str, device: str = "cuda:0") -> torch.Tensor:
+    """``cv2.imread(path)`` + ``cvtColor(BGR2RGB)`` of the reference's loop (pipeline2.py:284-288) for a baseline JPEG file: the file's bytes
+    through ``imdecode``.  OSError for an unreadable file (the reference gets ``None`` and skips the image), ValueError for one that is
+    not a supported JPEG."""
+    with open(path, "rb") as f:
+        return imdecode(f.read(), device)
+
+
 def detect_and_recognize(original_image, det_model, rec_model, post_processor: DBPostProcessor, device: str = "cuda:0", det_size: int = 640,
                          rec_size: Tuple[int, int] = (32, 256), rec_batch_size: int = 64, binary_head: bool = False, quad=None,
                          enhance: bool = False, crop: str = "rect"):
     """Steps 2 and 3 of the reference's per-image loop (pipeline2.py:306-352) with every stage on this library: resize + normalise on the
     device -> ``det_model`` -> ``post_processor`` on the host copy of the binary map -> boxes rescaled to the original image -> the
     bounding rectangle of each box cropped, resized and normalised on the device straight from the uploaded page -> ``rec_model`` greedy
-    CTC in batches of ``rec_batch_size``.  ``original_image``: RGB uint8 HxWx3 (numpy or device tensor).
+    CTC in batches of ``rec_batch_size``.  ``original_image``: RGB uint8 HxWx3 (numpy or device tensor), or the bytes of a baseline JPEG file
+    (``bytes`` / ``bytearray`` / ``memoryview``: ``imdecode`` first, the reference's cv2.imread, pipeline2.py:284-288).
     ``binary_head``: call ``det_model.forward_binary`` (the binarise branch alone; same map in f32 / f16x2) instead of ``det_model(...)``.
     ``quad``: the document's four corners in ``original_image`` (step 1, pipeline2.py:291-302): the page is rectified first
     (``four_point_transform``) and replaces the original, so the boxes are in the rectified page's coordinates (:297).
@@ -597,6 +727,8 @@ def detect_and_recognize(original_image, det_model, rec_model, post_processor: D
     recogniser instead of its bounding rectangle (``quad_crops``, ``preprocess_crops_quad``); boxes and scores do not change.
     Returns (rescaled_boxes [int32 (n_i, 2)], scores, texts); empty crops decode the all-zero tensor as pipeline2.py:154-156 does."""
     _check_crop(crop)
+    if isinstance(original_image, JPEG_BYTES):               # a JPEG file's bytes: decoded on the device (``imdecode``)
+        original_image = imdecode(original_image, device)
     page = original_image if isinstance(original_image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(original_image))
     page = page.to(device).contiguous()
     if quad is not None:
