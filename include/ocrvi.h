@@ -583,6 +583,23 @@ int ocrvi_test_deform_conv_res(int device, int dtype, const float* x, const floa
 int ocrvi_test_conv(int device, int dtype, const float* x, const float* weight_host, const float* bias_host,
                     int N, int C, int H, int W, int Co, int ksize, int sh, int sw, int groups, int act, float* out,
                     int iters, float* avg_ms);
+/* Stride-1 conv2d (square kernel 1 or 3, pad = k/2) with a residual in the epilogue: out = act(conv(x) + bias + res).  res_mode 1: res
+ * is float32 NCHW [N,Co,H,W] (Bottleneck conv3, BasicBlock conv2); res_mode 2: res is [N,Co,H/2,W/2] and is added nearest-2x upsampled,
+ * out[.., oh, ow] += res[.., oh/2, ow/2] (the FPN laterals, neck.py:36-38; H and W must be even); res NULL with res_mode 0: no residual.
+ * res is converted to NHWC in the compute type exactly as x is.  Same conventions as ocrvi_test_conv. */
+int ocrvi_test_conv_res(int device, int dtype, const float* x, const float* weight_host, const float* bias_host, const float* res, int N,
+                        int C, int H, int W, int Co, int ksize, int res_mode, int act, float* out, int iters, float* avg_ms);
+/* The DB head's two deconvolutions (head.py:13-16) as the detector runs them: ConvTranspose2d(64,64,2,2) + folded BN + ReLU of both
+ * branches packed as one grouped GEMM (group 0 = binarise, 1 = threshold), ConvTranspose2d(64,1,2,2) in its epilogue.  dc1_w_*: host
+ * [64][64][2][2] (c_in, c_out, a, b), dc1_b_*: host [64], dc2_w_*: host [64][1][2][2], dc2_b_*: host [1].
+ * groups = 2, binary_only = 0: x float32 NCHW device [N,128,OH,OW] (channels 0..63 are the binarise branch's input, 64..127 the threshold
+ * branch's); out = bin_logits, out2 = thresh_logits, float32 device [N,1,4*OH,4*OW].
+ * groups = 1, binary_only = 1: the binarise-branch view of the same packed weights, as ocrvi_det_forward_binary launches it; x is
+ * [N,64,OH,OW]; out = sigmoid(bin_logits); out2 is not used.  Any other combination, or out2 NULL with binary_only = 0, is OCRVI_EINVAL. */
+int ocrvi_test_db_tail(int device, int dtype, const float* x, const float* dc1_w_bin_host, const float* dc1_b_bin_host,
+                       const float* dc1_w_thr_host, const float* dc1_b_thr_host, const float* dc2_w_bin_host, const float* dc2_b_bin_host,
+                       const float* dc2_w_thr_host, const float* dc2_b_thr_host, int N, int OH, int OW, int groups, int binary_only,
+                       float* out, float* out2, int iters, float* avg_ms);
 /* Linear / 1x1 convolution as a plain GEMM with the fused epilogue of the hot path: out[M][N] = act(a[M][K] . weight[N][K]^T + bias
  * (+ res)) (res_post = 0) or act(...) + res (res_post = 1); a, res and out are float32 DEVICE buffers (converted to/from `dtype`
  * around the call; the residual is kept in fp32 when out_f32 is set, as the recogniser's residual stream is), weight/bias HOST.  Takes

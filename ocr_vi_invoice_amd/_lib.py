@@ -36,6 +36,7 @@ EXPORTS = [
     "ocrvi_rgb_to_lab_u8", "ocrvi_lab_to_rgb_u8", "ocrvi_clahe_lab_u8", "ocrvi_nlm_lab_u8", "ocrvi_sharpen_u8",
     "ocrvi_min_area_quads", "ocrvi_quad_crops", "ocrvi_crop_quad_resize_normalize_pages", "ocrvi_crop_quad_resize_normalize",
     "ocrvi_jpeg_info", "ocrvi_jpeg_parse", "ocrvi_jpeg_table_entry", "ocrvi_jpeg_decode_pages",
+    "ocrvi_test_conv_res", "ocrvi_test_db_tail",
 ]
 PAGE_ENTRY = 4          # int64 fields of one page-table entry: (device address, height, width, 0) -- OCRVI_PAGE_ENTRY
 # ocrvi_det_eval's record: 13 slots of 8 bytes (OCRVI_DET_EVAL_*), the first six int64, the rest float64
@@ -128,6 +129,9 @@ def load() -> C.CDLL:
     lib.ocrvi_test_offset_conv.argtypes = [i32, i32, f32p, vp, vp, i32, i32, i32, i32, i32, f32p, i32, C.POINTER(C.c_float)]
     lib.ocrvi_test_conv.argtypes = [i32, i32, f32p, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32p, i32,
                                     C.POINTER(C.c_float)]
+    lib.ocrvi_test_conv_res.argtypes = [i32, i32, f32p, vp, vp, f32p, i32, i32, i32, i32, i32, i32, i32, i32, f32p, i32, C.POINTER(C.c_float)]
+    lib.ocrvi_test_db_tail.argtypes = [i32, i32, f32p, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32p, f32p, i32,
+                                       C.POINTER(C.c_float)]
     lib.ocrvi_test_gemm.argtypes = [i32, i32, f32p, vp, vp, f32p, i32, i32, i32, i32, i32, i32, f32p, i32, C.POINTER(C.c_float)]
     lib.ocrvi_test_stem_pool.argtypes = [i32, i32, f32p, vp, vp, i32, i32, i32, i32, f32p, i32, C.POINTER(C.c_float)]
     lib.ocrvi_test_attention.argtypes = [i32, i32, f32p, i32, i32, i32, f32p, i32, C.POINTER(C.c_float)]

@@ -2,6 +2,7 @@
 // caller-supplied float32 NCHW device tensors.  They allocate scratch, convert layouts, time with HIP events on
 // their own stream (the MFMA kernels' hooks; the memory-bound kernels' hooks at the end take no timing arguments),
 // and synchronise -- test infrastructure around the same kernels the model graphs launch.
+#include <algorithm>
 #include <memory>
 
 #include "model.h"
@@ -201,6 +202,101 @@ extern "C" int ocrvi_test_conv(int device, int dtype, const float* x, const floa
     o.sh = sh; o.sw = sw; o.pad = pad; o.act = act;
     OCRVI_TRY(timed(sc, iters, avg_ms, [&]() { return conv(r, L, tx, ty, o); }));
     OCRVI_TRY(k_nhwc_to_nchw_f32(dtype, yn, out, N, Ho, Wo, Co, Co, 0, sc.s));
+    OCRVI_HIP(hipStreamSynchronize(sc.s));
+    return OCRVI_OK;
+}
+
+// Stride-1 conv (1x1, or 3x3 pad 1) with a residual in the epilogue: out = act(conv(x) + bias + res).  res_mode RES_SAME: res is
+// [N, Co, H, W] (Bottleneck conv3, BasicBlock conv2); RES_UP2: res is [N, Co, H/2, W/2], added nearest-2x upsampled (the FPN laterals,
+// neck.py:36-38).  The residual is converted to the mode's element type, as the model's own residuals are.
+extern "C" int ocrvi_test_conv_res(int device, int dtype, const float* x, const float* weight_host, const float* bias_host, const float* res, int N,
+                                   int C, int H, int W, int Co, int ksize, int res_mode, int act, float* out, int iters, float* avg_ms) {
+    OCRVI_CHECK(x && weight_host && out && (ksize == 1 || ksize == 3) && N > 0 && C > 0 && H > 0 && W > 0 && Co > 0 && dtype_valid(dtype),
+                OCRVI_EINVAL, "test_conv_res: bad argument");
+    OCRVI_CHECK(act == ACT_NONE || act == ACT_RELU || act == ACT_GELU, OCRVI_EINVAL, "test_conv_res: unknown activation %d", act);
+    OCRVI_CHECK(res ? (res_mode == RES_SAME || res_mode == RES_UP2) : res_mode == RES_NONE, OCRVI_EINVAL,
+                "test_conv_res: res_mode %d %s a residual (1 = same shape, 2 = half resolution)", res_mode, res ? "with" : "without");
+    OCRVI_HIP(hipSetDevice(device));
+    Scratch sc;
+    OCRVI_TRY(sc.init());
+    const int amode = ksize == 1 ? AM_CONV1 : AM_CONV3;
+    DeviceStore st;
+    ConvLayer L;
+    // (as a model's loader would: a 3x3 that runs WITHOUT a residual asks for conv3_halo's weight form; with one it must not -- conv3_halo
+    // takes no residual and launch_conv rejects quartet weights everywhere else)
+    const bool halo = !res && ksize == 3 && (act == ACT_NONE || act == ACT_RELU);
+    PackedConv pc = pack_conv(weight_host, bias_host, Co, C, ksize, ksize, 1, amode, dtype, halo);
+    OCRVI_TRY(upload_packed(st, pc, amode, &L));
+    void *xn = nullptr, *yn = nullptr;
+    OCRVI_TRY(sc.alloc((size_t)N * H * W * C * dtype_size(dtype), &xn));
+    OCRVI_TRY(sc.alloc((size_t)N * H * W * Co * dtype_size(dtype), &yn));
+    OCRVI_TRY(to_nhwc(dtype, x, xn, N, C, H * W, sc.s));
+    Runner r(dtype, sc.s, (void*)256, 0);
+    Tensor tx; tx.p = xn; tx.n = N; tx.h = H; tx.w = W; tx.c = C;
+    Tensor ty; ty.p = yn; ty.n = N; ty.h = H; ty.w = W; ty.c = Co;
+    Tensor tr = ty;
+    ConvOpts o;
+    o.pad = ksize / 2; o.act = act;
+    if (res) {
+        if (res_mode == RES_UP2) { tr.h = H / 2; tr.w = W / 2; }   // (odd H or W: launch_conv refuses the call before anything reads it)
+        void* rn = nullptr;
+        OCRVI_TRY(sc.alloc(tr.pixels() * Co * dtype_size(dtype), &rn));
+        OCRVI_TRY(to_nhwc(dtype, res, rn, N, Co, tr.h * tr.w, sc.s));
+        tr.p = rn;
+        o.res = &tr; o.res_mode = res_mode;
+    }
+    OCRVI_TRY(timed(sc, iters, avg_ms, [&]() { return conv(r, L, tx, ty, o); }));
+    OCRVI_TRY(k_nhwc_to_nchw_f32(dtype, yn, out, N, H, W, Co, Co, 0, sc.s));
+    OCRVI_HIP(hipStreamSynchronize(sc.s));
+    return OCRVI_OK;
+}
+
+// The DB head's tail (head.py:13-16 per branch: ConvTranspose2d(64,64,2,2) + BN + ReLU, ConvTranspose2d(64,1,2,2)) as det_model.hip builds and
+// launches it: both branches' first deconvolutions packed as ONE grouped pixel-shuffle GEMM (group 0 = binarise, 1 = threshold), the second
+// deconvolution's weights as [2][64][4] + 2 biases, the 64 -> 1 dot in the GEMM's epilogue.  groups = 2: the launch sees the whole pack,
+// x is [N, 128, OH, OW] (channels 0..63 feed group 0, 64..127 group 1, as the 256 -> 128 head conv leaves them); groups = 1: the launch
+// sees the one-group VIEW of the same pack that the binary-only forward takes (never a second pack), x is [N, 64, OH, OW].  binary_only:
+// ST_DB_BIN (out = sigmoid of group 0's logits) instead of ST_DB_TAIL (out, out2 = the two logit maps).  Which (store mode, groups, out2)
+// combinations are legal is launch_conv's to say: the hook hands them through.
+extern "C" int ocrvi_test_db_tail(int device, int dtype, const float* x, const float* dc1_w_bin_host, const float* dc1_b_bin_host,
+                                  const float* dc1_w_thr_host, const float* dc1_b_thr_host, const float* dc2_w_bin_host, const float* dc2_b_bin_host,
+                                  const float* dc2_w_thr_host, const float* dc2_b_thr_host, int N, int OH, int OW, int groups, int binary_only,
+                                  float* out, float* out2, int iters, float* avg_ms) {
+    OCRVI_CHECK(x && dc1_w_bin_host && dc1_b_bin_host && dc1_w_thr_host && dc1_b_thr_host && dc2_w_bin_host && dc2_b_bin_host && dc2_w_thr_host &&
+                    dc2_b_thr_host && out && N > 0 && OH > 0 && OW > 0 && dtype_valid(dtype),
+                OCRVI_EINVAL, "test_db_tail: bad argument");
+    OCRVI_CHECK(groups == 1 || groups == 2, OCRVI_EINVAL, "test_db_tail: groups = %d (2: the packed layer, 1: its binarise-branch view)", groups);
+    OCRVI_HIP(hipSetDevice(device));
+    Scratch sc;
+    OCRVI_TRY(sc.init());
+    DeviceStore st;
+    ConvLayer dc1;
+    float* dc2_wb = nullptr;
+    {   // det_model.hip, ocrvi_det_create: the head's deconvolutions
+        const float* dw[2] = {dc1_w_bin_host, dc1_w_thr_host};
+        const float* db[2] = {dc1_b_bin_host, dc1_b_thr_host};
+        PackedConv both = pack_deconv2(dw, db, 2, 64, 64, dtype);
+        OCRVI_TRY(upload_packed(st, both, AM_CONV1, &dc1));
+        dc1.shuffle_co = 64;
+        std::vector<float> w2(2 * 64 * 4);
+        std::copy(dc2_w_bin_host, dc2_w_bin_host + 256, w2.begin());
+        std::copy(dc2_w_thr_host, dc2_w_thr_host + 256, w2.begin() + 256);
+        w2.push_back(dc2_b_bin_host[0]);
+        w2.push_back(dc2_b_thr_host[0]);
+        OCRVI_TRY(st.upload_f32(w2, &dc2_wb));
+    }
+    ConvLayer L = dc1;
+    L.groups = groups;   // (1: det_run's `hdc`, the first group of the shared pack)
+    const int Cx = 64 * groups;
+    void* xn = nullptr;
+    OCRVI_TRY(sc.alloc((size_t)N * OH * OW * Cx * dtype_size(dtype), &xn));
+    OCRVI_TRY(to_nhwc(dtype, x, xn, N, Cx, OH * OW, sc.s));
+    Runner r(dtype, sc.s, (void*)256, 0);
+    Tensor tx; tx.p = xn; tx.n = N; tx.h = OH; tx.w = OW; tx.c = Cx;
+    Tensor lm; lm.p = out; lm.n = N; lm.h = 4 * OH; lm.w = 4 * OW; lm.c = 1; lm.f32 = true;
+    ConvOpts o;
+    o.store_mode = binary_only ? ST_DB_BIN : ST_DB_TAIL; o.out2 = binary_only ? nullptr : out2; o.offs = dc2_wb;
+    OCRVI_TRY(timed(sc, iters, avg_ms, [&]() { return conv(r, L, tx, lm, o); }));
     OCRVI_HIP(hipStreamSynchronize(sc.s));
     return OCRVI_OK;
 }

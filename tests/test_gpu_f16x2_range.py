@@ -203,9 +203,11 @@ def test_model_level_overflow_is_reported_not_swallowed():
 # packs |x| >= 65520; each writer carries its own copy of the check, and the pointer to the flag word is a per-translation-unit device
 # variable (a silent no-op in a unit that forgot OCRVI_RANGE_FLAG_TU()).  Per writer, with inputs that are themselves in range: the flag
 # stays 0 at ordinary scale, is 1 when the OUTPUT passes 65520 (activation x 2^10, weight x 2^7, as case (2) above), and stays 0 for the
-# same call in f32.  Not covered: the ring GEMM's 3x3 mode is 16-bit only (gemm_ring_eligible: esz == 2), so no f16x2 shape selects it;
-# conv_gemm's generic store4 path (RES_UP2 / pixel-shuffle stores, unaligned rows) cannot be reached through ocrvi_test_conv, whose buffers
-# are always 16-byte aligned rows -- it packs through common.h's store4, the check the cast and LayerNorm cases exercise.
+# same call in f32.  Not covered: the ring GEMM's 3x3 mode is 16-bit only (gemm_ring_eligible: esz == 2), so no f16x2 shape selects it.
+# conv_gemm's generic store4 path (RES_UP2 / pixel-shuffle stores, unaligned rows), which ocrvi_test_conv's 16-byte aligned rows never
+# take, is reached through ocrvi_test_conv_res with a half-resolution residual on a 1x1 whose 80 input channels keep it off the ring
+# (test_res_up2_output_overflow_raises_the_flag), and the ring GEMM's own RES_UP2 epilogue by the same call at 64 channels.
+from test_gpu_conv_epilogues import run_conv_res                     # noqa: E402
 from test_gpu_kernels import _run_dcn, _run_stem_pool, run_conv      # noqa: E402
 
 
@@ -238,6 +240,21 @@ def test_conv_gemm_output_overflow_raises_the_flag(case):
     w = torch.randn(Co, Cin // groups, ks, ks, generator=g) / np.sqrt(Cin // groups * ks * ks)
     b = torch.zeros(Co)
     _three_calls(lambda dt, sa, sw: run_conv(x * sa, w * sw, b, ks, st, st, groups, 0, dt))
+
+
+@pytest.mark.parametrize("case", [
+    # conv_gemm AM_CONV1, 128 x 128 tile, the generic per-lane store (RES_UP2 clears epi_lds): packs through common.h's store4
+    (3, 80, 10, 14, 256),
+    # the ring GEMM (128-row tiles) with the half-resolution residual read in load_group: its own f16x2 epilogue pack
+    (3, 64, 10, 14, 256),
+])
+def test_res_up2_output_overflow_raises_the_flag(case):
+    N, Cin, H, W, Co = case
+    g = torch.Generator().manual_seed(sum(case))
+    x = torch.randn(N, Cin, H, W, generator=g)
+    w = torch.randn(Co, Cin, 1, 1, generator=g) / np.sqrt(Cin)
+    res = torch.randn(N, Co, H // 2, W // 2, generator=g)          # in range at every scale: only the sum leaves it
+    _three_calls(lambda dt, sa, sw: run_conv_res(x * sa, w * sw, torch.zeros(Co), res, 1, 2, 0, dt))
 
 
 def test_conv3_halo_output_overflow_raises_the_flag():
