@@ -472,6 +472,66 @@ int ocrvi_db_boxes_batch_sparse(const uint32_t* mask_bits, const int32_t* comps,
                                 int32_t* rects, float* scores, int cap_per_page, int32_t* counts, int threads, int32_t* skipped);
 
 /* ------------------------------------------------------------------------------------------------
+ * DB ground truth: the reference's DetectionDataset without augmentation (src/det/dataloader.py:27-362, is_training=False, plus the
+ * threshold maps of is_training=True on request) -- `image`, `gt`, `mask`, `thresh_map`, `thresh_mask` from polygon annotations.
+ * The reference builds them on the host with shapely, pyclipper and cv2; here the polygon geometry runs on the host (Clipper's offset
+ * is host code in this library already) and every pixel is produced on the device.  Parity with GEOS, Clipper and cv2 is unpinned, as
+ * for the rest of the host geometry; tests/dbtarget_ref.py states the same path in Python and the library equals it exactly.
+ * ------------------------------------------------------------------------------------------------ */
+#define OCRVI_DB_TARGET_GT 0      /* fill gt with 1                                  (cv2.fillPoly(gt, [shrunk], 1.0), :342) */
+#define OCRVI_DB_TARGET_MASK 1    /* fill mask with 0                                (cv2.fillPoly(mask, [polygon], 0.0), :344) */
+#define OCRVI_DB_TARGET_THRESH 2  /* fill thresh_mask with 1, thresh_map with thresh_max  (_draw_border_map, :164-194) */
+#define OCRVI_DB_TARGET_JOB 8     /* int32 fields of a job: (image, kind, p0, p1, x0, y0, x1, y1): points p0 .. p1-1, their inclusive bounding box */
+#define OCRVI_DB_TARGET_MAX_SIDE 16384   /* largest image side and S: keeps every coordinate below 2^20, where the integer fill tests
+                                          * decide as the double arithmetic of the stated fill rule does */
+/* Replaces the polygon loop of _load_sample (dataloader.py:334-350) with _shrink_polygon (:71-102), _dilate_polygon (:104-133) and the
+ * gates of _draw_border_map (:139-161) for n_images images.  HOST code.  Inputs: sizes int32 [n_images][2] = (h, w); xy float32 (x, y)
+ * pairs of every vertex; polygon k owns vertices poly_offsets[k] .. poly_offsets[k+1]; image i owns polygons image_offsets[i] ..
+ * image_offsets[i+1] (both start at 0).  Coordinates must be finite; a polygon of fewer than 3 vertices is skipped (:320).
+ * Per polygon, in the reference's order:
+ *   1. clip to [0, w-1] x [0, h-1] in float32 (:336-337);
+ *   2. shapely is_valid / .area / .length on the FLOAT ring, stated here as: all in double without fused multiply-adds; consecutive
+ *      duplicate vertices are dropped, at least 3 must remain; a predicate is the sign of (bx-ax)(cy-ay) - (by-ay)(cx-ax); two edges
+ *      that are not neighbours may not share a point (touching counts), two neighbours may share only their common vertex (the ring is
+ *      simple); area = |sequential shoelace sum| / 2 and length = sequential sum of sqrt(dx dx + dy dy) over the ring as given;
+ *   3. `not valid or area < 1` or `length < 1` -> no shrunk polygon;
+ *   4. d = area * (1 - shrink_ratio^2) / length;  5. the vertices truncated (astype(int));
+ *   6. Execute(-d): the raw round-join offset path at -d, then EVERY outer loop of its positive-winding region (a shrink can fall apart);
+ *   7. no loop -> a MASK job with the truncated polygon;  8. else a GT job with the loop of largest signed area -- among equal areas
+ *      the loop whose smallest vertex (by x, then y) is smallest, then the first found;
+ *   9. with want_thresh, a valid polygon and d >= 1: Execute(+d) (ocrvi_unclip_polygon's routine) -> a THRESH job when it is not empty.
+ * A FINDING about the reference, reproduced and not corrected: _draw_border_map takes np.minimum(dist_inside, dist_outside) (:172-177),
+ * and one of the two is 0 at every pixel, so its threshold map is float32(thresh_max) over the whole dilated polygon and thresh_min is
+ * never used.  A THRESH job is therefore a plain fill; no distance transform is involved.
+ * Outputs: jobs int32 [cap_jobs][OCRVI_DB_TARGET_JOB] and points int32 [cap_points][2], image after image, polygon after polygon, the
+ * GT or MASK job of a polygon before its THRESH job; *n_jobs, *n_points = the room needed.  When either exceeds its capacity *overflow = 1
+ * and nothing is written (call again with that room), otherwise 0.  Nothing is ever truncated.  Images run on `threads` host threads,
+ * the pool of ocrvi_db_boxes_batch. */
+int ocrvi_db_target_jobs(const int32_t* sizes, const float* xy, const int32_t* poly_offsets, const int32_t* image_offsets, int n_images,
+                         double shrink_ratio, int want_thresh, int32_t* jobs, int cap_jobs, int32_t* points, int cap_points, int32_t* n_jobs,
+                         int32_t* n_points, int32_t* overflow, int threads);
+/* Replaces the four maps of _load_sample (:328-332, the cv2.fillPoly calls :342, :344, :164-194) after _resize_pad (:263-271).  jobs, points:
+ * DEVICE copies of ocrvi_db_target_jobs' output; rows DEVICE int32 [n][4] = (h, w, new_h, new_w) with (new_h, new_w) = (int(h * scale),
+ * int(w * scale)), scale = S / max(h, w) (:242-244).  Writes float32 [n,1,S,S]: gt = 0 with the GT fills, mask = 1 inside new_h x new_w with
+ * the MASK fills at 0, thresh_map / thresh_mask = 0 with the THRESH fills (thresh_max, 1); 0 in the pad.  A row with new_h <= 0 or
+ * new_w <= 0 gives four zero maps (the reference's _blank_sample: cv2.resize raises).
+ * The fill rule is this library's statement of cv2.fillPoly: the pixels of the 8-connected Bresenham line (cv::LineIterator) from vertex i
+ * to vertex i+1 of every edge, plus the even-odd interior at pixel centres with the half-open vertex rule (row y meets edge a-b when
+ * ay <= y < by or by <= y < ay; crossings sorted and paired; x filled for ceil(lo) <= x <= floor(hi)).  The maps are filled at h x w and then
+ * sampled as cv2.resize(INTER_NEAREST) does: output (X, Y) takes source (sx, sy), sx = min(floor(X * (1.0 / (new_w / w))), w - 1) in
+ * double, likewise sy (for scale == 1.0 that is the identity, the reference's copy).  Jobs may overlap and run in any order: every store
+ * to a map writes that map's constant.  A job whose image or point range is out of bounds is skipped.  Enqueue-only on `stream`, no
+ * allocation, no workspace. */
+int ocrvi_db_target_maps(int device, const int32_t* jobs, int n_jobs, const int32_t* points, int n_points, const int32_t* rows, int n, int S,
+                         float thresh_max, float* gt, float* mask, float* thresh_map, float* thresh_mask, void* stream);
+/* Replaces _resize_pad's image half (:240-261): page i of the page table (OCRVI_PAGE_ENTRY) resized to rows[i]'s (new_h, new_w) with
+ * ocrvi_resize_u8's arithmetic (the identity when the sizes agree: the scale == 1.0 branch), normalised in FLOAT32 -- ((v / 255) - mean)
+ * / std with float32 mean and std, every step rounded to float32 (:251-252), not the float64 form of ocrvi_normalize_u8 -- and
+ * zero-padded to S x S: out float32 [n,3,S,S].  An invalid page entry or a row with new_h <= 0 or new_w <= 0 gives zeros.
+ * Enqueue-only on `stream`. */
+int ocrvi_resize_normalize_pad_pages(int device, const int64_t* pages, const int32_t* rows, int n, int S, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Validation: the numbers the reference's two validation loops report (src/det/val.py, src/rec2/val.py) from maps, log-probs and ids
  * that stay on the device.  Forward values only: no backward pass, no SGM term (both are training).  All three
  * entries are enqueue-only on `stream`, allocate nothing and never synchronise; every pointer is DEVICE memory.

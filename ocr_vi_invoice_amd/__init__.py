@@ -2,7 +2,8 @@
 
 Importing the package is cheap and CPU-safe; ``DBNetPP`` / ``SVTRv2`` / ``Engine`` (batched OCR over pages of mixed sizes) load ``lib/libocrvi.so`` on first use and
 raise if it is missing (there is no CPU fallback).  ``DBLoss`` / ``SVTRv2Loss`` / ``compute_metrics`` / ``compute_cer`` / ``compute_acc`` /
-``validate_detection`` / ``validate_recognition`` (``val.py``) mirror the reference's validation loops on the device."""
+``validate_detection`` / ``validate_recognition`` (``val.py``) mirror the reference's validation loops on the device; ``DetectionDataset``
+(``data.py``) builds the detection batches they consume from polygon annotations."""
 from .vocab import VOCAB, Tokenizer  # noqa: F401
 
 
@@ -16,6 +17,9 @@ def __getattr__(name):
     if name == "Engine":
         from .engine import Engine
         return Engine
+    if name == "DetectionDataset":   # the reference's detection dataloader without augmentation: validation batches from polygons (data.py)
+        from .data import DetectionDataset
+        return DetectionDataset
     if name in _VAL_NAMES:      # validation: the reference's loss values, pixel metrics, CER and accuracy (val.py)
         from . import val
         return getattr(val, name)

@@ -37,6 +37,7 @@ EXPORTS = [
     "ocrvi_min_area_quads", "ocrvi_quad_crops", "ocrvi_crop_quad_resize_normalize_pages", "ocrvi_crop_quad_resize_normalize",
     "ocrvi_jpeg_info", "ocrvi_jpeg_parse", "ocrvi_jpeg_table_entry", "ocrvi_jpeg_decode_pages",
     "ocrvi_test_conv_res", "ocrvi_test_db_tail",
+    "ocrvi_db_target_jobs", "ocrvi_db_target_maps", "ocrvi_resize_normalize_pad_pages",
 ]
 PAGE_ENTRY = 4          # int64 fields of one page-table entry: (device address, height, width, 0) -- OCRVI_PAGE_ENTRY
 # ocrvi_det_eval's record: 13 slots of 8 bytes (OCRVI_DET_EVAL_*), the first six int64, the rest float64
@@ -47,6 +48,9 @@ CTC_LOSS_MAX_TARGET = 1024      # OCRVI_CTC_LOSS_MAX_TARGET
 EDIT_DISTANCE_MAX_LEN = 2048    # OCRVI_EDIT_DISTANCE_MAX_LEN
 CLAHE_WORKSPACE_BYTES = 16384   # OCRVI_CLAHE_WORKSPACE_BYTES
 ENHANCE_MIN_SIDE = 16           # the smallest page side the enhance entries take
+DB_TARGET_GT, DB_TARGET_MASK, DB_TARGET_THRESH = 0, 1, 2   # OCRVI_DB_TARGET_*: the map a fill job writes
+DB_TARGET_JOB = 8               # int32 fields of one fill job -- OCRVI_DB_TARGET_JOB
+DB_TARGET_MAX_SIDE = 16384      # OCRVI_DB_TARGET_MAX_SIDE
 JPEG_ENTRY = 64                 # int64 fields of one ocrvi_jpeg_decode_pages table entry -- OCRVI_JPEG_ENTRY
 
 
@@ -162,6 +166,10 @@ def load() -> C.CDLL:
     lib.ocrvi_jpeg_parse.argtypes = [vp, sz, vp, sz, C.POINTER(sz)]
     lib.ocrvi_jpeg_table_entry.argtypes = [C.POINTER(JpegInfo), sz, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp]
     lib.ocrvi_jpeg_decode_pages.argtypes = [i32, vp, vp, i32, vp, vp, sz, vp]
+    lib.ocrvi_db_target_jobs.argtypes = [vp, vp, vp, vp, i32, C.c_double, i32, vp, i32, vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int32), i32]
+    lib.ocrvi_db_target_maps.argtypes = [i32, vp, i32, vp, i32, vp, i32, i32, C.c_float, f32p, f32p, f32p, f32p, vp]
+    lib.ocrvi_resize_normalize_pad_pages.argtypes = [i32, vp, vp, i32, i32, f32p, vp]
     lib.ocrvi_det_status.argtypes = [vp]
     lib.ocrvi_rec_status.argtypes = [vp]
     lib.ocrvi_range_reset.argtypes = [i32, vp]

@@ -142,9 +142,14 @@ struct VtxLess {
 
 struct Half { int u, v, mult, dx, dy, seg, twin, face, pos; bool boundary; };
 
-// Outer polygon of Clipper's ctUnion / pftPositive of one closed integer path
-inline void union_outline(const std::vector<P2>& path, std::vector<P2>& out) {
-    out.clear();
+// One boundary loop of the positive-winding region (interior on its left), crossing points already rounded as Clipper rounds them, before
+// FixupOutPolygon; `lo` is its left-most (then lowest) vertex in exact coordinates
+struct BoundaryLoop { std::vector<P2> outline; Vtx lo; };
+
+// Every boundary loop of the region of one closed integer path whose winding number is positive: outer loops and the loops around enclosed
+// pockets alike, in the order their first half-edge was created
+inline void union_boundary_loops(const std::vector<P2>& path, std::vector<BoundaryLoop>& loops) {
+    loops.clear();
     std::vector<P2> P = path;
     addpath_cleanup(P);
     const int n = (int)P.size();
@@ -277,8 +282,7 @@ inline void union_outline(const std::vector<P2>& path, std::vector<P2>& out) {
     // boundary loops (interior on the left): at a vertex the next boundary edge is the first one counter-clockwise from the way back;
     // the outer loop is the one through the left-most boundary vertex
     std::vector<char> seen(nh, 0);
-    std::vector<int> best, loop;
-    int best_lo = -1;
+    std::vector<int> loop;
     for (int s = 0; s < nh; ++s) {
         if (!he[s].boundary || seen[s]) continue;
         loop.clear();
@@ -294,18 +298,112 @@ inline void union_outline(const std::vector<P2>& path, std::vector<P2>& out) {
         int lo = he[loop[0]].u;
         for (int g : loop)
             if (VtxLess()(vpt[he[g].u], vpt[lo])) lo = he[g].u;
-        if (best_lo < 0 || VtxLess()(vpt[lo], vpt[best_lo])) { best_lo = lo; best = loop; }
+        loops.emplace_back();
+        loops.back().lo = vpt[lo];
+        std::vector<P2>& outline = loops.back().outline;
+        for (size_t k = 0; k < loop.size(); ++k) {  // vertex u of edge k: reached on the previous edge, left on this one
+            const Half& cur = he[loop[k]];
+            const Half& prv = he[loop[(k + loop.size() - 1) % loop.size()]];
+            const Vtx& p = vpt[cur.u];
+            if (p.d == 1) outline.push_back({(int)p.xn, (int)p.yn});
+            else outline.push_back(clipper_intersect_point(A(prv.seg), B(prv.seg), A(cur.seg), B(cur.seg)));
+        }
     }
-    if (best.empty()) return;
-    std::vector<P2> outline;
-    for (size_t k = 0; k < best.size(); ++k) {  // vertex u of edge k: reached on the previous edge, left on this one
-        const Half& cur = he[best[k]];
-        const Half& prv = he[best[(k + best.size() - 1) % best.size()]];
-        const Vtx& p = vpt[cur.u];
-        if (p.d == 1) outline.push_back({(int)p.xn, (int)p.yn});
-        else outline.push_back(clipper_intersect_point(A(prv.seg), B(prv.seg), A(cur.seg), B(cur.seg)));
+}
+
+// Outer polygon of Clipper's ctUnion / pftPositive of one closed integer path: the loop through the left-most boundary vertex
+inline void union_outline(const std::vector<P2>& path, std::vector<P2>& out) {
+    out.clear();
+    std::vector<BoundaryLoop> loops;
+    union_boundary_loops(path, loops);
+    const BoundaryLoop* best = nullptr;
+    for (const BoundaryLoop& l : loops)
+        if (!best || VtxLess()(l.lo, best->lo)) best = &l;
+    if (best) fixup_and_emit(best->outline, out);
+}
+
+inline i64 signed_area2(const std::vector<P2>& p) {  // twice ClipperLib::Area: positive for an outer path
+    i64 a2 = 0;
+    for (size_t i = 0, n = p.size(); i < n; ++i) a2 += (i64)p[i].x * p[(i + 1) % n].y - (i64)p[(i + 1) % n].x * p[i].y;
+    return a2;
+}
+
+// ClipperOffset::Execute with a NEGATIVE delta closes with a union against a surrounding rectangle under pftNegative and drops the
+// rectangle: what is left are the outlines of the region where the raw path winds positively.  A shrink can fall apart, so that region
+// may have several components: every outer loop is returned (positive area after FixupOutPolygon; the loops around enclosed pockets have
+// negative area and are left out, as max(paths, key=Area) never picks one).  As for union_outline, the cyclic vertex sequence of each
+// loop is what is claimed.
+inline void union_outer_loops(const std::vector<P2>& path, std::vector<std::vector<P2>>& out) {
+    out.clear();
+    std::vector<BoundaryLoop> loops;
+    union_boundary_loops(path, loops);
+    std::vector<P2> poly;
+    for (const BoundaryLoop& l : loops) {
+        fixup_and_emit(l.outline, poly);
+        if (poly.size() >= 3 && signed_area2(poly) > 0) out.push_back(poly);
     }
-    fixup_and_emit(outline, out);
+}
+
+// pyclipper.PyclipperOffset().AddPath(box, JT_ROUND, ET_CLOSEDPOLYGON); Execute(delta), first half: the raw offset path (Clipper 6.4.2
+// DoOffset / OffsetPoint / DoRound, arc tolerance 0.25).  delta < 0 shrinks.  Execute's closing union is union_outline (delta > 0) or
+// union_outer_loops (delta < 0).
+inline void offset_round(const std::vector<P2>& in, double delta, std::vector<P2>& out) {
+    out.clear();
+    if (in.empty()) return;
+    std::vector<P2> q;
+    q.push_back(in[0]);
+    for (size_t i = 1; i < in.size(); ++i)
+        if (in[i].x != q.back().x || in[i].y != q.back().y) q.push_back(in[i]);
+    if (q.size() > 1 && q.back().x == q[0].x && q.back().y == q[0].y) q.pop_back();
+    const int n = (int)q.size();
+    if (n < 3) return;
+    if (signed_area2(q) < 0) std::reverse(q.begin(), q.end());   // FixOrientations: outer paths must have positive area
+    const double pi = 3.14159265358979323846;
+    double y = 0.25;
+    if (y > fabs(delta) * 0.25) y = fabs(delta) * 0.25;
+    double steps = pi / acos(1 - y / fabs(delta));
+    if (steps > fabs(delta) * pi) steps = fabs(delta) * pi;
+    double m_sin = sin(2 * pi / steps);
+    const double m_cos = cos(2 * pi / steps), steps_per_rad = steps / (2 * pi);
+    if (delta < 0) m_sin = -m_sin;
+    std::vector<double> nx(n), ny(n);
+    for (int j = 0; j < n; ++j) {
+        const double dx = (double)(q[(j + 1) % n].x - q[j].x), dy = (double)(q[(j + 1) % n].y - q[j].y);
+        const double f = 1.0 / sqrt(dx * dx + dy * dy);
+        nx[j] = dy * f;
+        ny[j] = -dx * f;
+    }
+    auto push = [&](double px, double py) { out.push_back({(int)cround(px), (int)cround(py)}); };
+    int k = n - 1;
+    for (int j = 0; j < n; ++j) {
+        const double sx = q[j].x, sy = q[j].y;
+        double sin_a = nx[k] * ny[j] - nx[j] * ny[k];
+        if (fabs(sin_a * delta) < 1.0) {
+            const double cos_a = nx[k] * nx[j] + ny[j] * ny[k];
+            if (cos_a > 0) {  // (almost) straight: one point; Clipper returns here WITHOUT advancing k
+                push(sx + nx[k] * delta, sy + ny[k] * delta);
+                continue;
+            }
+        } else if (sin_a > 1.0) sin_a = 1.0;
+        else if (sin_a < -1.0) sin_a = -1.0;
+        if (sin_a * delta < 0) {
+            push(sx + nx[k] * delta, sy + ny[k] * delta);
+            out.push_back(q[j]);
+            push(sx + nx[j] * delta, sy + ny[j] * delta);
+        } else {
+            const double a = atan2(sin_a, nx[k] * nx[j] + ny[k] * ny[j]);
+            const int st = std::max((int)cround(steps_per_rad * fabs(a)), 1);
+            double X = nx[k], Y = ny[k];
+            for (int i = 0; i < st; ++i) {
+                push(sx + X * delta, sy + Y * delta);
+                const double X2 = X;
+                X = X * m_cos - m_sin * Y;
+                Y = X2 * m_sin + Y * m_cos;
+            }
+            push(sx + nx[j] * delta, sy + ny[j] * delta);
+        }
+        k = j;
+    }
 }
 
 }  // namespace clipu

@@ -8,12 +8,14 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <mutex>
 #include <thread>
 #include <vector>
 
 #include "clip_union.h"
 #include "common.h"
+#include "db_target_geom.h"
 
 namespace {
 
@@ -280,77 +282,11 @@ double box_score(const float* prob, int H, int W, const std::vector<Pt>& box) {
     return cnt ? sum / (double)cnt : 0.0;
 }
 
-inline long long cround(double v) { return v < 0 ? (long long)(v - 0.5) : (long long)(v + 0.5); }  // ClipperLib::Round
-
-// pyclipper.PyclipperOffset().AddPath(box, JT_ROUND, ET_CLOSEDPOLYGON); Execute(delta), first half: the raw offset path (Clipper 6.4.2
-// DoOffset / OffsetPoint / DoRound, arc tolerance 0.25).  Execute's closing self-union is unclip_polygon() below.
-void clipper_offset_round(const std::vector<Pt>& in, double delta, std::vector<Pt>& out) {
-    out.clear();
-    if (in.empty()) return;
-    std::vector<Pt> q;
-    q.push_back(in[0]);
-    for (size_t i = 1; i < in.size(); ++i)
-        if (in[i].x != q.back().x || in[i].y != q.back().y) q.push_back(in[i]);
-    if (q.size() > 1 && q.back().x == q[0].x && q.back().y == q[0].y) q.pop_back();
-    const int n = (int)q.size();
-    if (n < 3) return;
-    long long a2 = 0;
-    for (int i = 0; i < n; ++i) a2 += (long long)q[i].x * q[(i + 1) % n].y - (long long)q[(i + 1) % n].x * q[i].y;
-    if (a2 < 0) std::reverse(q.begin(), q.end());   // FixOrientations: outer paths must have positive area
-    const double pi = 3.14159265358979323846;
-    double y = 0.25;
-    if (y > fabs(delta) * 0.25) y = fabs(delta) * 0.25;
-    double steps = pi / acos(1 - y / fabs(delta));
-    if (steps > fabs(delta) * pi) steps = fabs(delta) * pi;
-    double m_sin = sin(2 * pi / steps);
-    const double m_cos = cos(2 * pi / steps), steps_per_rad = steps / (2 * pi);
-    if (delta < 0) m_sin = -m_sin;
-    std::vector<double> nx(n), ny(n);
-    for (int j = 0; j < n; ++j) {
-        const double dx = (double)(q[(j + 1) % n].x - q[j].x), dy = (double)(q[(j + 1) % n].y - q[j].y);
-        const double f = 1.0 / sqrt(dx * dx + dy * dy);
-        nx[j] = dy * f;
-        ny[j] = -dx * f;
-    }
-    auto push = [&](double px, double py) { out.push_back({(int)cround(px), (int)cround(py)}); };
-    int k = n - 1;
-    for (int j = 0; j < n; ++j) {
-        const double sx = q[j].x, sy = q[j].y;
-        double sin_a = nx[k] * ny[j] - nx[j] * ny[k];
-        if (fabs(sin_a * delta) < 1.0) {
-            const double cos_a = nx[k] * nx[j] + ny[j] * ny[k];
-            if (cos_a > 0) {  // (almost) straight: one point; Clipper returns here WITHOUT advancing k
-                push(sx + nx[k] * delta, sy + ny[k] * delta);
-                continue;
-            }
-        } else if (sin_a > 1.0) sin_a = 1.0;
-        else if (sin_a < -1.0) sin_a = -1.0;
-        if (sin_a * delta < 0) {
-            push(sx + nx[k] * delta, sy + ny[k] * delta);
-            out.push_back(q[j]);
-            push(sx + nx[j] * delta, sy + ny[j] * delta);
-        } else {
-            const double a = atan2(sin_a, nx[k] * nx[j] + ny[k] * ny[j]);
-            const int st = std::max((int)cround(steps_per_rad * fabs(a)), 1);
-            double X = nx[k], Y = ny[k];
-            for (int i = 0; i < st; ++i) {
-                push(sx + X * delta, sy + Y * delta);
-                const double X2 = X;
-                X = X * m_cos - m_sin * Y;
-                Y = X2 * m_sin + Y * m_cos;
-            }
-            push(sx + nx[j] * delta, sy + ny[j] * delta);
-        }
-        k = j;
-    }
-}
-
 // unclip (src/det/test.py:37-43) for a given distance: raw offset path -> Clipper's closing union (clip_union.h) -> its outer polygon
 void unclip_polygon(const std::vector<Pt>& in, double delta, std::vector<Pt>& out) {
-    std::vector<Pt> raw;
-    clipper_offset_round(in, delta, raw);
-    std::vector<clipu::P2> path(raw.size()), outline;
-    for (size_t i = 0; i < raw.size(); ++i) path[i] = {raw[i].x, raw[i].y};
+    std::vector<clipu::P2> src(in.size()), path, outline;
+    for (size_t i = 0; i < in.size(); ++i) src[i] = {in[i].x, in[i].y};
+    clipu::offset_round(src, delta, path);
     clipu::union_outline(path, outline);
     out.resize(outline.size());
     for (size_t i = 0; i < outline.size(); ++i) out[i] = {outline[i].x, outline[i].y};
@@ -572,4 +508,60 @@ extern "C" int ocrvi_db_boxes_batch_sparse(const uint32_t* mask_bits, const int3
     auto geom = [&](int pg) { return PageGeom{scale_w, scale_h, orig_h, orig_w, page_base + pg}; };
     return boxes_batch_impl(page, geom, n_pages, H, W, 0.f, box_thresh, max_candidates, unclip_ratio, min_area, rects, scores, cap_per_page, counts,
                             threads, skipped);
+}
+
+// ---------------------------------------------------------------- DB ground-truth fill jobs (db_target_geom.h; include/ocrvi.h "DB ground truth")
+extern "C" int ocrvi_db_target_jobs(const int32_t* sizes, const float* xy, const int32_t* poly_offsets, const int32_t* image_offsets, int n_images,
+                                    double shrink_ratio, int want_thresh, int32_t* jobs, int cap_jobs, int32_t* points, int cap_points,
+                                    int32_t* n_jobs, int32_t* n_points, int32_t* overflow, int threads) {
+    using namespace ocrvi;
+    OCRVI_CHECK(sizes && poly_offsets && image_offsets && jobs && points && n_jobs && n_points && overflow && n_images > 0 && cap_jobs >= 0 &&
+                    cap_points >= 0 && shrink_ratio > 0 && shrink_ratio < 1,
+                OCRVI_EINVAL, "db_target_jobs: bad argument (0 < shrink_ratio < 1)");
+    OCRVI_CHECK(image_offsets[0] == 0 && poly_offsets[0] == 0, OCRVI_EINVAL, "db_target_jobs: offsets must start at 0");
+    for (int i = 0; i < n_images; ++i) {
+        OCRVI_CHECK(sizes[2 * i] >= 1 && sizes[2 * i] <= OCRVI_DB_TARGET_MAX_SIDE && sizes[2 * i + 1] >= 1 && sizes[2 * i + 1] <= OCRVI_DB_TARGET_MAX_SIDE,
+                    OCRVI_EINVAL, "db_target_jobs: image %d is %d x %d (sides 1 .. %d)", i, sizes[2 * i], sizes[2 * i + 1], OCRVI_DB_TARGET_MAX_SIDE);
+        OCRVI_CHECK(image_offsets[i + 1] >= image_offsets[i], OCRVI_EINVAL, "db_target_jobs: image_offsets decrease at %d", i);
+    }
+    const int n_poly = image_offsets[n_images];
+    for (int k = 0; k < n_poly; ++k) OCRVI_CHECK(poly_offsets[k + 1] >= poly_offsets[k], OCRVI_EINVAL, "db_target_jobs: poly_offsets decrease at %d", k);
+    const int n_vtx = poly_offsets[n_poly];
+    OCRVI_CHECK(n_vtx == 0 || xy, OCRVI_EINVAL, "db_target_jobs: null coordinates");
+    for (int i = 0; i < 2 * n_vtx; ++i) OCRVI_CHECK(std::isfinite(xy[i]), OCRVI_EINVAL, "db_target_jobs: coordinate %d is not finite", i);
+    std::lock_guard<std::mutex> lk(g_batch_mu);
+    std::vector<dbtarget::ImageJobs> per(n_images);
+    std::atomic<int> next(0);
+    auto work = [&]() {
+        for (;;) {
+            const int i = next.fetch_add(1);
+            if (i >= n_images) break;
+            dbtarget::image_jobs(i, sizes[2 * i], sizes[2 * i + 1], xy, poly_offsets + image_offsets[i], image_offsets[i + 1] - image_offsets[i],
+                                 shrink_ratio, want_thresh != 0, per[i]);
+        }
+    };
+    const int nt = std::max(1, std::min(threads, n_images));
+    std::vector<std::thread> pool;
+    for (int t = 1; t < nt; ++t) pool.emplace_back(work);
+    work();
+    for (auto& t : pool) t.join();
+    long long nj = 0, np = 0;
+    for (const auto& im : per) { nj += (long long)im.jobs.size() / dbtarget::kJobInts; np += (long long)im.points.size() / 2; }
+    OCRVI_CHECK(nj <= INT32_MAX && np <= INT32_MAX, OCRVI_EINVAL, "db_target_jobs: %lld jobs, %lld points do not fit an int32", nj, np);
+    *n_jobs = (int32_t)nj;
+    *n_points = (int32_t)np;
+    *overflow = (nj > cap_jobs || np > cap_points) ? 1 : 0;
+    if (*overflow) return OCRVI_OK;   // the room needed is reported; nothing is written, nothing is truncated
+    int32_t jb = 0, pb = 0;
+    for (const auto& im : per) {
+        const int m = (int)im.jobs.size() / dbtarget::kJobInts;
+        for (int j = 0; j < m; ++j) {
+            int32_t* row = jobs + (size_t)(jb + j) * dbtarget::kJobInts;
+            memcpy(row, im.jobs.data() + (size_t)j * dbtarget::kJobInts, sizeof(int32_t) * dbtarget::kJobInts);
+            row[2] += pb; row[3] += pb;
+        }
+        if (!im.points.empty()) memcpy(points + 2 * (size_t)pb, im.points.data(), sizeof(int32_t) * im.points.size());
+        jb += m; pb += (int32_t)im.points.size() / 2;
+    }
+    return OCRVI_OK;
 }

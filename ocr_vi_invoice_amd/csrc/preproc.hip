@@ -204,6 +204,33 @@ __global__ void resize_normalize_pages_kernel(const int64_t* __restrict__ table,
     }
 }
 
+// DetectionDataset._resize_pad's image half (src/det/dataloader.py:240-261): page i resized to its own new_h x new_w (rows int32 [n][4] =
+// (h, w, new_h, new_w), the row ocrvi_db_target_maps reads) with resize_u8_kernel's arithmetic -- a resize to the page's own size is the
+// identity there, which is the reference's scale == 1.0 branch --, normalised in FLOAT32 ((v / 255 - mean) / std, every step rounded), then
+// zero-padded to S x S.  One thread per output pixel: the pad and an invalid page are stores without a read.
+__global__ void resize_normalize_pad_pages_kernel(const int64_t* __restrict__ table, const int32_t* __restrict__ rows, int n, int S,
+                                                  float* __restrict__ out) {
+    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
+    const size_t plane = (size_t)S * S, total = (size_t)n * plane;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int pg = (int)(i / plane);
+        const size_t r = i - (size_t)pg * plane;
+        const int y = (int)(r / S), x = (int)(r - (size_t)y * S);
+        const PageRef src = load_page(table, pg);
+        const int nh = min(rows[4 * pg + 2], S), nw = min(rows[4 * pg + 3], S);
+        float f[3] = {0.f, 0.f, 0.f};
+        if (src.h != 0 && x < nw && y < nh) {
+            int v[3];
+            resized_px(src.p, src.h, src.w, nh, nw, x, axis_coef(y, src.h, nh), y, src.w == 2 * nw && src.h == 2 * nh, v);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) f[c] = ((float)v[c] / 255.0f - mean[c]) / stdv[c];
+        }
+        float* o = out + (size_t)pg * 3 * plane + r;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[(size_t)c * plane] = f[c];
+    }
+}
+
 // crop_resize_normalize_kernel with each rectangle's page taken from the page table: boxes int32 [B,5] = (table index, x, y, w, h)
 __global__ void crop_resize_normalize_pages_kernel(const int64_t* __restrict__ table, int n_pages, const int32_t* __restrict__ boxes, int B,
                                                    int oh, int ow, float* __restrict__ out) {
@@ -615,6 +642,18 @@ extern "C" int ocrvi_resize_normalize_pages(int device, const int64_t* pages, in
     const size_t total = (size_t)n * H * (W / 4);
     const int grid = (int)std::min<size_t>((total + 255) / 256, 16384);
     hipLaunchKernelGGL(resize_normalize_pages_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, pages, n, H, W, out);
+    OCRVI_HIP(hipGetLastError());
+    return OCRVI_OK;
+}
+
+extern "C" int ocrvi_resize_normalize_pad_pages(int device, const int64_t* pages, const int32_t* rows, int n, int S, float* out, void* stream) {
+    OCRVI_CHECK(pages && rows && out && n > 0 && S > 0, OCRVI_EINVAL, "resize_normalize_pad_pages: bad argument");
+    DeviceGuard dg(device);  // the caller's current device is restored on return
+    OCRVI_HIP(dg.err);
+    const size_t total = (size_t)n * S * S;
+    const int grid = (int)std::min<size_t>((total + 255) / 256, 16384);
+    ProfScope ps("resize_normalize_pad", 0.0, 12.0 * total, (hipStream_t)stream);
+    hipLaunchKernelGGL(resize_normalize_pad_pages_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, pages, rows, n, S, out);
     OCRVI_HIP(hipGetLastError());
     return OCRVI_OK;
 }
