@@ -683,6 +683,12 @@ int ocrvi_test_attention(int device, int dtype, const float* qkv, int B, int N, 
 int ocrvi_test_mlp(int device, int dtype, float* x, const float* ln_g_host, const float* ln_b_host, const float* w1_host, const float* b1_host,
                    const float* w2_host, const float* b2_host, const float* next_g_host, const float* next_b_host, int want_xn, int M, int D,
                    float* xn_out, int iters, float* avg_ms);
+/* The same call with the xn buffer owned by the caller: xn_raw is a DEVICE buffer of at least M rows of D * (element size of `dtype`) bytes that
+ * the kernel writes directly (the caller pre-fills it, and any rows past M, and reads the bytes back); only its first M rows are converted to
+ * xn_out [M][D] float32 DEVICE (may be NULL).  xn is always produced.  x may likewise be longer than M rows: rows past M are not touched. */
+int ocrvi_test_mlp_raw(int device, int dtype, float* x, const float* ln_g_host, const float* ln_b_host, const float* w1_host, const float* b1_host,
+                       const float* w2_host, const float* b2_host, const float* next_g_host, const float* next_b_host, int M, int D, void* xn_raw,
+                       float* xn_out, int iters, float* avg_ms);
 /* Host-only (no GPU): the OCRVI_F16X2 weight format.  src: n fp32 values of one layer (n % 4 == 0) -> dst: n 4-byte elements, per chunk of
  * 4 consecutive elements [hi0 hi1 hi2 hi3 | lo0 lo1 lo2 lo3] (fp16), hi + lo = src * 2^s with one power of two s per layer that puts the
  * largest magnitude into [2^13, 2^14); *wscale = 2^-s.  (What ocrvi_*_create does to every GEMM weight in that mode.) */

@@ -38,6 +38,7 @@ EXPORTS = [
     "ocrvi_jpeg_info", "ocrvi_jpeg_parse", "ocrvi_jpeg_table_entry", "ocrvi_jpeg_decode_pages",
     "ocrvi_test_conv_res", "ocrvi_test_db_tail",
     "ocrvi_db_target_jobs", "ocrvi_db_target_maps", "ocrvi_resize_normalize_pad_pages",
+    "ocrvi_test_mlp_raw",
 ]
 PAGE_ENTRY = 4          # int64 fields of one page-table entry: (device address, height, width, 0) -- OCRVI_PAGE_ENTRY
 # ocrvi_det_eval's record: 13 slots of 8 bytes (OCRVI_DET_EVAL_*), the first six int64, the rest float64
@@ -140,6 +141,7 @@ def load() -> C.CDLL:
     lib.ocrvi_test_stem_pool.argtypes = [i32, i32, f32p, vp, vp, i32, i32, i32, i32, f32p, i32, C.POINTER(C.c_float)]
     lib.ocrvi_test_attention.argtypes = [i32, i32, f32p, i32, i32, i32, f32p, i32, C.POINTER(C.c_float)]
     lib.ocrvi_test_mlp.argtypes = [i32, i32, f32p, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32p, i32, C.POINTER(C.c_float)]
+    lib.ocrvi_test_mlp_raw.argtypes = [i32, i32, f32p, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, f32p, i32, C.POINTER(C.c_float)]
     lib.ocrvi_test_pack_f16x2.argtypes = [f32p, sz, vp, C.POINTER(C.c_float)]
     lib.ocrvi_test_layernorm.argtypes = [i32, i32, f32p, i32, i32, vp, vp, i32, i32, f32p]
     lib.ocrvi_test_frm_vertical.argtypes = [i32, i32, f32p, vp, i32, i32, i32, i32, f32p]

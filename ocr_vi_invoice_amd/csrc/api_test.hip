@@ -385,11 +385,13 @@ extern "C" int ocrvi_test_attention(int device, int dtype, const float* qkv, int
     return OCRVI_OK;
 }
 
-extern "C" int ocrvi_test_mlp(int device, int dtype, float* x, const float* ln_g_host, const float* ln_b_host, const float* w1_host, const float* b1_host,
-                              const float* w2_host, const float* b2_host, const float* next_g_host, const float* next_b_host, int want_xn, int M, int D,
-                              float* xn_out, int iters, float* avg_ms) {
+namespace {
+// xn_raw: the caller's own device xn buffer ([>= M][D] of `dtype`, ocrvi_test_mlp_raw), or null for one of exactly M rows allocated here
+int test_mlp_impl(int device, int dtype, float* x, const float* ln_g_host, const float* ln_b_host, const float* w1_host, const float* b1_host,
+                  const float* w2_host, const float* b2_host, const float* next_g_host, const float* next_b_host, int want_xn, int M, int D,
+                  void* xn_raw, float* xn_out, int iters, float* avg_ms) {
     OCRVI_CHECK(x && ln_g_host && ln_b_host && w1_host && b1_host && w2_host && b2_host && M > 0, OCRVI_EINVAL, "test_mlp: bad argument");
-    OCRVI_CHECK(mlp_fused_eligible(dtype, D), OCRVI_EINVAL, "test_mlp: the fused MLP needs a 16-bit dtype and D in {128, 256, 384}, or f16x2 and D in {128, 256} (got dtype %d, D %d)", dtype, D);
+    OCRVI_CHECK(mlp_fused_eligible(dtype, D), OCRVI_EINVAL, "test_mlp: the fused MLP needs bf16, f16 or f16x2 and D in {128, 256, 384} (got dtype %d, D %d)", dtype, D);
     OCRVI_HIP(hipSetDevice(device));
     Scratch sc;
     OCRVI_TRY(sc.init());
@@ -407,8 +409,8 @@ extern "C" int ocrvi_test_mlp(int device, int dtype, float* x, const float* ln_g
         OCRVI_TRY(st.upload(next_g_host, (size_t)D * 4, (void**)&ng));
         OCRVI_TRY(st.upload(next_b_host, (size_t)D * 4, (void**)&nb));
     }
-    void *xn = nullptr, *x0 = nullptr;
-    if (want_xn) OCRVI_TRY(sc.alloc((size_t)M * D * dtype_size(dtype), &xn));
+    void *xn = xn_raw, *x0 = nullptr;
+    if (want_xn && !xn) OCRVI_TRY(sc.alloc((size_t)M * D * dtype_size(dtype), &xn));
     OCRVI_TRY(sc.alloc((size_t)M * D * 4, &x0));   // the kernel updates x in place: every timed repeat starts from the caller's x
     OCRVI_HIP(hipMemcpyAsync(x0, x, (size_t)M * D * 4, hipMemcpyDeviceToDevice, sc.s));
     OCRVI_TRY(timed(sc, iters, avg_ms, [&]() {
@@ -419,6 +421,22 @@ extern "C" int ocrvi_test_mlp(int device, int dtype, float* x, const float* ln_g
     if (want_xn && xn_out) OCRVI_TRY(k_nhwc_to_nchw_f32(dtype, xn, xn_out, 1, 1, M * D, 1, 1, 0, sc.s));
     OCRVI_HIP(hipStreamSynchronize(sc.s));
     return OCRVI_OK;
+}
+}  // namespace
+
+extern "C" int ocrvi_test_mlp(int device, int dtype, float* x, const float* ln_g_host, const float* ln_b_host, const float* w1_host, const float* b1_host,
+                              const float* w2_host, const float* b2_host, const float* next_g_host, const float* next_b_host, int want_xn, int M, int D,
+                              float* xn_out, int iters, float* avg_ms) {
+    return test_mlp_impl(device, dtype, x, ln_g_host, ln_b_host, w1_host, b1_host, w2_host, b2_host, next_g_host, next_b_host, want_xn, M, D, nullptr,
+                         xn_out, iters, avg_ms);
+}
+
+extern "C" int ocrvi_test_mlp_raw(int device, int dtype, float* x, const float* ln_g_host, const float* ln_b_host, const float* w1_host,
+                                  const float* b1_host, const float* w2_host, const float* b2_host, const float* next_g_host, const float* next_b_host,
+                                  int M, int D, void* xn_raw, float* xn_out, int iters, float* avg_ms) {
+    OCRVI_CHECK(xn_raw, OCRVI_EINVAL, "test_mlp_raw: xn_raw is null");
+    return test_mlp_impl(device, dtype, x, ln_g_host, ln_b_host, w1_host, b1_host, w2_host, b2_host, next_g_host, next_b_host, 1, M, D, xn_raw, xn_out,
+                         iters, avg_ms);
 }
 
 // ---- the memory-bound kernels of kernels.hip, one hook each (no timing arguments: nothing benchmarks these)
