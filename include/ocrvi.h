@@ -649,6 +649,13 @@ int ocrvi_test_conv(int device, int dtype, const float* x, const float* weight_h
  * res is converted to NHWC in the compute type exactly as x is.  Same conventions as ocrvi_test_conv. */
 int ocrvi_test_conv_res(int device, int dtype, const float* x, const float* weight_host, const float* bias_host, const float* res, int N,
                         int C, int H, int W, int Co, int ksize, int res_mode, int act, float* out, int iters, float* avg_ms);
+/* The fused ResNet-50 layer1 chain of the f16x2 detector (csrc/bneck_tail.h) as ONE launch: conv2 3x3 64->64 + ReLU, conv3 1x1 64->256 +
+ * identity + ReLU -> y_out, and (no_phase_c = 0) the next block's conv1 1x1 256->64 + ReLU -> t1n_out.  t1: float32 NCHW device [N,64,H,W];
+ * identity: [N,256,H,W]; y_out: [N,256,H,W]; t1n_out: [N,64,H,W] (ignored with no_phase_c = 1, as are w1_host / b1_host).  Host weights:
+ * w2 [64][64][3][3], w3 [256][64], w1 [64][256]; biases [64] / [256] / [64] or NULL.  Same conventions as ocrvi_test_conv. */
+int ocrvi_test_bneck_tail(int device, const float* t1, const float* identity, const float* w2_host, const float* b2_host,
+                          const float* w3_host, const float* b3_host, const float* w1_host, const float* b1_host, int N, int H, int W,
+                          int no_phase_c, float* y_out, float* t1n_out, int iters, float* avg_ms);
 /* The DB head's two deconvolutions (head.py:13-16) as the detector runs them: ConvTranspose2d(64,64,2,2) + folded BN + ReLU of both
  * branches packed as one grouped GEMM (group 0 = binarise, 1 = threshold), ConvTranspose2d(64,1,2,2) in its epilogue.  dc1_w_*: host
  * [64][64][2][2] (c_in, c_out, a, b), dc1_b_*: host [64], dc2_w_*: host [64][1][2][2], dc2_b_*: host [1].

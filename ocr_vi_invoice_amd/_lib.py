@@ -39,6 +39,7 @@ EXPORTS = [
     "ocrvi_test_conv_res", "ocrvi_test_db_tail",
     "ocrvi_db_target_jobs", "ocrvi_db_target_maps", "ocrvi_resize_normalize_pad_pages",
     "ocrvi_test_mlp_raw",
+    "ocrvi_test_bneck_tail",
 ]
 PAGE_ENTRY = 4          # int64 fields of one page-table entry: (device address, height, width, 0) -- OCRVI_PAGE_ENTRY
 # ocrvi_det_eval's record: 13 slots of 8 bytes (OCRVI_DET_EVAL_*), the first six int64, the rest float64
@@ -135,6 +136,7 @@ def load() -> C.CDLL:
     lib.ocrvi_test_conv.argtypes = [i32, i32, f32p, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32p, i32,
                                     C.POINTER(C.c_float)]
     lib.ocrvi_test_conv_res.argtypes = [i32, i32, f32p, vp, vp, f32p, i32, i32, i32, i32, i32, i32, i32, i32, f32p, i32, C.POINTER(C.c_float)]
+    lib.ocrvi_test_bneck_tail.argtypes = [i32, f32p, f32p, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32p, f32p, i32, C.POINTER(C.c_float)]
     lib.ocrvi_test_db_tail.argtypes = [i32, i32, f32p, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32p, f32p, i32,
                                        C.POINTER(C.c_float)]
     lib.ocrvi_test_gemm.argtypes = [i32, i32, f32p, vp, vp, f32p, i32, i32, i32, i32, i32, i32, f32p, i32, C.POINTER(C.c_float)]

@@ -251,6 +251,46 @@ extern "C" int ocrvi_test_conv_res(int device, int dtype, const float* x, const 
     return OCRVI_OK;
 }
 
+// The fused ResNet-50 layer1 chain (bneck_tail.h), f16x2: t1 [N,64,H,W] -> conv2 3x3 + ReLU -> conv3 1x1 + identity [N,256,H,W] + ReLU = y
+// -> (unless no_phase_c) the next block's conv1 1x1 + ReLU = t1n [N,64,H,W].  Weights as the detector's loader packs them.
+extern "C" int ocrvi_test_bneck_tail(int device, const float* t1, const float* identity, const float* w2_host, const float* b2_host,
+                                     const float* w3_host, const float* b3_host, const float* w1_host, const float* b1_host, int N, int H, int W,
+                                     int no_phase_c, float* y_out, float* t1n_out, int iters, float* avg_ms) {
+    OCRVI_CHECK(t1 && identity && w2_host && w3_host && y_out && N > 0 && H > 0 && W > 0, OCRVI_EINVAL, "test_bneck_tail: bad argument");
+    OCRVI_CHECK(no_phase_c || (w1_host && t1n_out), OCRVI_EINVAL, "test_bneck_tail: phase C needs the next conv1's weights and an output");
+    OCRVI_HIP(hipSetDevice(device));
+    Scratch sc;
+    OCRVI_TRY(sc.init());
+    const int dt = OCRVI_F16X2;
+    DeviceStore st;
+    ConvLayer L2;
+    PackedConv pc = pack_conv(w2_host, b2_host, 64, 64, 3, 3, 1, AM_CONV3, dt, true);
+    OCRVI_CHECK(pc.quartets, OCRVI_EINVAL, "test_bneck_tail: conv2 is not packed for conv3_halo (OCRVI_CONV3_HALO=0?)");
+    OCRVI_TRY(upload_packed(st, pc, AM_CONV3, &L2));
+    PackedBneckTail pt = pack_bneck_tail(w3_host, b3_host, no_phase_c ? nullptr : w1_host, no_phase_c ? nullptr : b1_host);
+    void* wt = nullptr;
+    float* bt = nullptr;
+    OCRVI_TRY(st.upload(pt.stream.data(), pt.stream.size(), &wt));
+    OCRVI_TRY(st.upload_f32(pt.bias, &bt));
+    const size_t P = (size_t)N * H * W;
+    void *xn = nullptr, *in = nullptr, *yn = nullptr, *tn = nullptr;
+    OCRVI_TRY(sc.alloc(P * 64 * 4, &xn));
+    OCRVI_TRY(sc.alloc(P * 256 * 4, &in));
+    OCRVI_TRY(sc.alloc(P * 256 * 4, &yn));
+    if (!no_phase_c) OCRVI_TRY(sc.alloc(P * 64 * 4, &tn));
+    OCRVI_TRY(to_nhwc(dt, t1, xn, N, 64, H * W, sc.s));
+    OCRVI_TRY(to_nhwc(dt, identity, in, N, 256, H * W, sc.s));
+    BneckTailParams p;
+    p.x = xn; p.w2 = L2.w; p.wt = wt; p.bias2 = L2.bias; p.bias_t = bt; p.idn = in; p.y = yn; p.t1n = tn;
+    p.n_img = N; p.H = H; p.W = W;
+    p.ws2 = L2.wscale; p.ws3 = pt.ws3; p.ws1 = pt.ws1;
+    OCRVI_TRY(timed(sc, iters, avg_ms, [&]() { return launch_bneck_tail(p, sc.s); }));
+    OCRVI_TRY(k_nhwc_to_nchw_f32(dt, yn, y_out, N, H, W, 256, 256, 0, sc.s));
+    if (!no_phase_c) OCRVI_TRY(k_nhwc_to_nchw_f32(dt, tn, t1n_out, N, H, W, 64, 64, 0, sc.s));
+    OCRVI_HIP(hipStreamSynchronize(sc.s));
+    return OCRVI_OK;
+}
+
 // The DB head's tail (head.py:13-16 per branch: ConvTranspose2d(64,64,2,2) + BN + ReLU, ConvTranspose2d(64,1,2,2)) as det_model.hip builds and
 // launches it: both branches' first deconvolutions packed as ONE grouped pixel-shuffle GEMM (group 0 = binarise, 1 = threshold), the second
 // deconvolution's weights as [2][64][4] + 2 biases, the 64 -> 1 dot in the GEMM's epilogue.  groups = 2: the launch sees the whole pack,

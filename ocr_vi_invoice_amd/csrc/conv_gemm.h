@@ -584,4 +584,30 @@ PackedConv pack_conv(const float* w, const float* bias, int cout, int cin_g, int
 // `groups` ConvTranspose2d(k=2,s=2) weights [Cin][Cout][2][2] -> grouped GEMM [group][n=(a*2+b)*Cout+co][k=ci]
 PackedConv pack_deconv2(const float* const* w, const float* const* bias, int groups, int cin, int cout, int dtype);
 
+// ---- f16x2 ResNet-50 layer1 chain as ONE kernel (bneck_tail.h): conv2 3x3 64->64 + ReLU, conv3 1x1 64->256 + identity + ReLU, and
+// (unless y-only) the next block's conv1 1x1 256->64 + ReLU.  The loader builds the tail stream only where conv2 is packed for conv3_halo,
+// so OCRVI_CONV3_HALO=0 (read by the packer) also restores the three launches.
+struct BneckTailParams {
+    const void* x = nullptr;      // t1   f16x2 [n_img][H][W][64]
+    const void* w2 = nullptr;     // conv2 weights, (hi, lo) quartets [64][576] (pack_conv with halo)
+    const void* wt = nullptr;     // tail stream (pack_bneck_tail): 8 (y-only) or 16 units of 8 KiB in LDS image order
+    const float* bias2 = nullptr; // [64]
+    const float* bias_t = nullptr;   // [256] conv3 bias, then [64] next conv1 bias (pack_bneck_tail)
+    const void* idn = nullptr;    // identity f16x2 [n_img][H][W][256]
+    void* y = nullptr;            // block output f16x2 [n_img][H][W][256]
+    void* t1n = nullptr;          // next block's t1 f16x2 [n_img][H][W][64]; null: y-only
+    const void* zero_page = nullptr;
+    void* dump_page = nullptr;
+    int n_img = 1, H = 1, W = 1;
+    float ws2 = 1.f, ws3 = 1.f, ws1 = 1.f;   // the three layers' weight scales
+};
+struct PackedBneckTail {
+    std::vector<char> stream;     // the units
+    std::vector<float> bias;      // [256] (+ [64])
+    float ws3 = 1.f, ws1 = 1.f;
+};
+// w3 [256][64] fp32 (+ b3 [256] or null); w1 [64][256] (+ b1) of the next block's conv1, or null for the y-only form
+PackedBneckTail pack_bneck_tail(const float* w3, const float* b3, const float* w1, const float* b1);
+int launch_bneck_tail(const BneckTailParams& p, hipStream_t stream);
+
 }  // namespace ocrvi

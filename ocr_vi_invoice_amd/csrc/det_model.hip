@@ -20,6 +20,11 @@ struct Bottleneck {
     ConvLayer conv1, conv2, off, conv3, down;
     bool dcn = false, has_down = false;
     int stride = 1;
+    // f16x2 layer1: conv2 + conv3 (+ the next block's conv1) as one launch (bneck_tail.h); tail_w = the packed stream (pack_bneck_tail)
+    void* tail_w = nullptr;
+    float* tail_bias = nullptr;
+    float tail_ws3 = 1.f, tail_ws1 = 1.f;
+    bool tail = false, tail_c = false;   // fused; ... including the next block's conv1
 };
 }  // namespace
 
@@ -86,6 +91,26 @@ extern "C" int ocrvi_det_create(int device, const void* blob_p, size_t blob_byte
             if (!basic) OCRVI_TRY(load_conv(st, blob, p + ".conv3", 4 * w, w, 1, 1, AM_CONV1, dt, true, &bk.conv3));
             if (bk.has_down) OCRVI_TRY(load_conv(st, blob, p + ".down", ex * w, inpl, 1, 1, AM_CONV1, dt, true, &bk.down));
             inpl = ex * w;
+        }
+        // The fused layer1 chain: by shape only (f16x2, conv2 64 -> 64 packed for conv3_halo, conv3 64 -> 256, the next conv1 256 -> 64);
+        // a layer's last block has no successor in the layer (layer2.0.conv1 is 256 -> 128) and ends at y.
+        for (int b = 0; b < nblk && !basic && dt == OCRVI_F16X2; ++b) {
+            Bottleneck& bk = h->layers[li][b];
+            if (bk.dcn || bk.stride != 1 || !bk.conv2.quartets || w != 64 || bk.conv2.Np != 64 || bk.conv2.Cin_g != 64) continue;
+            const std::string p = "layer" + std::to_string(li + 1) + "." + std::to_string(b);
+            const std::string pn = "layer" + std::to_string(li + 1) + "." + std::to_string(b + 1);
+            const BlobTensor *w3 = nullptr, *b3 = nullptr, *w1 = nullptr, *b1 = nullptr;
+            OCRVI_TRY(blob.get(p + ".conv3.w", 256, 64, 1, 1, &w3));
+            OCRVI_TRY(blob.get(p + ".conv3.b", 256, 0, 0, 0, &b3));
+            if (b + 1 < nblk) {
+                OCRVI_TRY(blob.get(pn + ".conv1.w", 64, 256, 1, 1, &w1));
+                OCRVI_TRY(blob.get(pn + ".conv1.b", 64, 0, 0, 0, &b1));
+            }
+            PackedBneckTail pt = pack_bneck_tail(w3->data, b3->data, w1 ? w1->data : nullptr, b1 ? b1->data : nullptr);
+            OCRVI_TRY(st.upload(pt.stream.data(), pt.stream.size(), &bk.tail_w));
+            OCRVI_TRY(st.upload_f32(pt.bias, &bk.tail_bias));
+            bk.tail_ws3 = pt.ws3; bk.tail_ws1 = pt.ws1;
+            bk.tail = true; bk.tail_c = w1 != nullptr;
         }
     }
     for (int i = 0; i < 4; ++i) {
@@ -181,11 +206,44 @@ static int det_run(ocrvi_det* h, Runner& r, const float* x, int N, int H, int W,
         Tensor tap = r.alloc(N, lh, lw, cw);                          // the layer's final output
         const size_t slot_mark = r.arena.mark();
         Tensor slot[2] = {r.alloc(N, lh, lw, cw), r.alloc(N, lh, lw, cw)};
+        // Fused chains (bneck_tail.h): block b reads t1 from t1pp[b & 1] and writes the next block's into the other one, so both live
+        // outside the blocks' own marks (released with the slots); t2 is never allocated.
+        const bool fused_layer = !h->basic && h->layers[li][0].tail;
+        Tensor t1pp[2];
+        if (fused_layer) { t1pp[0] = r.alloc(N, lh, lw, w); t1pp[1] = r.alloc(N, lh, lw, w); }
+        bool have_t1 = false;   // the previous block's launch has written this block's t1
         for (int b = 0; b < nb; ++b) {
             const Bottleneck& bk = h->layers[li][b];
             const int oh = cur.h / bk.stride, ow = cur.w / bk.stride;
             Tensor y = b == nb - 1 ? tap : slot[b & 1];               // never the buffer `cur` lives in (slot[(b-1)&1] or the previous tap)
             const size_t mark2 = r.arena.mark();
+            if (fused_layer && bk.tail) {
+                Tensor t1 = t1pp[b & 1];
+                if (!have_t1) {
+                    ConvOpts o;
+                    o.act = ACT_RELU;
+                    OCRVI_TRY(conv(r, bk.conv1, cur, t1, o));
+                }
+                Tensor idn = cur;
+                if (bk.has_down) {
+                    idn = r.alloc(N, oh, ow, 4 * w);
+                    ConvOpts o;
+                    OCRVI_TRY(conv(r, bk.down, cur, idn, o));
+                }
+                OCRVI_CHECK(idn.c == 256 && y.c == 256 && t1.c == 64 && !idn.f32 && !y.f32, OCRVI_EINVAL, "det: fused layer1 chain on a foreign shape");
+                if (!r.dry()) {
+                    BneckTailParams q;
+                    q.x = t1.p; q.w2 = bk.conv2.w; q.wt = bk.tail_w; q.bias2 = bk.conv2.bias; q.bias_t = bk.tail_bias;
+                    q.idn = idn.p; q.y = y.p; q.t1n = bk.tail_c ? t1pp[(b + 1) & 1].p : nullptr;
+                    q.n_img = N; q.H = oh; q.W = ow;
+                    q.ws2 = bk.conv2.wscale; q.ws3 = bk.tail_ws3; q.ws1 = bk.tail_ws1;
+                    OCRVI_TRY(launch_bneck_tail(q, r.stream));
+                }
+                have_t1 = bk.tail_c;
+                r.arena.release(mark2);   // the downsample output is dead
+                cur = y;
+                continue;
+            }
             if (h->basic) {
                 // BasicBlock: relu(bn2(conv2(relu(bn1(conv1(x))))) + identity); conv1 carries the stride and is never deformable, the
                 // residual and the final ReLU sit in conv2's epilogue (the pipelined deformable kernel's RES build in the 16-bit / f16x2 modes)

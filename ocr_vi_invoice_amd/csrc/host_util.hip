@@ -193,6 +193,58 @@ PackedConv pack_deconv2(const float* const* w, const float* const* bias, int gro
     return pc;
 }
 
+// The tail stream of bneck_tail.h.  Per group q of 32 conv3 channels: a B unit = conv3's slice K 64 x N 32 as 64 rows R = 32 j + n
+// (K-step j, channel 32 q + n), then (with w1) a C unit = the next conv1's slice K 32 x N 64 as 64 rows m.  A row is 128 bytes = eight
+// 16-byte positions; positions 2 g and 2 g + 1 hold the hi and the lo halves of lane group g's eight k-slots, which are the channels the
+// kernel's accumulator lanes hand over: base + 4 g + e and base + 16 + 4 g + e (e = 0..3; base = 32 j for B, 32 q for C).  Position P of row R
+// is stored at byte R * 128 + ((P ^ swz_halo(R)) << 4): the unit is the LDS image, copied linearly.  One power-of-two scale per layer, as
+// finish_pack chooses it.
+PackedBneckTail pack_bneck_tail(const float* w3, const float* b3, const float* w1, const float* b1) {
+    PackedBneckTail pk;
+    auto scale_of = [](const float* w, size_t n) {
+        float mx = 0.f, scale = 1.f;
+        for (size_t i = 0; i < n; ++i) mx = std::max(mx, fabsf(w[i]));
+        if (mx > 0.f && std::isfinite(mx)) {
+            int e = 0;
+            (void)frexpf(mx, &e);
+            scale = ldexpf(1.0f, std::min(std::max(14 - e, -100), 100));
+        }
+        return scale;
+    };
+    const float s3 = scale_of(w3, 256 * 64), s1 = w1 ? scale_of(w1, 64 * 256) : 1.f;
+    pk.ws3 = 1.0f / s3;
+    pk.ws1 = 1.0f / s1;
+    const int nu = w1 ? 16 : 8;
+    pk.stream.assign((size_t)nu * 8192, 0);
+    auto swz = [](int row) { return ((row >> 1) & 1) | (((row >> 2) & 1) << 2); };   // swz_halo
+    // row R of unit u: the weights of output channel `n` of matrix w (row stride ld) at input channels base + ...
+    auto put_row = [&](int u, int R, const float* wrow, int base, float scale) {
+        char* unit = pk.stream.data() + (size_t)u * 8192;
+        for (int g = 0; g < 4; ++g) {
+            _Float16 hi[8], lo[8];
+            for (int e = 0; e < 8; ++e) {
+                const int k = base + (e < 4 ? 4 * g + e : 16 + 4 * g + (e - 4));
+                const float x = wrow[k] * scale;
+                hi[e] = (_Float16)x;
+                lo[e] = (_Float16)(x - (float)hi[e]);
+            }
+            memcpy(unit + R * 128 + (((2 * g) ^ swz(R)) << 4), hi, 16);
+            memcpy(unit + R * 128 + (((2 * g + 1) ^ swz(R)) << 4), lo, 16);
+        }
+    };
+    for (int q = 0; q < 8; ++q) {
+        const int ub = w1 ? 2 * q : q;
+        for (int j = 0; j < 2; ++j)
+            for (int n = 0; n < 32; ++n) put_row(ub, 32 * j + n, w3 + (size_t)(32 * q + n) * 64, 32 * j, s3);
+        if (w1)
+            for (int m = 0; m < 64; ++m) put_row(ub + 1, m, w1 + (size_t)m * 256, 32 * q, s1);
+    }
+    pk.bias.assign(w1 ? 320 : 256, 0.f);
+    if (b3) std::copy(b3, b3 + 256, pk.bias.begin());
+    if (w1 && b1) std::copy(b1, b1 + 64, pk.bias.begin() + 256);
+    return pk;
+}
+
 // ------------------------------------------------------------------ profiler
 namespace {
 struct ProfEntry { std::string tag; double flops, bytes; hipEvent_t e0, e1; };

@@ -61,7 +61,7 @@ def touches_before_wait(body, start, dst):
     return hits
 
 
-ALL_SOURCES = ["conv_bf16.hip", "conv_f16.hip", "conv_f32.hip", "conv_f16x2.hip", "mlp_fused.hip", "attention.hip", "stem_pool.hip", "mlp_x2.hip"]
+ALL_SOURCES = ["conv_bf16.hip", "conv_f16.hip", "conv_f32.hip", "conv_f16x2.hip", "mlp_fused.hip", "attention.hip", "stem_pool.hip", "mlp_x2.hip", "bneck_tail.hip"]
 _ASM = {}
 
 
@@ -183,6 +183,41 @@ def check_halo(src="conv_f16x2.hip"):
                          v_mov=sum(t.startswith("v_mov_b32") for t in loop), s_nop=sum(t.startswith("s_nop") for t in loop),
                          waits=sum(t.startswith("s_waitcnt") for t in loop), v_add=sum(t.startswith("v_add_u32") for t in loop),
                          vgprs=int(v.group(1)) if v else -1)
+    return rep
+
+
+def check_bneck_tail(src="bneck_tail.hip"):
+    """The fused layer1 chain (bneck_tail.h): conv3_halo's unit loop (phase A) followed per tile by eight groups of conv3 / next-conv1
+    MFMAs fed from the accumulator lanes, with the identity fetched by inline-asm loads inside the counted vmcnt protocol.  name -> dict for
+    both builds (with phase C / y only):
+      scratch, vgprs    spill instructions in the whole kernel (an uncounted VMEM operation inside the protocol); the register count;
+      exposed_waits     `s_waitcnt lgkmcnt(0)` directly behind a `ds_read` inside phase A's unit loop (between the first counted barrier
+                        behind the prologue's and the first identity load, which follows the tile's last conv2 unit);
+      mfma_a, mfma_bc   MFMA instructions of phase A (the nine unrolled taps: the channel-block loop runs them twice per tile) and of the tail;
+      asm_loads, touches   the identity loads, and instructions that read or write one's destination before the counted wait behind it
+                        (to the end of the basic block, as for the ring's residual loads);
+      compiler_vmcnt_waits   hipcc's own vmcnt waits between the pipeline's first and last inline-asm statement (they would drain the ring)."""
+    txt = asm_of(src)
+    rep = {}
+    for name, body in kernel_bodies(txt, "_ZN5ocrvi17bneck_tail_kernel").items():
+        ins = [(t, a) for t, a in body if not t.endswith(":")]
+        bars = [i for i, (t, a) in enumerate(ins) if a and t.startswith("s_barrier")]
+        loads = [i for i, (t, a) in enumerate(ins) if a and t.startswith("global_load_dwordx4")]
+        a0, a1 = bars[1], loads[0]
+        span_a, span_bc = [t for t, _ in ins[a0:a1]], [t for t, _ in ins[a1:]]
+        exposed = sum(1 for x, y in zip(span_a, span_a[1:]) if x.startswith("ds_read") and re.match(r"s_waitcnt lgkmcnt\(0\)\s*$", y))
+        touches = []
+        for i, (t, a) in enumerate(body):
+            m = re.match(r"global_load_dwordx4 v\[(\d+):(\d+)\], v\[\d+:\d+\], off$", t)
+            if m and a:
+                touches += [(t, tt) for tt in touches_before_wait(body, i + 1, set(range(int(m.group(1)), int(m.group(2)) + 1)))]
+        first_asm = min(i for i, (t, a) in enumerate(ins) if a and t.startswith("global_load_lds"))
+        last_asm = max(i for i, (t, a) in enumerate(ins) if a)
+        cwaits = [t for i, (t, a) in enumerate(ins) if not a and first_asm < i < last_asm and t.startswith("s_waitcnt") and "vmcnt" in t]
+        v = re.search(r"\.name:\s+" + re.escape(name) + r"\n(?:(?!\.name:).*\n)*?\s*\.vgpr_count:\s*(\d+)", txt)
+        rep[name] = dict(scratch=sum("scratch_" in t for t, _ in ins), vgprs=int(v.group(1)) if v else -1, exposed_waits=exposed,
+                         mfma_a=sum(t.startswith("v_mfma") for t in span_a), mfma_bc=sum(t.startswith("v_mfma") for t in span_bc),
+                         asm_loads=len(loads), touches=touches, compiler_vmcnt_waits=cwaits)
     return rep
 
 
