@@ -412,6 +412,86 @@ int ocrvi_jpeg_table_entry(const ocrvi_jpeg_info_t* info, size_t used, int64_t s
 int ocrvi_jpeg_decode_pages(int device, const void* records_dev, const int64_t* table_dev, int n_pages, void* dst_base, void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * JPEG encode: replaces the cv2.imwrite at the end of the reference's loop (src/pipeline/pipeline2.py:397-400, and the det-only CLI in
+ * src/det/test.py) for baseline JPEG.  The host writes the header; colour conversion, down-sampling, forward DCT, quantisation, Huffman
+ * coding, bit packing and byte stuffing run on the device, batched over pages, and only the compressed bytes leave it.  Input is uint8
+ * RGB (3 bytes per pixel; cv2's BGR is the caller's business, as for decode) or uint8 grey (1 byte per pixel, a one-component file).
+ * Written: SOF0, one interleaved scan, the four Annex K Huffman tables, 4:2:0 or 4:4:4.  Not built: 4:2:2, restart intervals, optimised
+ * Huffman tables, progressive files, EXIF or ICC segments.
+ * The arithmetic is the library's own definition, stated here; tests/jpegenc_ref.py restates it in NumPy.  It equals libjpeg-turbo's
+ * default encoder (PIL's Image.save(..., "JPEG", quality=q, subsampling=2 or 0), which is also what cv2.imwrite links) byte for byte,
+ * the whole file -- pinned by tests/golden/jpeg_encode_cases.npz; parity with cv2.imwrite itself is UNPINNED (cv2 absent).  All values
+ * are integers and shifts are arithmetic.
+ *   tables      Annex K.1 luminance and chrominance; s = 5000 / q (integer) for q < 50, else 200 - 2 q; entry = clamp((std s + 50) / 100, 1, 255)
+ *   colour      Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + 8388608 + 32767) >> 16,
+ *               Cr = (32768 R - 27439 G - 5329 B + 8388608 + 32767) >> 16; a grey page is its own Y
+ *   planes      luma H x W; 4:2:0 chroma ceil(H / 2) x ceil(W / 2); a component of h x w samples has ceil(h / 8) x ceil(w / 8) real blocks
+ *   4:2:0       chroma[i][j] = (a + b + c + d + bias) >> 2 over the cell of rows 2i, 2i+1 and columns 2j, 2j+1, bias 1 in even and 2 in odd
+ *               columns j.  Columns beyond W repeat column W - 1 at full resolution, before the down-sampling; so does the one row an
+ *               odd H lacks.  Chroma rows beyond ceil(H / 2) repeat the last down-sampled row (not a down-sampling of repeated rows)
+ *   4:4:4, grey samples beyond the image repeat the last column and the last row
+ *   forward DCT the 8 x 8 "slow integer" form on sample - 128, the LL&M factorisation with the 13-bit constants of the decoder above.
+ *               t0..t7 = d0 + d7, d1 + d6, d2 + d5, d3 + d4, d3 - d4, d2 - d5, d1 - d6, d0 - d7; t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2,
+ *               t12 = t1 - t2; z1 = (t12 + t13) 4433, out2 = z1 + t13 6270, out6 = z1 - t12 15137; odd part: z1 = t4 + t7, z2 = t5 + t6,
+ *               z3 = t4 + t6, z4 = t5 + t7, z5 = (z3 + z4) 9633, out7 = t4 2446 - z1 7373 + (z5 - z3 16069), out5 = t5 16819 - z2 20995 +
+ *               (z5 - z4 3196), out3 = t6 25172 - z2 20995 + (z5 - z3 16069), out1 = t7 12299 - z1 7373 + (z5 - z4 3196).
+ *               Pass 1 along rows: outputs 0 and 4 are (t10 +- t11) << 2, the others (x + 2^10) >> 11.  Pass 2 down columns: outputs 0 and 4
+ *               are (t10 +- t11 + 2) >> 2, the others (x + 2^14) >> 15.  Results are 8 x the true DCT.
+ *   quantise    d = 8 x table entry; v = sign(c) ((|c| + (d >> 1)) / d).  AC values are saturated to [-1023, 1023] and DC differences
+ *               to [-2047, 2047]: neither is reached from 8-bit samples (|AC| <= about 1020, at coefficient (0, 4) of columns alternating
+ *               -128 and 127; |DC| <= 1024), they bound the bits of a block
+ *   dummy       in 4:2:0 an MCU may reach past the real luma blocks (an odd number of block columns or rows).  Such a block is not
+ *               computed from pixels: its AC coefficients are 0 and its DC is the DC of the block coded just before it in the same MCU;
+ *               it takes part in DC prediction like any block
+ *   entropy     Annex K.3's four Huffman tables.  DC: the category of the difference to the previous block of the component, then its
+ *               low bits (diff - 1 for negatives).  AC in zigzag order: (run, size) symbols, ZRL F0 per 16 zeros of a run, EOB 00 when
+ *               coefficient 63 is zero.  The last byte is padded with 1-bits; every FF byte is followed by 00
+ *   header      SOI; APP0 JFIF 1.1, units 0, density 1 x 1, no thumbnail; one DQT per table (8-bit, zigzag, ids 0 and 1; grey: id 0 only);
+ *               SOF0 (precision 8, height, width, components (1, 0x22 or 0x11, 0) (2, 0x11, 1) (3, 0x11, 1)); one DHT per table in the order
+ *               DC0, AC0, DC1, AC1 (grey: DC0, AC0); SOS with Ss = 0, Se = 63, Ah/Al = 0.  After the scan: EOI
+ * Block order (of every per-block array below): MCU by MCU in raster order; inside a 4:2:0 MCU the four luma blocks row by row, then
+ * Cb, then Cr; 4:4:4: Y, Cb, Cr; grey: block by block.
+ * Bound: a block adds at most 1660 bits to the scan -- a DC code of at most 11 bits (chrominance) + 11 low bits, and 63 AC symbols
+ * of at most 16 + 10 bits (a ZRL, 11 bits for 16 coefficients, costs less than the coefficients it stands for) -- that is 208 bytes,
+ * and byte stuffing at most doubles them: scan_capacity = 2 x 208 x blocks + 16.
+ * ------------------------------------------------------------------------------------------------ */
+/* Host only.  The two quantisation tables of `quality` (1..100), natural (row-major) order, 64 entries each. */
+int ocrvi_jpeg_quant_tables(int quality, uint16_t* luma, uint16_t* chroma);
+/* Host only.  Writes a file's header, SOI .. SOS as listed above, into out[0 .. cap); *used = its bytes (at most OCRVI_JPEG_HEADER_MAX;
+ * OCRVI_ENOMEM when cap is smaller).  components: 1 (grey) or 3; subsampling: the luma sampling factor, 2 (4:2:0) or 1 (4:4:4), ignored
+ * for grey.  The file is header + scan + FF D9. */
+#define OCRVI_JPEG_HEADER_MAX 640
+int ocrvi_jpeg_encode_header(int width, int height, int components, int subsampling, int quality, void* out, size_t cap, size_t* used);
+/* Host only.  For a page's geometry: *blocks = the 8 x 8 blocks of its scan (dummy blocks included), *workspace_bytes = the device bytes
+ * ocrvi_jpeg_encode_pages needs for it (a multiple of 256, about 352 per block), *scan_capacity = bytes its stuffed scan never exceeds
+ * (the bound above).  offsets (8 values, may be NULL as may the other outputs): the byte offsets of the page's regions in its workspace,
+ * for tests and tools -- 0 coef int16 [blocks][64] (quantised, zigzag order; the DC is the block's own value, 0 for a dummy block),
+ * 1 dc int16 [blocks] (unset for dummy blocks), 2 DC differences int16 [blocks], 3 bits uint32 [blocks] (what each block adds to the
+ * scan), 4 bit offsets uint64 [blocks + 1], 5 the scan before stuffing, 6 FF counts per 4096-byte segment, 7 uint64 the bytes of 5.
+ * OCRVI_EINVAL for sides outside 1..65500, other component counts or sampling factors, or more than 20648881 blocks. */
+int ocrvi_jpeg_encode_sizes(int width, int height, int components, int subsampling, int64_t* blocks, uint64_t* workspace_bytes,
+                            uint64_t* scan_capacity, uint64_t* offsets);
+/* Host only.  Fills one entry of the table ocrvi_jpeg_encode_pages reads, int64 [OCRVI_JPEG_ENC_ENTRY]: (0 source offset, 1 source row
+ * stride, 2 width, 3 height, 4 components, 5 luma sampling factor, 6 output offset, 7 output capacity, 8 workspace offset, 9 quality,
+ * 10..15 zero, 16..47 the two quantisation tables as uint16 [2][64], natural order, 48..63 zero).  Offsets are in bytes from src_base and
+ * out_base (signed: pages of one launch may lie in different buffers either side of the base) and from workspace (a multiple of 256);
+ * src_stride >= width x components; out_capacity >= scan_capacity. */
+#define OCRVI_JPEG_ENC_ENTRY 64
+int ocrvi_jpeg_encode_table_entry(int width, int height, int components, int subsampling, int quality, int64_t src_offset, int64_t src_stride,
+                                  int64_t out_offset, int64_t out_capacity, int64_t workspace_offset, int64_t* entry);
+/* Encodes the scans of n_pages pages in six launches (jpeg_fdct_kernel: pixels -> coefficients and AC bit counts; jpeg_bits_kernel: DC
+ * differences, bits per block, their exclusive prefix sum; jpeg_pack_kernel: Huffman codes ORed in at those offsets; jpeg_ffcount_kernel,
+ * jpeg_ffscan_kernel, jpeg_stuff_kernel: FF bytes per segment, prefix sum, scatter).  Page i's entropy-coded scan -- the last byte padded
+ * with 1-bits, every FF followed by 00, no EOI -- is written at out_base + its output offset and its byte count to lengths_dev[i]
+ * (int64; 0 for a skipped page).  table_dev: int64 [n_pages][OCRVI_JPEG_ENC_ENTRY], DEVICE memory like the pixels, read when the kernels
+ * run, so a captured graph survives rewritten tables.  Enqueue-only on `stream`: no allocation, no synchronisation.  workspace: 16-byte
+ * aligned; the pages' regions of it and of the output must not overlap.  An entry whose fields are out of range, whose regions do not
+ * fit workspace_bytes or whose capacity is below scan_capacity is skipped and never dereferenced.  The bytes are the same on every run
+ * (integer arithmetic; the only atomics are ORs into zeroed words). */
+int ocrvi_jpeg_encode_pages(int device, const void* src_base, const int64_t* table_dev, int n_pages, void* out_base, int64_t* lengths_dev,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 /* Replaces DBPostProcessor(thresh, box_thresh, max_candidates, unclip_ratio).__call__ with .min_area (src/det/test.py:46-106) on a HOST
  * probability map prob[H*W] (the reference also runs this stage on the CPU after `.cpu().numpy()`, pipeline2.py:320-321).
  * Output: the unclipped polygons as int32 (x, y) pairs in points[2*cap_points]; box i owns points box_offsets[i] .. box_offsets[i+1]

@@ -40,6 +40,7 @@ EXPORTS = [
     "ocrvi_db_target_jobs", "ocrvi_db_target_maps", "ocrvi_resize_normalize_pad_pages",
     "ocrvi_test_mlp_raw",
     "ocrvi_test_bneck_tail",
+    "ocrvi_jpeg_quant_tables", "ocrvi_jpeg_encode_header", "ocrvi_jpeg_encode_sizes", "ocrvi_jpeg_encode_table_entry", "ocrvi_jpeg_encode_pages",
 ]
 PAGE_ENTRY = 4          # int64 fields of one page-table entry: (device address, height, width, 0) -- OCRVI_PAGE_ENTRY
 # ocrvi_det_eval's record: 13 slots of 8 bytes (OCRVI_DET_EVAL_*), the first six int64, the rest float64
@@ -54,6 +55,8 @@ DB_TARGET_GT, DB_TARGET_MASK, DB_TARGET_THRESH = 0, 1, 2   # OCRVI_DB_TARGET_*: 
 DB_TARGET_JOB = 8               # int32 fields of one fill job -- OCRVI_DB_TARGET_JOB
 DB_TARGET_MAX_SIDE = 16384      # OCRVI_DB_TARGET_MAX_SIDE
 JPEG_ENTRY = 64                 # int64 fields of one ocrvi_jpeg_decode_pages table entry -- OCRVI_JPEG_ENTRY
+JPEG_ENC_ENTRY = 64             # int64 fields of one ocrvi_jpeg_encode_pages table entry -- OCRVI_JPEG_ENC_ENTRY
+JPEG_HEADER_MAX = 640           # OCRVI_JPEG_HEADER_MAX
 
 
 class DetCfg(C.Structure):
@@ -170,6 +173,11 @@ def load() -> C.CDLL:
     lib.ocrvi_jpeg_parse.argtypes = [vp, sz, vp, sz, C.POINTER(sz)]
     lib.ocrvi_jpeg_table_entry.argtypes = [C.POINTER(JpegInfo), sz, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp]
     lib.ocrvi_jpeg_decode_pages.argtypes = [i32, vp, vp, i32, vp, vp, sz, vp]
+    lib.ocrvi_jpeg_quant_tables.argtypes = [i32, vp, vp]
+    lib.ocrvi_jpeg_encode_header.argtypes = [i32, i32, i32, i32, i32, vp, sz, C.POINTER(sz)]
+    lib.ocrvi_jpeg_encode_sizes.argtypes = [i32, i32, i32, i32, C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]
+    lib.ocrvi_jpeg_encode_table_entry.argtypes = [i32, i32, i32, i32, i32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp]
+    lib.ocrvi_jpeg_encode_pages.argtypes = [i32, vp, vp, i32, vp, vp, vp, sz, vp]
     lib.ocrvi_db_target_jobs.argtypes = [vp, vp, vp, vp, i32, C.c_double, i32, vp, i32, vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                          C.POINTER(C.c_int32), i32]
     lib.ocrvi_db_target_maps.argtypes = [i32, vp, i32, vp, i32, vp, i32, i32, C.c_float, f32p, f32p, f32p, f32p, vp]

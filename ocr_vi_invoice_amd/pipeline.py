@@ -710,6 +710,179 @@ def imread(path: str, device: str = "cuda:0") -> torch.Tensor:
         return imdecode(f.read(), device)
 
 
+JPEG_SUBSAMPLINGS = {"4:2:0": 2, "4:4:4": 1}      # name -> luma sampling factor
+
+
+def jpeg_quant_tables(quality: int) -> Tuple[np.ndarray, np.ndarray]:
+    """``ocrvi_jpeg_quant_tables`` (host only): the luminance and chrominance tables of ``quality``, uint16 [64] in natural order."""
+    luma, chroma = np.zeros(64, np.uint16), np.zeros(64, np.uint16)
+    _lib.check(_lib.load().ocrvi_jpeg_quant_tables(int(quality), luma.ctypes.data, chroma.ctypes.data))
+    return luma, chroma
+
+
+def jpeg_encode_header(height: int, width: int, components: int, subsampling: str = "4:2:0", quality: int = 95) -> bytes:
+    """``ocrvi_jpeg_encode_header`` (host only): the bytes SOI .. SOS of the file ``imencode`` writes for such a page."""
+    if subsampling not in JPEG_SUBSAMPLINGS:
+        raise ValueError(f"subsampling {subsampling!r}: expected one of {sorted(JPEG_SUBSAMPLINGS)}")
+    buf = np.zeros(_lib.JPEG_HEADER_MAX, np.uint8)
+    used = ctypes.c_size_t()
+    _lib.check(_lib.load().ocrvi_jpeg_encode_header(int(width), int(height), int(components), JPEG_SUBSAMPLINGS[subsampling], int(quality),
+                                                    buf.ctypes.data, buf.size, ctypes.byref(used)))
+    return buf[:used.value].tobytes()
+
+
+def jpeg_encode_sizes(height: int, width: int, components: int, subsampling: str = "4:2:0") -> dict:
+    """``ocrvi_jpeg_encode_sizes`` (host only): ``blocks``, ``workspace_bytes``, ``scan_capacity`` and the workspace ``offsets`` of a page."""
+    if subsampling not in JPEG_SUBSAMPLINGS:
+        raise ValueError(f"subsampling {subsampling!r}: expected one of {sorted(JPEG_SUBSAMPLINGS)}")
+    blocks, wsb, cap = ctypes.c_int64(), ctypes.c_uint64(), ctypes.c_uint64()
+    offs = np.zeros(8, np.uint64)
+    _lib.check(_lib.load().ocrvi_jpeg_encode_sizes(int(width), int(height), int(components), JPEG_SUBSAMPLINGS[subsampling], ctypes.byref(blocks),
+                                                   ctypes.byref(wsb), ctypes.byref(cap), offs.ctypes.data))
+    return {"blocks": blocks.value, "workspace_bytes": wsb.value, "scan_capacity": cap.value, "offsets": [int(v) for v in offs]}
+
+
+class JpegEncodeJob:
+    """The pages of one ``ocrvi_jpeg_encode_pages`` call: validated and laid out by the constructor (ValueError before anything touches
+    the device), uploaded and enqueued by ``launch`` (one page table, one set of launches, no synchronisation), read back by ``collect``
+    (the lengths, then only the compressed bytes).  ``imencode_pages`` is ``JpegEncodeJob(...).launch().collect()``."""
+
+    def __init__(self, images, quality=95, subsampling: str = "4:2:0", device="cuda:0", what: str = "imencode"):
+        if subsampling not in JPEG_SUBSAMPLINGS:
+            raise ValueError(f"{what}: subsampling {subsampling!r}: expected one of {sorted(JPEG_SUBSAMPLINGS)}")
+        self.images = list(images)
+        n = len(self.images)
+        if isinstance(quality, (list, tuple, np.ndarray)):
+            if len(quality) != n:
+                raise ValueError(f"{what}: {len(quality)} qualities for {n} pages")
+            qualities = list(quality)
+        else:
+            qualities = [quality] * n
+        self.qualities = []
+        for i, q in enumerate(qualities):
+            if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or not 1 <= int(q) <= 100:
+                raise ValueError(f"{what}: page {i}: quality {q!r} outside 1..100")
+            self.qualities.append(int(q))
+        self.subsampling = subsampling
+        self.dev = torch.device(device)
+        self.geom = []                          # (h, w, components, luma sampling factor)
+        for i, im in enumerate(self.images):
+            if not isinstance(im, (np.ndarray, torch.Tensor)):
+                raise ValueError(f"{what}: page {i}: expected a numpy array or a tensor, got {type(im).__name__}")
+            if im.dtype not in (np.uint8, torch.uint8):
+                raise ValueError(f"{what}: page {i}: dtype {im.dtype} (uint8 expected)")
+            shape = tuple(im.shape)
+            if not (len(shape) == 2 or (len(shape) == 3 and shape[2] == 3)):
+                raise ValueError(f"{what}: page {i}: shape {shape} (H x W x 3 RGB or H x W grey expected)")
+            if not (1 <= shape[0] <= 65500 and 1 <= shape[1] <= 65500):
+                raise ValueError(f"{what}: page {i}: sides {shape[0]} x {shape[1]} outside 1..65500")
+            nc = 1 if len(shape) == 2 else 3
+            self.geom.append((shape[0], shape[1], nc, 1 if nc == 1 else JPEG_SUBSAMPLINGS[subsampling]))
+        lib = _lib.load()
+        self.w_off, self.o_off, self.caps = [0], [0], []
+        for h, w, nc, hs in self.geom:
+            wsb, cap = ctypes.c_uint64(), ctypes.c_uint64()
+            rc = lib.ocrvi_jpeg_encode_sizes(w, h, nc, hs, None, ctypes.byref(wsb), ctypes.byref(cap), None)
+            if rc == -1:
+                raise ValueError(f"{what}: {_lib.last_error()}")
+            _lib.check(rc)
+            self.caps.append(_align(cap.value))
+            self.w_off.append(self.w_off[-1] + wsb.value)
+            self.o_off.append(self.o_off[-1] + self.caps[-1])
+        self.lengths = self.out = None
+
+    def launch(self) -> "JpegEncodeJob":
+        n = len(self.images)
+        if n == 0:
+            return self
+        dev, lib = self.dev, _lib.load()
+        with torch.cuda.device(dev):
+            # host pages travel in one pinned buffer and one copy; device pages are read where they lie
+            host = [i for i, im in enumerate(self.images) if isinstance(im, np.ndarray) or not im.is_cuda]
+            h_off = [0]
+            for i in host:
+                h, w, nc, _ = self.geom[i]
+                h_off.append(h_off[-1] + _align(h * w * nc))
+            src = [None] * n
+            if host:
+                stage = torch.empty(h_off[-1], dtype=torch.uint8).pin_memory()
+                for k, i in enumerate(host):
+                    im = self.images[i]
+                    flat = torch.from_numpy(np.ascontiguousarray(im)) if isinstance(im, np.ndarray) else im.contiguous()
+                    stage[h_off[k]:h_off[k] + flat.numel()].copy_(flat.reshape(-1))
+                d_stage = stage.to(dev, non_blocking=True)
+                for k, i in enumerate(host):
+                    src[i] = d_stage[h_off[k]:]
+            for i, im in enumerate(self.images):
+                if src[i] is None:
+                    src[i] = im.to(dev).contiguous()
+            base = src[0].data_ptr()
+            table = np.zeros((n, _lib.JPEG_ENC_ENTRY), np.int64)
+            for i, (h, w, nc, hs) in enumerate(self.geom):
+                _lib.check(lib.ocrvi_jpeg_encode_table_entry(w, h, nc, hs, self.qualities[i], src[i].data_ptr() - base, w * nc, self.o_off[i],
+                                                             self.caps[i], self.w_off[i], table[i].ctypes.data))
+            self._src = src                     # kept alive until collect
+            d_tab = torch.from_numpy(table).pin_memory().to(dev, non_blocking=True)
+            self._ws = torch.empty(self.w_off[-1], dtype=torch.uint8, device=dev)
+            self.out = torch.empty(self.o_off[-1], dtype=torch.uint8, device=dev)
+            self.lengths = torch.empty(n, dtype=torch.int64, device=dev)
+            self._tab, self._base = d_tab, base
+            self.enqueue()
+        return self
+
+    def enqueue(self) -> None:
+        """The six launches alone, on the current stream (what tools/jpeg_encode_bench.py times as "kernels")."""
+        _lib.check(_lib.load().ocrvi_jpeg_encode_pages(_dev_index(self.dev), self._base, self._tab.data_ptr(), len(self.images), self.out.data_ptr(),
+                                                       self.lengths.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
+                                                       torch.cuda.current_stream(self.dev).cuda_stream))
+
+    def collect_scans(self) -> List[bytes]:
+        """Waits for the lengths, then copies the compressed bytes alone to the host."""
+        n = len(self.images)
+        if n == 0:
+            return []
+        lens = [int(v) for v in self.lengths.cpu()]
+        for i, ln in enumerate(lens):
+            if not 0 < ln <= self.caps[i]:
+                raise RuntimeError(f"jpeg encode: page {i} was skipped by the device (length {ln})")
+        packed = torch.cat([self.out[self.o_off[i]:self.o_off[i] + lens[i]] for i in range(n)]) if n > 1 else self.out[:lens[0]]
+        host = packed.cpu().numpy()
+        ends = np.cumsum([0] + lens)
+        return [host[ends[i]:ends[i + 1]].tobytes() for i in range(n)]
+
+    def collect(self) -> List[bytes]:
+        scans = self.collect_scans()
+        return [jpeg_encode_header(h, w, nc, self.subsampling, self.qualities[i]) + scans[i] + b"\xff\xd9"
+                for i, (h, w, nc, _) in enumerate(self.geom)]
+
+
+def imencode_pages(images, quality=95, subsampling: str = "4:2:0", device: str = "cuda:0") -> List[bytes]:
+    """``imencode`` for a list of pages of any sizes, grey and colour mixed, ``quality`` a scalar or one value per page: one upload of a
+    page table and one set of launches (``ocrvi_jpeg_encode_pages``) serve the whole list; only the compressed bytes come back."""
+    return JpegEncodeJob(images, quality, subsampling, device, "imencode_pages").launch().collect()
+
+
+def imencode(image, quality: int = 95, subsampling: str = "4:2:0", device: str = "cuda:0") -> bytes:
+    """``cv2.imencode(".jpg", image, [IMWRITE_JPEG_QUALITY, quality])`` for an RGB page: the bytes of a baseline JPEG file.  ``image`` is
+    uint8 [h, w, 3] RGB or uint8 [h, w] grey (a one-component file), a numpy array or a tensor on the host or the device; ``subsampling`` is
+    "4:2:0" (what cv2.imwrite and PIL write by default) or "4:4:4".  The host writes the header; everything else runs on the device.  The
+    arithmetic is stated in include/ocrvi.h: libjpeg-turbo's default encoder byte for byte (PIL's ``save(..., "JPEG", quality=q)``), cv2
+    parity unpinned.  ValueError for sides outside 1..65500, other dtypes, shapes or subsamplings, or a quality outside 1..100."""
+    return JpegEncodeJob([image], quality, subsampling, device, "imencode").launch().collect()[0]
+
+
+def imwrite(path: str, image, quality: int = 95, subsampling: str = "4:2:0", device: str = "cuda:0") -> bool:
+    """``cv2.imwrite(path, image)`` of the reference's loop (pipeline2.py:397-400) for an RGB page and a ``.jpg`` path: ``imencode`` into
+    the file.  True when the file was written, False when it could not be (cv2's convention); ValueError as ``imencode``."""
+    data = imencode(image, quality, subsampling, device)
+    try:
+        with open(path, "wb") as f:
+            f.write(data)
+    except OSError:
+        return False
+    return True
+
+
 def detect_and_recognize(original_image, det_model, rec_model, post_processor: DBPostProcessor, device: str = "cuda:0", det_size: int = 640,
                          rec_size: Tuple[int, int] = (32, 256), rec_batch_size: int = 64, binary_head: bool = False, quad=None,
                          enhance: bool = False, crop: str = "rect"):

@@ -9,7 +9,7 @@ offsets and tables read, planes written; rgb: planes read, RGB written) and ``hb
 importable (``null`` otherwise).  PCIe: coefficient-stream bytes against 3 H W.  End to end: ``Engine.run`` on ``--engine-pages`` pages as
 JPEG bytes against the same pages as pre-decoded device arrays (no decode at all: the upper bound), the two settings alternating run by
 run, median and spread of each.
-The files are encoded with PIL (the library has no encoder); ``--dir`` takes a folder of baseline .jpg files instead.  Needs a GPU: there
+The files are encoded with PIL (an encoder independent of the library's own); ``--dir`` takes a folder of baseline .jpg files instead.  Needs a GPU: there
 is no fallback."""
 import argparse
 import concurrent.futures
@@ -37,7 +37,7 @@ def encode_pages(n, subsampling):
     try:
         from PIL import Image
     except ImportError:
-        raise SystemExit("jpeg_bench encodes its pages with PIL, which is not importable here (the library has no encoder): "
+        raise SystemExit("jpeg_bench encodes its pages with PIL, which is not importable here: "
                          "pass --dir with a folder of baseline .jpg files instead") from None
     out = []
     for i in range(n):
