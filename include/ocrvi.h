@@ -753,6 +753,17 @@ int ocrvi_test_db_tail(int device, int dtype, const float* x, const float* dc1_w
  * the persistent LDS-DMA ring GEMM whenever the shape is eligible (svtrv2.py:51-61,80-86 Linears; resnet Bottleneck 1x1 convs). */
 int ocrvi_test_gemm(int device, int dtype, const float* a, const float* weight_host, const float* bias_host, const float* res, int M,
                     int K, int N, int act, int res_post, int out_f32, float* out, int iters, float* avg_ms);
+/* The same call with the output buffer owned by the caller: out_raw is a DEVICE buffer of at least M rows of N output elements (float32
+ * when out_f32 is set or `dtype` is OCRVI_F32, else `dtype` elements) that the kernel writes directly (the caller pre-fills it, and any
+ * rows past M, and reads the bytes back); only its first M rows are converted to out [M][N] float32 DEVICE. */
+int ocrvi_test_gemm_raw(int device, int dtype, const float* a, const float* weight_host, const float* bias_host, const float* res, int M,
+                        int K, int N, int act, int res_post, int out_f32, void* out_raw, float* out);
+/* Host-only (no GPU): which build of the ring GEMM a plain NHWC convolution of M output pixels, N output channels and GEMM depth K takes
+ * on a device of n_cu compute units, from the same function the launcher dispatches on.  amode 0: 1x1 / nn.Linear (K = C_in); amode 1:
+ * 3x3, stride 1, pad 1 (K = 9 C_in).  has_res: a residual of the output's shape and element type.  plan = {eligible for the ring GEMM
+ * (0 / 1), tile rows BM, tile columns BN, 16-row slices per slice group SPS, fp32-output build (0 / 1), workgroups, fewest row tiles
+ * one workgroup walks, most row tiles one workgroup walks}; entries 1..7 describe the ring launch whether or not entry 0 is set. */
+int ocrvi_test_ring_plan(int dtype, int amode, int M, int K, int N, int out_f32, int has_res, int n_cu, int32_t plan[8]);
 /* Multi-head self-attention on a packed qkv tensor [B, N, 3*heads*32] float32 (layout of
  * qkv.reshape(B,N,3,heads,32), svtrv2.py:80) -> out [B, N, heads*32] float32 (svtrv2.py:82-85). */
 /* The detector's stem: conv 7x7 stride 2 pad 3 (3 -> 64 channels) + bias + ReLU + max-pool 3x3 stride 2 pad 1 (torchvision resnet50's

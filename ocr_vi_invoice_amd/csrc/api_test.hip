@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <memory>
 
+#include "conv_launch.h"
 #include "model.h"
 
 using namespace ocrvi;
@@ -367,8 +368,11 @@ extern "C" int ocrvi_test_offset_conv(int device, int dtype, const float* x, con
     return OCRVI_OK;
 }
 
-extern "C" int ocrvi_test_gemm(int device, int dtype, const float* a, const float* weight_host, const float* bias_host, const float* res, int M,
-                               int K, int N, int act, int res_post, int out_f32, float* out, int iters, float* avg_ms) {
+namespace {
+// out_raw: the caller's own device output buffer ([>= M][N] of the output's element type, ocrvi_test_gemm_raw), or null for one of exactly
+// M rows allocated here
+int test_gemm_impl(int device, int dtype, const float* a, const float* weight_host, const float* bias_host, const float* res, int M, int K, int N,
+                   int act, int res_post, int out_f32, void* out_raw, float* out, int iters, float* avg_ms) {
     OCRVI_CHECK(a && weight_host && out && M > 0 && K > 0 && N > 0, OCRVI_EINVAL, "test_gemm: bad argument");
     OCRVI_HIP(hipSetDevice(device));
     Scratch sc;
@@ -378,9 +382,9 @@ extern "C" int ocrvi_test_gemm(int device, int dtype, const float* a, const floa
     ConvLayer L;
     PackedConv pc = pack_conv(weight_host, bias_host, N, K, 1, 1, 1, AM_CONV1, dtype);
     OCRVI_TRY(upload_packed(st, pc, AM_CONV1, &L));
-    void *an = nullptr, *yn = nullptr, *rn = nullptr;
+    void *an = nullptr, *yn = out_raw, *rn = nullptr;
     OCRVI_TRY(sc.alloc((size_t)M * K * dtype_size(dtype), &an));
-    OCRVI_TRY(sc.alloc((size_t)M * N * (f32o ? 4 : dtype_size(dtype)), &yn));
+    if (!yn) OCRVI_TRY(sc.alloc((size_t)M * N * (f32o ? 4 : dtype_size(dtype)), &yn));
     OCRVI_TRY(k_cast_from_f32(dtype, a, an, (size_t)M * K, sc.s));
     Runner r(dtype, sc.s, (void*)256, 0);
     Tensor tx; tx.p = an; tx.n = 1; tx.h = 1; tx.w = M; tx.c = K;
@@ -402,6 +406,42 @@ extern "C" int ocrvi_test_gemm(int device, int dtype, const float* a, const floa
     if (f32o) OCRVI_HIP(hipMemcpyAsync(out, yn, (size_t)M * N * 4, hipMemcpyDeviceToDevice, sc.s));
     else OCRVI_TRY(k_nhwc_to_nchw_f32(dtype, yn, out, 1, 1, M * N, 1, 1, 0, sc.s));
     OCRVI_HIP(hipStreamSynchronize(sc.s));
+    return OCRVI_OK;
+}
+}  // namespace
+
+extern "C" int ocrvi_test_gemm(int device, int dtype, const float* a, const float* weight_host, const float* bias_host, const float* res, int M,
+                               int K, int N, int act, int res_post, int out_f32, float* out, int iters, float* avg_ms) {
+    return test_gemm_impl(device, dtype, a, weight_host, bias_host, res, M, K, N, act, res_post, out_f32, nullptr, out, iters, avg_ms);
+}
+
+extern "C" int ocrvi_test_gemm_raw(int device, int dtype, const float* a, const float* weight_host, const float* bias_host, const float* res,
+                                   int M, int K, int N, int act, int res_post, int out_f32, void* out_raw, float* out) {
+    OCRVI_CHECK(out_raw, OCRVI_EINVAL, "test_gemm_raw: out_raw is null");
+    return test_gemm_impl(device, dtype, a, weight_host, bias_host, res, M, K, N, act, res_post, out_f32, out_raw, out, 0, nullptr);
+}
+
+// Host only: what launch_gemm_ring would do with a plain NHWC 1x1 (amode 0; K = C_in) or stride-1 3x3 (amode 1; K = 9 C_in) of M output
+// pixels on a device of n_cu compute units.  No device is touched.
+extern "C" int ocrvi_test_ring_plan(int dtype, int amode, int M, int K, int N, int out_f32, int has_res, int n_cu, int32_t plan[8]) {
+    OCRVI_CHECK(plan && dtype_valid(dtype) && (amode == AM_CONV1 || amode == AM_CONV3) && M > 0 && K > 0 && N > 0 && n_cu > 0, OCRVI_EINVAL,
+                "test_ring_plan: bad argument");
+    OCRVI_CHECK(amode == AM_CONV1 || K % 9 == 0, OCRVI_EINVAL, "test_ring_plan: K = %d of a 3x3 is not a multiple of 9", K);
+    const int bke = conv_bke(dtype), bn = conv_bn_for(N), taps = amode == AM_CONV3 ? 9 : 1;
+    const bool f32o = out_f32 || dtype == OCRVI_F32;
+    ConvParams p;   // as conv() fills it for pack_conv's layer; the pointers are only tested for alignment
+    p.x = p.w = (const void*)256; p.out = (void*)256;
+    p.n_img = 1; p.H = p.OH = 1; p.W = p.OW = M; p.M = M;
+    p.KH = taps == 9 ? 3 : 1; p.PH = p.PW = taps == 9 ? 1 : 0;
+    p.Cin = p.Cin_g = K / taps;
+    p.N_g = N; p.Np = cdiv(N, bn) * bn; p.Kp = cdiv(K, bke) * bke;
+    p.ldo = N; p.out_f32 = f32o ? 1 : 0;
+    p.identity_pix = taps == 1 ? 1 : 0;
+    if (has_res) { p.res = (const void*)256; p.res_mode = RES_SAME; p.ldr = N; p.res_f32 = f32o ? 1 : 0; }
+    const RingPlan pl = ring_plan((int)dtype_size(dtype), dtype == OCRVI_F16X2, amode, M, p.Np, p.Kp, out_f32 != 0, n_cu);
+    plan[0] = (gemm_ring_eligible(p, amode, dtype) && pl.ntiles <= n_cu) ? 1 : 0;
+    plan[1] = pl.bm; plan[2] = pl.bn; plan[3] = pl.sps; plan[4] = pl.f32o ? 1 : 0;
+    plan[5] = pl.grid; plan[6] = pl.tiles_min; plan[7] = pl.tiles_max;
     return OCRVI_OK;
 }
 

@@ -87,6 +87,46 @@ static int launch_ring_cfg(const ConvParams& p, int amode, int grid, hipStream_t
     }
 }
 
+// Which build of gemm_ring_kernel a GEMM takes and on what grid: a pure function of the shape, the element type and the CU count.
+// launch_gemm_ring dispatches on it and ocrvi_test_ring_plan reports it, so a test can assert the build it means to reach.
+struct RingPlan {
+    int bn, ntiles, nk;        // column tile, column tiles, K-steps per tile
+    bool big_m, mid256, f32o;
+    int bm, sps;               // row tile; 16-row slices per slice group of the build (BM x BN x SPS and F32O name the instantiation)
+    int mtiles, gm, grid;      // row tiles, row-tile lanes, workgroups = gm * ntiles
+    int tiles_min, tiles_max;  // row tiles the workgroups walk
+};
+// esz: sizeof(T); split: f16x2
+inline RingPlan ring_plan(int esz, bool split, int amode, int M, int Np, int Kp, bool out_f32, int n_cu) {
+    RingPlan r;
+    r.bn = Np % 128 == 0 ? 128 : 64;  // 64-channel layers: a 256x64 tile (16-bit types only, checked by gemm_ring_eligible)
+    r.ntiles = Np / r.bn;
+    r.nk = Kp / (128 / esz);
+    // 256-row tiles (4 slice groups riding on the next tile's first 4 K-steps) when K is deep enough for that and M still gives every
+    // CU work; otherwise 128-row tiles (one group)
+    r.big_m = amode == AM_CONV3 || cdiv(M, 256) * r.ntiles >= 192;
+    r.f32o = esz == 4 || (out_f32 && amode != AM_CONV3);
+    const bool f32o = esz == 4 || out_f32;
+    // nk = 2..3 with a 16-bit output: 256-row tiles with two slice groups of two slices (the fp32-output build of that shape spills)
+    r.mid256 = r.nk >= 2 && r.nk < 4 && !f32o && r.big_m && amode == AM_CONV1;
+    // (fp32 GEMMs -- the parity mode -- stay on 128-row tiles: their 256-row build does not fit the register file without a spill)
+    // (f16x2: 4-byte operands like fp32, but its 256-row build -- 255 VGPRs, no scratch -- fits, and the kernel is bound by the bytes it
+    // streams per FLOP, not by the matrix pipe: 256 x 128 tiles move 2/3 of the bytes of 128 x 128 ones)
+    const bool wide_ok = esz == 2 || split;
+    r.bm = r.bn == 64 ? 256 : ((wide_ok && ((r.nk >= 4 && r.big_m) || r.mid256)) ? 256 : 128);
+    if (!wide_ok) r.bm = 128;   // (no 256-row build exists for fp32: launch_gemm_ring falls through to 128 rows)
+    r.sps = r.bm == 128 ? 2 : ((r.bn == 64 || r.mid256) ? 2 : 1);
+    // one persistent workgroup per CU; a workgroup keeps its column tile, so the grid is Gm row-tile lanes x ntiles, with Gm chosen
+    // for equal row-tile counts
+    r.mtiles = cdiv(M, r.bm);
+    int gm = std::min(r.mtiles, std::max(1, n_cu / std::max(1, r.ntiles)));
+    r.gm = cdiv(r.mtiles, cdiv(r.mtiles, gm));
+    r.grid = r.gm * r.ntiles;
+    r.tiles_min = r.mtiles / r.gm;
+    r.tiles_max = cdiv(r.mtiles, r.gm);
+    return r;
+}
+
 template <typename T>
 int launch_gemm_ring(const ConvParams& p_in, int amode, hipStream_t stream) {
     ConvParams p = p_in;
@@ -97,36 +137,19 @@ int launch_gemm_ring(const ConvParams& p_in, int amode, hipStream_t stream) {
     }
     int n_cu = 0;
     OCRVI_TRY(device_cus(&n_cu));
-    const int bn = p.Np % 128 == 0 ? 128 : 64;  // 64-channel layers: a 256x64 tile (16-bit types only, checked by gemm_ring_eligible)
-    const int ntiles = p.Np / bn, nk = p.Kp / (int)(128 / sizeof(T));
-    OCRVI_CHECK(ntiles >= 1 && ntiles <= n_cu && nk >= 1, OCRVI_EINVAL, "gemm_ring: Np=%d Kp=%d out of range", p.Np, p.Kp);
-    // 256-row tiles (4 slice groups riding on the next tile's first 4 K-steps) when K is deep enough for that and M still gives every
-    // CU work; otherwise 128-row tiles (one group)
-    const bool big_m = amode == AM_CONV3 || cdiv(p.M, 256) * ntiles >= 192;
-    const bool f32o = sizeof(T) == 4 || p.out_f32;
-    // nk = 2..3 with a 16-bit output: 256-row tiles with two slice groups of two slices (the fp32-output build of that shape spills)
-    const bool mid256 = nk >= 2 && nk < 4 && !f32o && big_m && amode == AM_CONV1;
-    // (fp32 GEMMs -- the parity mode -- stay on 128-row tiles: their 256-row build does not fit the register file without a spill)
-    // (f16x2: 4-byte operands like fp32, but its 256-row build -- 255 VGPRs, no scratch -- fits, and the kernel is bound by the bytes it
-    // streams per FLOP, not by the matrix pipe: 256 x 128 tiles move 2/3 of the bytes of 128 x 128 ones)
-    const bool wide_ok = sizeof(T) == 2 || IsSplit<T>::value;
-    const int bm = bn == 64 ? 256 : ((wide_ok && ((nk >= 4 && big_m) || mid256)) ? 256 : 128);
-    // one persistent workgroup per CU; a workgroup keeps its column tile, so the grid is Gm row-tile lanes x ntiles, with Gm chosen
-    // for equal row-tile counts
-    const int mtiles = cdiv(p.M, bm);
-    int gm = std::min(mtiles, std::max(1, n_cu / ntiles));
-    gm = cdiv(mtiles, cdiv(mtiles, gm));
-    const int grid = gm * ntiles;
+    const RingPlan pl = ring_plan((int)sizeof(T), IsSplit<T>::value, amode, p.M, p.Np, p.Kp, p.out_f32 != 0, n_cu);
+    OCRVI_CHECK(pl.ntiles >= 1 && pl.ntiles <= n_cu && pl.nk >= 1, OCRVI_EINVAL, "gemm_ring: Np=%d Kp=%d out of range", p.Np, p.Kp);
+    const int grid = pl.grid;
     if constexpr (sizeof(T) == 2) {
-        if (bn == 64) {  // 8 waves along M (32 rows each: one slice group of two slices)
+        if (pl.bn == 64) {  // 8 waves along M (32 rows each: one slice group of two slices)
             return launch_ring_f<T, 256, 8, 2, false, false, 64>(p, grid, stream);
         }
     }
     if constexpr (sizeof(T) == 2) {
-        if (bm == 256 && mid256) return launch_ring_f<T, 256, 8, 2, false, false>(p, grid, stream);
+        if (pl.bm == 256 && pl.mid256) return launch_ring_f<T, 256, 8, 2, false, false>(p, grid, stream);
     }
     if constexpr (sizeof(T) == 2 || IsSplit<T>::value) {
-        if (bm == 256) return launch_ring_cfg<T, 256, 8, 1>(p, amode, grid, stream);
+        if (pl.bm == 256) return launch_ring_cfg<T, 256, 8, 1>(p, amode, grid, stream);
     }
     return launch_ring_cfg<T, 128, 8, 2>(p, amode, grid, stream);  // MI = 2: one group
 }

@@ -192,15 +192,18 @@ def _x2_scale(w):
     return 2.0 ** (14 - math.frexp(mx)[1]) if mx > 0 else 1.0
 
 
-def _mfma_chain(a, w, dt):
+def _mfma_chain(a, w, dt, acc0=None):
     """a [M, K] (values T holds) times w [N, K]^T as a chain of MFMAs over 32 consecutive k each, the accumulator rounded to fp32 once per
     MFMA (products and the sum inside one MFMA exact: an assumption, the adder's inner order and rounding are not documented, and the
     16-bit kernel's fc1 takes its 32 k of a 64-wide K-step from four 8-element groups, not consecutively).  f16x2 runs mlp_x2.hip's
     three products per step in its order -- w_lo a_hi, w_hi a_lo, w_hi a_hi -- on weights scaled by _x2_scale and split into fp16 halves,
-    and undoes the scale (a power of two) at the end, as the kernel does in the fma that adds the bias."""
+    and undoes the scale (a power of two) at the end, as the kernel does in the fma that adds the bias.  acc0: what the accumulators start
+    at instead of zero, in the result's scale ([N] or [M, N]; the ring GEMM's fp32 and f16x2 builds start at the bias, tests/gemm_refs.py)."""
     K = a.shape[1]
     acc = torch.zeros(a.shape[0], w.shape[0], dtype=torch.float32)
     a64, w64 = a.double(), w.double()
+    if acc0 is not None:
+        acc = (acc.double() + acc0.double() * (_x2_scale(w) if dt == "f16x2" else 1.0)).float()
     if dt != "f16x2":
         for k in range(0, K, 32):
             acc = (acc.double() + a64[:, k:k + 32] @ w64[:, k:k + 32].t()).float()
