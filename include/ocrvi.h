@@ -492,6 +492,68 @@ int ocrvi_jpeg_encode_table_entry(int width, int height, int components, int sub
 int ocrvi_jpeg_encode_pages(int device, const void* src_base, const int64_t* table_dev, int n_pages, void* out_base, int64_t* lengths_dev,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Result overlay: the page `--save_result` writes.  Replaces draw_boxes_with_text (src/pipeline/pipeline2.py:173-190) as the per-image
+ * loop calls it (:358-360) ahead of cv2.imwrite (:397-400): every box outlined, its 1-based index written beside it.  cv2.drawContours
+ * and cv2.putText are not reproduced (cv2 and its Hershey glyphs are absent from the build container; its thick lines are fixed-point
+ * convex fills): the rule below is the library's own, exact on integers, and parity with cv2 is UNPINNED.  tests/overlay_ref.py restates
+ * the rule in numpy int64 and in fractions.
+ *
+ * THE PAINTING RULE.  Everything painted is a list of segments with integer endpoints; segment number s (its ORDINAL, the position in
+ * the list) has a colour and a thickness T, 1 <= T <= 15.  Pixel (x, y) is its integer centre p.  For segment a -> b:
+ *     d = b - a,  L2 = d.d,  t = (p - a).d
+ *     t <= 0   (this includes a == b)   covered iff 4 |p - a|^2 <= T^2
+ *     t >= L2                           covered iff 4 |p - b|^2 <= T^2
+ *     otherwise, c = d.x (p - a).y - d.y (p - a).x:   covered iff c^2 <= floor(T^2 L2 / 4)
+ * (the last line is 4 dist^2 <= T^2 without the factor that would overflow).  A pixel no segment covers keeps its value and is not
+ * written.  A pixel several segments cover takes the colour of the one with the LARGEST ordinal -- the reference's sequential overdraw,
+ * independent of evaluation order: the kernel needs neither atomics on global memory nor an order between workgroups.
+ * Limits: page sides 1..16384, every endpoint (labels included) in [-16384, 16384]; all products then stay below 2^63 in int64.
+ * Anything else is OCRVI_EINVAL.  Endpoints outside the page are legal.  Hand check: (2,5) -> (8,5) with T = 2 paints
+ * {2 <= x <= 8, 4 <= y <= 6} and (1,5), (9,5): 23 pixels.
+ *
+ * THE SEGMENT ORDER.  For pair i = 0, 1, .. of a page (box i with its text; the strings themselves are never rendered, as in the
+ * reference, which writes str(idx + 1)):
+ *   1. the n_i closed edges v_k -> v_(k+1 mod n_i) of the box in the box colour (one vertex: one zero-length edge, a disc; two vertices:
+ *      the edge there and back).  A box without vertices contributes nothing, neither outline nor label; it keeps its index.
+ *   2. the label: top = the FIRST vertex of minimum y; text_pos = (top.x, top.y - 10); if text_pos.y < 20 then text_pos = (top.x, max_y +
+ *      20) with max_y the largest vertex y (pipeline2.py:182-187).  The decimal digits of i + 1, left to right, digit k with its origin at
+ *      (text_pos.x + 10 k, text_pos.y) (bottom-left, as cv2.putText), each as the strokes of a seven-stroke font, in the order A..G, in the
+ *      label colour and the same thickness:
+ *          A (0,-10)-(6,-10)  B (6,-10)-(6,-5)  C (6,-5)-(6,0)  D (0,0)-(6,0)  E (0,-5)-(0,0)  F (0,-10)-(0,-5)  G (0,-5)-(6,-5)
+ *          0 ABCDEF  1 BC  2 ABDEG  3 ABCDG  4 BCFG  5 ACDFG  6 ACDEFG  7 ABC  8 ABCDEFG  9 ABCDFG        (csrc/overlay_font.h)
+ * ------------------------------------------------------------------------------------------------ */
+#define OCRVI_OVERLAY_SEG 8        /* int32 fields of a segment: (a.x, a.y, b.x, b.y, colour = r | g << 8 | b << 16, T, pair index i, 0) */
+#define OCRVI_OVERLAY_PRIM 8       /* int32 fields of a primitive: (first segment, one past its last segment, x0, y0, x1, y1, kind, pair index i) */
+#define OCRVI_OVERLAY_MAX_COORD 16384
+/* Host only, needs no GPU.  Builds the segment table and the primitive table of n_pages pages.
+ *   points int32 [total][2], offs int32 [n_boxes + 1]: box j = points[offs[j] .. offs[j+1]) (the convention of ocrvi_min_area_quads);
+ *   page_boxes int32 [n_pages + 1]: page p owns boxes page_boxes[p] .. page_boxes[p+1]; page_pairs int32 [n_pages] or NULL: the number of
+ *   texts of page p -- only min(boxes, texts) pairs are drawn, as zip() does (NULL: every box); page_hw int32 [n_pages][2] = (h, w);
+ *   box_rgb, label_rgb: r | g << 8 | b << 16; thickness: T.
+ * A primitive is one box outline (kind 0) or one label (kind 1): its range of the segment table and the inclusive bounding box of its
+ * endpoints dilated by ceil(T / 2) on every side.  Primitives and segments are listed page by page in drawing order; prim_offs int32
+ * [n_pages + 1]: page p owns primitives prim_offs[p] .. prim_offs[p+1].  Segment numbers are indices into the one table of all pages.
+ * Sizes: *n_segs and *n_prims are always written; with segs, prims and prim_offs all NULL nothing else is (the size query; validation
+ * still runs).  Never more than sum n_i + 7 digits(i + 1) segments and two primitives per pair.  seg_cap / prim_cap: entries the
+ * tables hold.
+ * OCRVI_EINVAL with a message, nothing painted anywhere: a null pointer, n_pages < 0, a page side outside 1..16384, T outside 1..15, a
+ * colour above 0xffffff, offsets that run backwards, a vertex or a label endpoint outside [-16384, 16384], a table too small. */
+int ocrvi_overlay_segments(const int32_t* points, const int32_t* offs, const int32_t* page_boxes, const int32_t* page_pairs,
+                           const int32_t* page_hw /*[n_pages][2]*/, int n_pages, uint32_t box_rgb, uint32_t label_rgb, int thickness,
+                           int32_t* segs /*[seg_cap][OCRVI_OVERLAY_SEG]*/, int64_t seg_cap, int32_t* prims /*[prim_cap][OCRVI_OVERLAY_PRIM]*/,
+                           int64_t prim_cap, int32_t* prim_offs /*[n_pages + 1]*/, int64_t* n_segs, int64_t* n_prims);
+/* Paints n_pages pages IN PLACE in one launch (pipeline2.py:173-190 by the rule above).  pages: a page table (OCRVI_PAGE_ENTRY) of uint8
+ * HWC [h,w,3] pages; prims, segs, prim_offs: the tables of ocrvi_overlay_segments for the same pages, all in DEVICE memory; max_h, max_w:
+ * at least every page's height and width (they size the grid; 1..16384).  1 <= n_pages <= 65535.  Enqueue-only on `stream`: no
+ * allocation, no synchronisation; tables and pages are read when the kernel runs.  An invalid page entry is skipped and never
+ * dereferenced.  One workgroup per 64 x 16 tile: the page's primitive boxes are tested against the tile and the hits compacted in LDS, a
+ * tile without a hit ends there without touching the page; the hit primitives' segments are staged through LDS 256 at a time (those
+ * whose own dilated box misses the tile are dropped while staging) and every thread keeps, for its four pixels, the largest covering
+ * ordinal; only covered pixels are stored.  The result does not depend on the order of evaluation. */
+int ocrvi_overlay_pages(int device, const int64_t* pages, int n_pages, const int32_t* prims, const int32_t* segs, const int32_t* prim_offs,
+                        int max_h, int max_w, void* stream);
+
 /* Replaces DBPostProcessor(thresh, box_thresh, max_candidates, unclip_ratio).__call__ with .min_area (src/det/test.py:46-106) on a HOST
  * probability map prob[H*W] (the reference also runs this stage on the CPU after `.cpu().numpy()`, pipeline2.py:320-321).
  * Output: the unclipped polygons as int32 (x, y) pairs in points[2*cap_points]; box i owns points box_offsets[i] .. box_offsets[i+1]

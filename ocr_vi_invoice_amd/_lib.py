@@ -42,6 +42,7 @@ EXPORTS = [
     "ocrvi_test_bneck_tail",
     "ocrvi_jpeg_quant_tables", "ocrvi_jpeg_encode_header", "ocrvi_jpeg_encode_sizes", "ocrvi_jpeg_encode_table_entry", "ocrvi_jpeg_encode_pages",
     "ocrvi_test_gemm_raw", "ocrvi_test_ring_plan",
+    "ocrvi_overlay_segments", "ocrvi_overlay_pages",
 ]
 PAGE_ENTRY = 4          # int64 fields of one page-table entry: (device address, height, width, 0) -- OCRVI_PAGE_ENTRY
 # ocrvi_det_eval's record: 13 slots of 8 bytes (OCRVI_DET_EVAL_*), the first six int64, the rest float64
@@ -58,6 +59,9 @@ DB_TARGET_MAX_SIDE = 16384      # OCRVI_DB_TARGET_MAX_SIDE
 JPEG_ENTRY = 64                 # int64 fields of one ocrvi_jpeg_decode_pages table entry -- OCRVI_JPEG_ENTRY
 JPEG_ENC_ENTRY = 64             # int64 fields of one ocrvi_jpeg_encode_pages table entry -- OCRVI_JPEG_ENC_ENTRY
 JPEG_HEADER_MAX = 640           # OCRVI_JPEG_HEADER_MAX
+OVERLAY_SEG = 8                 # int32 fields of one overlay segment -- OCRVI_OVERLAY_SEG
+OVERLAY_PRIM = 8                # int32 fields of one overlay primitive -- OCRVI_OVERLAY_PRIM
+OVERLAY_MAX_COORD = 16384       # OCRVI_OVERLAY_MAX_COORD: page sides 1..16384, endpoints within +-16384
 
 
 class DetCfg(C.Structure):
@@ -181,6 +185,9 @@ def load() -> C.CDLL:
     lib.ocrvi_jpeg_encode_sizes.argtypes = [i32, i32, i32, i32, C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]
     lib.ocrvi_jpeg_encode_table_entry.argtypes = [i32, i32, i32, i32, i32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp]
     lib.ocrvi_jpeg_encode_pages.argtypes = [i32, vp, vp, i32, vp, vp, vp, sz, vp]
+    lib.ocrvi_overlay_segments.argtypes = [vp, vp, vp, vp, vp, i32, C.c_uint32, C.c_uint32, i32, vp, C.c_int64, vp, C.c_int64, vp,
+                                           C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.ocrvi_overlay_pages.argtypes = [i32, vp, i32, vp, vp, vp, i32, i32, vp]
     lib.ocrvi_db_target_jobs.argtypes = [vp, vp, vp, vp, i32, C.c_double, i32, vp, i32, vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                          C.POINTER(C.c_int32), i32]
     lib.ocrvi_db_target_maps.argtypes = [i32, vp, i32, vp, i32, vp, i32, i32, C.c_float, f32p, f32p, f32p, f32p, vp]

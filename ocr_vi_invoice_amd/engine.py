@@ -28,7 +28,7 @@ import torch
 
 from . import _lib
 from .pipeline import (JPEG_BYTES, DBPostProcessor, _check_crop, db_boxes_pages, enhance_init, enhance_workspace_bytes, four_point_geometry,
-                       jpeg_info_struct, jpeg_parse_into, jpeg_table_entry, quad_crops)
+                       jpeg_info_struct, jpeg_parse_into, jpeg_table_entry, overlay_paint_, overlay_segments, quad_crops)
 
 _ARENA_ALIGN = 256
 _STREAMS: Dict[int, Tuple[torch.cuda.Stream, torch.cuda.Stream]] = {}
@@ -113,11 +113,16 @@ class Engine:
     coefficient stream goes through pinned staging with its chunk and ``ocrvi_jpeg_decode_pages`` decodes it straight into its arena
     slot (into the raw region when it has a quad), ahead of the chunk's warp and enhancement.  The results are those of the same page
     passed as the array ``pipeline.imdecode`` returns.
+    ``annotate=True`` (the constructor's argument, or the attribute set between runs; ``run``'s own parameters stay as they were): each
+    page's result is a 4-tuple ``(boxes, scores, texts, annotated)``; ``annotated`` is a
+    new device uint8 tensor: the page as the detector saw it (rectified and enhanced where asked for, as the reference draws on its
+    preprocessed ``original_image``, pipeline2.py:358-360) with ``pipeline.draw_boxes_with_text(page, boxes, texts)`` painted on it -- per
+    wave, one copy per page out of the arena and one ``ocrvi_overlay_pages`` launch.  The arena and the caller's tensors are never written.
     The captured graphs hold the models' weights as they were: after reloading a model's weights, build a new Engine."""
 
     def __init__(self, det_model, rec_model, post_processor: DBPostProcessor, det_size: int = 960, rec_size: Tuple[int, int] = (32, 256),
                  det_chunk: int = 16, rec_batch: int = 256, max_pages: int = 256, graphs: bool = True, graph_cache: int = 16,
-                 post_threads: int = 0, prob_hook=None, binary_head: bool = False, crop: str = "rect"):
+                 post_threads: int = 0, prob_hook=None, binary_head: bool = False, crop: str = "rect", annotate: bool = False):
         rh, rw = int(rec_size[0]), int(rec_size[1])
         if rh <= 0 or rw <= 0 or rh % 16 or rw % 4:
             raise ValueError(f"rec_size {rec_size}: the height must be a multiple of 16 and the width of 4")
@@ -206,6 +211,8 @@ class Engine:
         self._rec_graph = None
         self._rec_warm = False
         self._pool = None                          # host threads of the JPEG entropy decoder, started with the first file
+        self.annotate = bool(annotate)             # read at the start of every run; may be switched between runs
+        self._annotate, self._annotated = False, []   # the running call's switch and its painted copies of the pages
         self.stats = {}
 
     # ------------------------------------------------------------------------------------------------ device work (enqueue-only)
@@ -556,11 +563,27 @@ class Engine:
             self._decode_oldest()
         self.s_det.synchronize()
         self.s_rec.synchronize()                   # (the table upload, even when the wave produced no crop)
+        if self._annotate:
+            self._annotate_wave(wave)
         self._keep = []
+
+    def _annotate_wave(self, wave):
+        """``annotate=True``: every page of the drained wave is copied out of the arena into a tensor of its own, and all copies
+        are painted with the wave's boxes and region numbers by one ``ocrvi_overlay_pages`` launch (``pipeline.draw_boxes_pages`` without
+        its upload of pixels), on the caller's stream.  Nothing writes the arena; the next wave reuses it, so the copies are waited for."""
+        outs = []
+        for slot, i in enumerate(wave):
+            (h, w), off, nb = self._sizes[i], self._offs[slot], self._nbytes[slot]
+            outs.append(self.arena[off:off + nb].clone().view(h, w, 3))
+        overlay_paint_(outs, *overlay_segments([self._boxes[i] for i in wave], [self._texts[i] for i in wave], [self._sizes[i] for i in wave]))
+        torch.cuda.current_stream(self.dev).synchronize()
+        for i, out in zip(wave, outs):
+            self._annotated[i] = out
 
     # ------------------------------------------------------------------------------------------------ public
     def run(self, pages: Sequence, quads: Sequence = None, enhance=None) -> List[Tuple[list, list, list]]:
         pages = list(pages)
+        self._annotate, self._annotated = bool(self.annotate), [None] * len(pages)
         t_start = time.perf_counter()              # (total_s includes the host entropy decode of JPEG pages)
         infos = {i: jpeg_info_struct(p, f"page {i}") for i, p in enumerate(pages) if isinstance(p, JPEG_BYTES)}
         raw_sizes = [self._check_page(i, p, infos.get(i)) for i, p in enumerate(pages)]
@@ -624,4 +647,7 @@ class Engine:
                 raise OverflowError(msg)
             _lib.check(rc)
         self.stats["total_s"] = time.perf_counter() - t_start
+        if self._annotate:
+            annotated, self._annotated = self._annotated, []
+            return [(self._boxes[i], self._scores[i], self._texts[i], annotated[i]) for i in range(len(pages))]
         return [(self._boxes[i], self._scores[i], self._texts[i]) for i in range(len(pages))]

@@ -5,7 +5,8 @@ Same names and argument meaning as the reference for the pieces either side of t
 ``recognize_text_batch`` (:144), ``resize_image_for_det`` (:33), ``crop_image`` (src/det/test.py:123) plus ``normalize_for_det`` (the
 inline code at :312-314), ``rescale_boxes`` (:324-328) and ``detect_and_recognize`` (steps 2-3 of the per-image loop, :306-352), and the geometric half of step 1
 (``four_point_transform``, ``preprocess_image``: src/preprocess/scanner.py:29-53,168-196 with the corners supplied by the caller) and
-its enhancement half (``enhance_document``, scanner.py:55-76).
+its enhancement half (``enhance_document``, scanner.py:55-76); ``draw_boxes_with_text`` (:173) and, for the ``--save_result`` branch
+(:358-360 + :397-400), ``save_result``.
 Image resizing and crop pre-processing run on the GPU (ocrvi_crop_resize_normalize / ocrvi_normalize_u8).
 
 ``DBPostProcessor`` (src/det/test.py:46-106) is the host C++ implementation behind ``ocrvi_db_postprocess``; like the reference's, it works on
@@ -881,6 +882,154 @@ def imwrite(path: str, image, quality: int = 95, subsampling: str = "4:2:0", dev
     except OSError:
         return False
     return True
+
+
+# ---------------------------------------------------------------------------------------------------- result overlay
+def _overlay_rgb(c, what: str) -> int:
+    try:
+        r, g, b = (int(v) for v in c)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: expected three integers 0..255, got {c!r}") from None
+    if not all(0 <= v <= 255 for v in (r, g, b)):
+        raise ValueError(f"{what}: expected three integers 0..255, got {c!r}")
+    return r | g << 8 | b << 16
+
+
+def _overlay_vertices(polys, names) -> np.ndarray:
+    """``box.astype(np.int32)`` (pipeline2.py:176) for every box at once, the range checked first: int32 [total, 2].  ``polys``: the
+    boxes as arrays of shape (n_i, 2) (empty ones of any shape); ``names(j)`` describes box j in an error message."""
+    for j, v in enumerate(polys):
+        if v.size and (v.dtype.kind not in "iuf" or v.ndim != 2 or v.shape[1] != 2):
+            raise ValueError(f"{names(j)}: expected an (n, 2) array of numbers, got dtype {v.dtype} shape {v.shape}")
+    full = [v for v in polys if v.size]
+    if not full:
+        return np.empty((0, 2), np.int32)
+    pts = np.concatenate(full, 0)
+    if pts.dtype.kind == "f":
+        pts = np.trunc(pts)
+    ok = np.abs(pts) <= _lib.OVERLAY_MAX_COORD          # (False for NaN)
+    if not ok.all():
+        row = int(np.argmin(ok.all(1)))
+        j = int(np.searchsorted(np.cumsum([len(v) if v.size else 0 for v in polys]), row, side="right"))
+        raise ValueError(f"{names(j)}: vertices must lie in [-{_lib.OVERLAY_MAX_COORD}, {_lib.OVERLAY_MAX_COORD}]")
+    return np.ascontiguousarray(pts, np.int32)
+
+
+def overlay_segments(boxes_per_page, texts_per_page, sizes, color=(0, 255, 0), label_color=(255, 0, 0), thickness: int = 2):
+    """``ocrvi_overlay_segments`` (host only, needs no GPU): the segments and primitives ``draw_boxes_pages`` paints for pages of
+    ``sizes[p] = (h, w)``: (segs int32 [n, 8], prims int32 [m, 8], prim_offs int32 [pages + 1]); include/ocrvi.h states the fields, the
+    painting rule, the segment order and the digit strokes.  ``texts_per_page`` is None or, per page, None or the page's texts: only
+    ``min(len(boxes), len(texts))`` pairs are drawn, as the reference's zip does.  ValueError for what the entry refuses."""
+    n = len(boxes_per_page)
+    if len(sizes) != n or (texts_per_page is not None and len(texts_per_page) != n):
+        raise ValueError(f"overlay: {n} box lists, {len(sizes)} pages, {None if texts_per_page is None else len(texts_per_page)} text lists")
+    if isinstance(thickness, bool) or not isinstance(thickness, (int, np.integer)):
+        raise ValueError(f"overlay: thickness {thickness!r} (an integer 1..15 expected)")
+    box_rgb, label_rgb = _overlay_rgb(color, "overlay: color"), _overlay_rgb(label_color, "overlay: label_color")
+    polys, page_boxes, pairs = [], [0], []
+    none = np.empty((0, 2), np.int32)
+    for p, boxes in enumerate(boxes_per_page):
+        texts = None if texts_per_page is None else texts_per_page[p]
+        pairs.append(len(boxes) if texts is None else min(len(boxes), len(texts)))
+        # a box past the last pair is never drawn and, as under the reference's zip, never looked at: it travels as a box without vertices
+        polys.extend(np.asarray(b) if j < pairs[-1] else none for j, b in enumerate(boxes))
+        page_boxes.append(len(polys))
+
+    def names(j):
+        p = int(np.searchsorted(page_boxes, j, side="right")) - 1
+        return f"overlay: page {p} box {j - page_boxes[p]}"
+
+    pts = _overlay_vertices(polys, names)
+    offs = np.zeros(len(polys) + 1, np.int32)
+    if polys:
+        offs[1:] = np.cumsum([len(v) if v.size else 0 for v in polys])
+    page_boxes, pairs = np.asarray(page_boxes, np.int32), np.asarray(pairs, np.int32)
+    hw = np.ascontiguousarray(np.asarray([(int(h), int(w)) for h, w in sizes], np.int64).reshape(n, 2).clip(-1, 1 << 30), np.int32)
+    lib = _lib.load()
+    ns, npr = ctypes.c_int64(), ctypes.c_int64()
+
+    # the documented upper bound sizes the tables: sum n_i + 7 digits segments, two primitives per pair (one call, which validates everything)
+    total = int(pairs.sum())
+    segs = np.empty((len(pts) + 7 * len(str(max(int(pairs.max()) if n else 0, 1))) * total, _lib.OVERLAY_SEG), np.int32)
+    prims, prim_offs = np.empty((2 * total, _lib.OVERLAY_PRIM), np.int32), np.zeros(n + 1, np.int32)
+    _lib.check(lib.ocrvi_overlay_segments(pts.ctypes.data, offs.ctypes.data, page_boxes.ctypes.data, pairs.ctypes.data, hw.ctypes.data, n, box_rgb,
+                                          label_rgb, int(thickness), segs.ctypes.data, len(segs), prims.ctypes.data, len(prims),
+                                          prim_offs.ctypes.data, ctypes.byref(ns), ctypes.byref(npr)))
+    return segs[:ns.value], prims[:npr.value], prim_offs
+
+
+def overlay_upload(pages: Sequence[torch.Tensor], segs: np.ndarray, prims: np.ndarray, prim_offs: np.ndarray) -> Tuple[torch.Tensor, tuple]:
+    """The page table of the device pages ``pages`` and the three tables of ``overlay_segments`` in one pinned buffer and one copy:
+    (the device buffer, the arguments of ``ocrvi_overlay_pages`` after the device index).  Every table starts on a 16-byte boundary."""
+    n = len(pages)
+    o_offs = n * _lib.PAGE_ENTRY * 2            # in int32 words
+    o_prims = o_offs + (n + 1 + 3) // 4 * 4
+    o_segs = o_prims + prims.size
+    host = torch.zeros(o_segs + max(segs.size, 4), dtype=torch.int32).pin_memory()
+    h = host.numpy()
+    h[:o_offs].view(np.int64).reshape(n, _lib.PAGE_ENTRY)[:] = [(t.data_ptr(), t.shape[0], t.shape[1], 0) for t in pages]
+    h[o_offs:o_offs + n + 1] = prim_offs
+    h[o_prims:o_segs] = prims.reshape(-1)
+    h[o_segs:o_segs + segs.size] = segs.reshape(-1)
+    dev = host.to(pages[0].device, non_blocking=True)
+    base = dev.data_ptr()
+    return dev, (base, n, base + 4 * o_prims, base + 4 * o_segs, base + 4 * o_offs, max(t.shape[0] for t in pages), max(t.shape[1] for t in pages))
+
+
+def overlay_paint_(pages: Sequence[torch.Tensor], segs: np.ndarray, prims: np.ndarray, prim_offs: np.ndarray) -> None:
+    """Paints the contiguous device pages ``pages`` IN PLACE on the current stream: one upload, one ``ocrvi_overlay_pages`` launch."""
+    if not len(pages) or not len(prims):
+        return                                  # nothing to paint
+    device = pages[0].device
+    with torch.cuda.device(device):
+        dev, args = overlay_upload(pages, segs, prims, prim_offs)
+        _lib.check(_lib.load().ocrvi_overlay_pages(_dev_index(device), *args, torch.cuda.current_stream(device).cuda_stream))
+
+
+def draw_boxes_pages(images, boxes_per_page, texts_per_page=None, color=(0, 255, 0), label_color=(255, 0, 0), thickness: int = 2,
+                     device: str = "cuda:0") -> List[torch.Tensor]:
+    """``draw_boxes_with_text`` for a list of pages of any sizes: one segment build on the host (``ocrvi_overlay_segments``), one upload
+    of the tables and one launch (``ocrvi_overlay_pages``) serve all pages.  Returns a list of new device tensors; no input is written."""
+    images = list(images)
+    sizes = []
+    for i, im in enumerate(images):
+        if not isinstance(im, (np.ndarray, torch.Tensor)):
+            raise ValueError(f"draw_boxes: page {i}: expected a numpy array or a tensor, got {type(im).__name__}")
+        if im.dtype not in (np.uint8, torch.uint8) or im.ndim != 3 or im.shape[2] != 3:
+            raise ValueError(f"draw_boxes: page {i}: expected an RGB uint8 HxWx3 page, got dtype {im.dtype} shape {tuple(im.shape)}")
+        sizes.append((int(im.shape[0]), int(im.shape[1])))
+    if len(boxes_per_page) != len(images):
+        raise ValueError(f"draw_boxes: {len(boxes_per_page)} box lists for {len(images)} pages")
+    if not images:
+        return []
+    tables = overlay_segments(boxes_per_page, texts_per_page, sizes, color, label_color, thickness)   # (every ValueError before device work)
+    dev = torch.device(device)
+    outs = []
+    for im in images:                           # the reference's .copy() (pipeline2.py:174): always a new tensor
+        src = torch.from_numpy(np.ascontiguousarray(im)) if isinstance(im, np.ndarray) else im
+        out = torch.empty(tuple(src.shape), dtype=torch.uint8, device=dev)
+        out.copy_(src)
+        outs.append(out)
+    overlay_paint_(outs, *tables)
+    return outs
+
+
+def draw_boxes_with_text(image, boxes, texts=None, color=(0, 255, 0), label_color=(255, 0, 0), thickness: int = 2,
+                         device: str = "cuda:0") -> torch.Tensor:
+    """``draw_boxes_with_text(image, boxes, texts)`` of the reference (pipeline2.py:173-190, called at :358-360) on the device: every box
+    outlined in ``color``, its 1-based index written at the reference's label position in ``label_color``; the strings of ``texts`` are
+    never rendered, they only bound the number of pairs (zip), ``None`` = every box.  ``image``: RGB uint8 HxWx3, numpy or tensor, host or
+    device (a grey or otherwise shaped page: ValueError).  Returns a new device tensor; ``image`` is not modified.
+    The pixels follow the library's own integer rule (include/ocrvi.h, "Result overlay": segments of thickness 1..15 with round caps, a
+    seven-stroke digit font) and equal tests/overlay_ref.py bit for bit; cv2.drawContours / cv2.putText parity is unpinned (cv2 and its
+    Hershey glyphs are absent).  Page sides up to 16384, vertices within +-16384."""
+    return draw_boxes_pages([image], [boxes], None if texts is None else [texts], color, label_color, thickness, device)[0]
+
+
+def save_result(path: str, image, boxes, texts=None, quality: int = 95, device: str = "cuda:0") -> bool:
+    """The reference's ``--save_result`` (pipeline2.py:358-360 + :397-400): ``draw_boxes_with_text`` then ``imwrite``; only the JPEG bytes
+    leave the device.  Returns what ``imwrite`` returns."""
+    return imwrite(path, draw_boxes_with_text(image, boxes, texts, device=device), quality, device=device)
 
 
 def detect_and_recognize(original_image, det_model, rec_model, post_processor: DBPostProcessor, device: str = "cuda:0", det_size: int = 640,
