@@ -5,7 +5,6 @@
 #include <algorithm>
 #include <memory>
 
-#include "gemm_ring.h"
 #include "model.h"
 
 using namespace ocrvi;
@@ -16,7 +15,7 @@ const int kWidth[4] = {64, 128, 256, 512};
 // One residual block.  Bottleneck (ResNet-50): conv1 1x1, conv2 3x3 (the stride; deformable in layers 2-4), conv3 1x1 + identity.
 // BasicBlock (ResNet-18, torchvision.models.resnet.BasicBlock): conv1 3x3 (the stride), conv2 3x3 stride 1 (deformable in layers 2-4,
 // backbone.py:39-53 replaces every block's conv2) + identity; no conv3.
-struct Bottleneck {
+struct ResBlock {
     ConvLayer conv1, conv2, off, conv3, down;
     bool dcn = false, has_down = false;
     int stride = 1;
@@ -33,7 +32,7 @@ struct ocrvi_det {
     ocrvi_det_cfg cfg{};
     DeviceStore store;
     ConvLayer stem;
-    std::vector<Bottleneck> layers[4];
+    std::vector<ResBlock> layers[4];
     ConvLayer lat[4], fpn[4];
     float *asf_w = nullptr, *asf_b = nullptr;
     ConvLayer head_conv, head_dc1;
@@ -78,7 +77,7 @@ extern "C" int ocrvi_det_create(int device, const void* blob_p, size_t blob_byte
         const int nblk = basic ? kBlocks18[li] : kBlocks50[li];
         h->layers[li].resize(nblk);
         for (int b = 0; b < nblk; ++b) {
-            Bottleneck& bk = h->layers[li][b];
+            ResBlock& bk = h->layers[li][b];
             const std::string p = "layer" + std::to_string(li + 1) + "." + std::to_string(b);
             bk.dcn = use_dcn && li >= 1;               // backbone.py:28-31: DCN in layer2..4
             bk.stride = (b == 0 && li >= 1) ? 2 : 1;   // torchvision Bottleneck v1.5: stride on the 3x3 (BasicBlock: on conv1)
@@ -95,7 +94,7 @@ extern "C" int ocrvi_det_create(int device, const void* blob_p, size_t blob_byte
         // The fused layer1 chain: by shape only (f16x2, conv2 64 -> 64 packed for conv3_halo, conv3 64 -> 256, the next conv1 256 -> 64);
         // a layer's last block has no successor in the layer (layer2.0.conv1 is 256 -> 128) and ends at y.
         for (int b = 0; b < nblk && !basic && dt == OCRVI_F16X2; ++b) {
-            Bottleneck& bk = h->layers[li][b];
+            ResBlock& bk = h->layers[li][b];
             if (bk.dcn || bk.stride != 1 || !bk.conv2.quartets || w != 64 || bk.conv2.Np != 64 || bk.conv2.Cin_g != 64) continue;
             const std::string p = "layer" + std::to_string(li + 1) + "." + std::to_string(b);
             const std::string pn = "layer" + std::to_string(li + 1) + "." + std::to_string(b + 1);
@@ -146,11 +145,7 @@ extern "C" int ocrvi_det_create(int device, const void* blob_p, size_t blob_byte
         w2.insert(w2.end(), b2.begin(), b2.end());
         OCRVI_TRY(st.upload_f32(w2, &h->dc2_wb));
     }
-    {   // scratch pages of the ring GEMM: allocate now so no forward (possibly under graph capture) ever allocates
-        const void* z; void* d;
-        OCRVI_TRY(ring_pages(&z, &d));
-    }
-    if (dt == OCRVI_F16X2) OCRVI_TRY(h->range.init());
+    OCRVI_TRY(finish_create(dt, h->range));
     *out = h.release();
     return OCRVI_OK;
 }
@@ -171,257 +166,236 @@ static int check_det_shape(const ocrvi_det* h, int N, int H, int W) {
     return OCRVI_OK;
 }
 
-// binary_head: the head of ocrvi_det_forward_binary -- the binarise branch alone, its probability written by the deconvolution's epilogue
-// (thresh / tbin / blog / tlog are not used).  Backbone, FPN and ASF are the same launches either way.
-static int det_run(ocrvi_det* h, Runner& r, const float* x, int N, int H, int W, float* binary, float* thresh, float* tbin, float* blog,
-                   float* tlog, bool binary_head = false) {
-    const int dt = h->cfg.dtype;
-    const int Hp = H + 6, Wp = W + 8;
+static ConvOpts conv_opts(int stride, int pad, int act) {
+    ConvOpts o;
+    o.sh = o.sw = stride; o.pad = pad; o.act = act;
+    return o;
+}
+
+// ---- stem: conv 7x7/2 + BN + ReLU, maxpool 3x3/2 (torchvision resnet50 via backbone.py:34)
+static int det_stem(const ocrvi_det& h, Runner& r, const float* x, int N, int H, int W, Tensor* out) {
+    const int dt = h.cfg.dtype, Hp = H + 6, Wp = W + 8;
     Tensor xpad = r.alloc(N, Hp, Wp, 4);
     if (!r.dry()) OCRVI_TRY(k_nchw3_to_nhwc4_pad(dt, x, xpad.p, N, H, W, 3, 3, Hp, Wp, r.stream));
-    // ---- stem: conv 7x7/2 + BN + ReLU, maxpool 3x3/2 (torchvision resnet50 via backbone.py:34)
-    Tensor cur;
-    if (stem_pool_eligible(dt, h->stem.N_g, h->stem.Kp, h->stem.KH, H, W)) {
+    if (stem_pool_eligible(dt, h.stem.N_g, h.stem.Kp, h.stem.KH, H, W)) {
         // f16x2: one kernel; the half-resolution 64-channel map (the detector's largest tensor) is never written (stem_pool.hip)
-        cur = r.alloc(N, H / 4, W / 4, 64);
-        if (!r.dry()) OCRVI_TRY(k_stem_pool(dt, xpad.p, h->stem.w, h->stem.bias, h->stem.wscale, cur.p, N, H, W, Hp, Wp, r.stream));
-    } else {
-        Tensor s = r.alloc(N, H / 2, W / 2, 64);
-        {
-            ConvOpts o;
-            o.sh = o.sw = 2; o.pad = 3; o.act = ACT_RELU; o.Hp = Hp; o.Wp = Wp;
-            OCRVI_TRY(conv(r, h->stem, xpad, s, o));
-        }
-        cur = r.alloc(N, H / 4, W / 4, 64);
-        if (!r.dry()) OCRVI_TRY(k_maxpool3x3s2(dt, s.p, cur.p, N, H / 2, W / 2, 64, r.stream));
+        *out = r.alloc(N, H / 4, W / 4, 64);
+        if (!r.dry()) OCRVI_TRY(k_stem_pool(dt, xpad.p, h.stem.w, h.stem.bias, h.stem.wscale, out->p, N, H, W, Hp, Wp, r.stream));
+        return OCRVI_OK;
     }
-    // ---- layers 1..4.  Block outputs ping-pong between two slots per layer (sized for the layer's output); the last block of a
-    // layer writes a fresh buffer that stays live as the c2..c5 tap (backbone.py:56-60).  Temporaries of a block are released
-    // when it ends, so a chunk of 16 pages keeps ~4 GB less live than with one buffer per block.
-    Tensor feats[4];
-    for (int li = 0; li < 4; ++li) {
-        const int w = kWidth[li], cw = h->expansion * w;
-        const int nb = (int)h->layers[li].size();
-        const int lh = cur.h / h->layers[li][0].stride, lw = cur.w / h->layers[li][0].stride;
-        Tensor tap = r.alloc(N, lh, lw, cw);                          // the layer's final output
-        const size_t slot_mark = r.arena.mark();
-        Tensor slot[2] = {r.alloc(N, lh, lw, cw), r.alloc(N, lh, lw, cw)};
-        // Fused chains (bneck_tail.h): block b reads t1 from t1pp[b & 1] and writes the next block's into the other one, so both live
-        // outside the blocks' own marks (released with the slots); t2 is never allocated.
-        const bool fused_layer = !h->basic && h->layers[li][0].tail;
-        Tensor t1pp[2];
-        if (fused_layer) { t1pp[0] = r.alloc(N, lh, lw, w); t1pp[1] = r.alloc(N, lh, lw, w); }
-        bool have_t1 = false;   // the previous block's launch has written this block's t1
-        for (int b = 0; b < nb; ++b) {
-            const Bottleneck& bk = h->layers[li][b];
-            const int oh = cur.h / bk.stride, ow = cur.w / bk.stride;
-            Tensor y = b == nb - 1 ? tap : slot[b & 1];               // never the buffer `cur` lives in (slot[(b-1)&1] or the previous tap)
-            const size_t mark2 = r.arena.mark();
-            if (fused_layer && bk.tail) {
-                Tensor t1 = t1pp[b & 1];
-                if (!have_t1) {
-                    ConvOpts o;
-                    o.act = ACT_RELU;
-                    OCRVI_TRY(conv(r, bk.conv1, cur, t1, o));
-                }
-                Tensor idn = cur;
-                if (bk.has_down) {
-                    idn = r.alloc(N, oh, ow, 4 * w);
-                    ConvOpts o;
-                    OCRVI_TRY(conv(r, bk.down, cur, idn, o));
-                }
-                OCRVI_CHECK(idn.c == 256 && y.c == 256 && t1.c == 64 && !idn.f32 && !y.f32, OCRVI_EINVAL, "det: fused layer1 chain on a foreign shape");
-                if (!r.dry()) {
-                    BneckTailParams q;
-                    q.x = t1.p; q.w2 = bk.conv2.w; q.wt = bk.tail_w; q.bias2 = bk.conv2.bias; q.bias_t = bk.tail_bias;
-                    q.idn = idn.p; q.y = y.p; q.t1n = bk.tail_c ? t1pp[(b + 1) & 1].p : nullptr;
-                    q.n_img = N; q.H = oh; q.W = ow;
-                    q.ws2 = bk.conv2.wscale; q.ws3 = bk.tail_ws3; q.ws1 = bk.tail_ws1;
-                    OCRVI_TRY(launch_bneck_tail(q, r.stream));
-                }
-                have_t1 = bk.tail_c;
-                r.arena.release(mark2);   // the downsample output is dead
-                cur = y;
-                continue;
-            }
-            if (h->basic) {
-                // BasicBlock: relu(bn2(conv2(relu(bn1(conv1(x))))) + identity); conv1 carries the stride and is never deformable, the
-                // residual and the final ReLU sit in conv2's epilogue (the pipelined deformable kernel's RES build in the 16-bit / f16x2 modes)
-                Tensor t1 = r.alloc(N, oh, ow, w);
-                {
-                    ConvOpts o;
-                    o.sh = o.sw = bk.stride; o.pad = 1; o.act = ACT_RELU;
-                    OCRVI_TRY(conv(r, bk.conv1, cur, t1, o));
-                }
-                Tensor idn = cur;
-                if (bk.has_down) {
-                    idn = r.alloc(N, oh, ow, w);
-                    ConvOpts o;
-                    o.sh = o.sw = bk.stride;
-                    OCRVI_TRY(conv(r, bk.down, cur, idn, o));
-                }
-                ConvOpts o;
-                o.pad = 1; o.act = ACT_RELU; o.res = &idn; o.res_mode = RES_SAME;
-                if (bk.dcn) {   // DeformableConv2d.forward (dcn.py:41-59) at stride 1
-                    float* offs = (float*)r.arena.alloc((size_t)N * oh * ow * 32 * 4);
-                    Tensor ot; ot.p = offs; ot.n = N; ot.h = oh; ot.w = ow; ot.c = 32; ot.f32 = true;
-                    ConvOpts oo;
-                    oo.pad = 1; oo.store_mode = ST_DCN_OFFS;
-                    OCRVI_TRY(conv(r, bk.off, t1, ot, oo));
-                    o.offs = offs;
-                }
-                OCRVI_TRY(conv(r, bk.conv2, t1, y, o));
-                r.arena.release(mark2);
-                cur = y;
-                continue;
-            }
-            Tensor t1 = r.alloc(N, cur.h, cur.w, w);
-            Tensor t2 = r.alloc(N, oh, ow, w);
-            {
-                ConvOpts o;
-                o.act = ACT_RELU;
-                OCRVI_TRY(conv(r, bk.conv1, cur, t1, o));
-            }
-            if (bk.dcn) {
-                // DeformableConv2d.forward (dcn.py:41-59): 27-ch conv -> offsets (ch 0..17) + sigmoid mask (ch 18..26) -> deform_conv2d
-                float* offs = (float*)r.arena.alloc((size_t)N * oh * ow * 32 * 4);
-                Tensor ot; ot.p = offs; ot.n = N; ot.h = oh; ot.w = ow; ot.c = 32; ot.f32 = true;
-                ConvOpts oo;
-                oo.sh = oo.sw = bk.stride; oo.pad = 1; oo.store_mode = ST_DCN_OFFS;
-                OCRVI_TRY(conv(r, bk.off, t1, ot, oo));
-                ConvOpts o;
-                o.sh = o.sw = bk.stride; o.pad = 1; o.act = ACT_RELU; o.offs = offs;
-                OCRVI_TRY(conv(r, bk.conv2, t1, t2, o));
-            } else {
-                ConvOpts o;
-                o.sh = o.sw = bk.stride; o.pad = 1; o.act = ACT_RELU;
-                OCRVI_TRY(conv(r, bk.conv2, t1, t2, o));
-            }
-            Tensor idn = cur;
-            if (bk.has_down) {
-                idn = r.alloc(N, oh, ow, 4 * w);
-                ConvOpts o;
-                o.sh = o.sw = bk.stride;
-                OCRVI_TRY(conv(r, bk.down, cur, idn, o));
-            }
-            {
-                ConvOpts o;
-                o.act = ACT_RELU; o.res = &idn; o.res_mode = RES_SAME;
-                OCRVI_TRY(conv(r, bk.conv3, t2, y, o));
-            }
-            r.arena.release(mark2);  // t1, t2, offsets, downsample are dead
-            cur = y;
+    Tensor s = r.alloc(N, H / 2, W / 2, 64);
+    ConvOpts o = conv_opts(2, 3, ACT_RELU);
+    o.Hp = Hp; o.Wp = Wp;
+    OCRVI_TRY(conv(r, h.stem, xpad, s, o));
+    *out = r.alloc(N, H / 4, W / 4, 64);
+    if (!r.dry()) OCRVI_TRY(k_maxpool3x3s2(dt, s.p, out->p, N, H / 2, W / 2, 64, r.stream));
+    return OCRVI_OK;
+}
+
+// ---- the pieces of a residual block.  Each block kind below allocates its temporaries in its own order, and the workspace size is the
+// peak of that sequence: the order is part of what a block computes, not a detail to tidy.
+
+// The identity branch: x itself, or the block's 1x1 downsample conv of it (the stride) into a fresh buffer of y's shape.
+static int identity(Runner& r, const ResBlock& bk, const Tensor& x, const Tensor& y, Tensor* idn) {
+    *idn = x;
+    if (!bk.has_down) return OCRVI_OK;
+    *idn = r.alloc(y.n, y.h, y.w, y.c);
+    return conv(r, bk.down, x, *idn, conv_opts(bk.stride, 0, ACT_NONE));
+}
+
+// DeformableConv2d.forward (dcn.py:41-59), first half: 27-ch conv -> offsets (ch 0..17) + sigmoid mask (ch 18..26), 32 fp32 per output
+// pixel in a fresh buffer; the deformable conv2 that reads them is the caller's.
+static int dcn_offsets(Runner& r, const ResBlock& bk, const Tensor& x, int oh, int ow, int stride, const float** offs) {
+    Tensor ot = wrap(r.arena.alloc((size_t)x.n * oh * ow * 32 * 4), x.n, oh, ow, 32, true);
+    ConvOpts o = conv_opts(stride, 1, ACT_NONE);
+    o.store_mode = ST_DCN_OFFS;
+    OCRVI_TRY(conv(r, bk.off, x, ot, o));
+    *offs = (const float*)ot.p;
+    return OCRVI_OK;
+}
+
+// Bottleneck: t1, t2, the offsets, then the downsample output.
+static int bottleneck(Runner& r, const ResBlock& bk, const Tensor& x, const Tensor& y, int w) {
+    Tensor t1 = r.alloc(x.n, x.h, x.w, w);
+    Tensor t2 = r.alloc(x.n, y.h, y.w, w);
+    OCRVI_TRY(conv(r, bk.conv1, x, t1, conv_opts(1, 0, ACT_RELU)));
+    ConvOpts o2 = conv_opts(bk.stride, 1, ACT_RELU);
+    if (bk.dcn) OCRVI_TRY(dcn_offsets(r, bk, t1, y.h, y.w, bk.stride, &o2.offs));
+    OCRVI_TRY(conv(r, bk.conv2, t1, t2, o2));
+    Tensor idn;
+    OCRVI_TRY(identity(r, bk, x, y, &idn));
+    ConvOpts o3 = conv_opts(1, 0, ACT_RELU);
+    o3.res = &idn; o3.res_mode = RES_SAME;
+    return conv(r, bk.conv3, t2, y, o3);
+}
+
+// BasicBlock: relu(bn2(conv2(relu(bn1(conv1(x))))) + identity); conv1 carries the stride and is never deformable, the residual and the
+// final ReLU sit in conv2's epilogue (the pipelined deformable kernel's RES build in the 16-bit / f16x2 modes).  t1, the downsample
+// output, then the offsets (conv2 runs at stride 1).
+static int basic_block(Runner& r, const ResBlock& bk, const Tensor& x, const Tensor& y, int w) {
+    Tensor t1 = r.alloc(x.n, y.h, y.w, w);
+    OCRVI_TRY(conv(r, bk.conv1, x, t1, conv_opts(bk.stride, 1, ACT_RELU)));
+    Tensor idn;
+    OCRVI_TRY(identity(r, bk, x, y, &idn));
+    ConvOpts o = conv_opts(1, 1, ACT_RELU);
+    o.res = &idn; o.res_mode = RES_SAME;
+    if (bk.dcn) OCRVI_TRY(dcn_offsets(r, bk, t1, y.h, y.w, 1, &o.offs));
+    return conv(r, bk.conv2, t1, y, o);
+}
+
+// The fused layer1 Bottleneck (bneck_tail.h): conv2 + conv3 (+ the next block's conv1 into `t1_next`) as one launch.  `t1` belongs to the
+// layer and is already written when the previous block's launch ended in this block's conv1 (`have_t1`); t2 is never allocated, so the
+// downsample output is the only temporary.
+static int fused_bottleneck(Runner& r, const ResBlock& bk, const Tensor& x, const Tensor& y, const Tensor& t1, bool have_t1,
+                            const Tensor& t1_next) {
+    if (!have_t1) OCRVI_TRY(conv(r, bk.conv1, x, t1, conv_opts(1, 0, ACT_RELU)));
+    Tensor idn;
+    OCRVI_TRY(identity(r, bk, x, y, &idn));
+    OCRVI_CHECK(idn.c == 256 && y.c == 256 && t1.c == 64 && !idn.f32 && !y.f32, OCRVI_EINVAL, "det: fused layer1 chain on a foreign shape");
+    if (r.dry()) return OCRVI_OK;
+    BneckTailParams q;
+    q.x = t1.p; q.w2 = bk.conv2.w; q.wt = bk.tail_w; q.bias2 = bk.conv2.bias; q.bias_t = bk.tail_bias;
+    q.idn = idn.p; q.y = y.p; q.t1n = bk.tail_c ? t1_next.p : nullptr;
+    q.n_img = x.n; q.H = y.h; q.W = y.w;
+    q.ws2 = bk.conv2.wscale; q.ws3 = bk.tail_ws3; q.ws1 = bk.tail_ws1;
+    return launch_bneck_tail(q, r.stream);
+}
+
+// ---- one of layers 1..4: *x is the layer's input on entry and its output (the c2..c5 tap, backbone.py:56-60) on return.  Block outputs
+// ping-pong between two slots (sized for the layer's output); the last block writes a fresh buffer that stays live as the tap.
+// Temporaries of a block are released when it ends, so a chunk of 16 pages keeps ~4 GB less live than with one buffer per block.
+static int det_layer(const ocrvi_det& h, Runner& r, int li, Tensor* x) {
+    const std::vector<ResBlock>& blocks = h.layers[li];
+    Tensor cur = *x;
+    const int N = cur.n, w = kWidth[li], cw = h.expansion * w, nb = (int)blocks.size();
+    const int lh = cur.h / blocks[0].stride, lw = cur.w / blocks[0].stride;
+    Tensor tap = r.alloc(N, lh, lw, cw);                          // the layer's final output
+    const size_t slot_mark = r.arena.mark();
+    Tensor slot[2] = {r.alloc(N, lh, lw, cw), r.alloc(N, lh, lw, cw)};
+    // Fused chains (bneck_tail.h): block b reads t1 from t1pp[b & 1] and writes the next block's into the other one, so both live
+    // outside the blocks' own marks (released with the slots).
+    const bool fused_layer = !h.basic && blocks[0].tail;
+    Tensor t1pp[2];
+    if (fused_layer) { t1pp[0] = r.alloc(N, lh, lw, w); t1pp[1] = r.alloc(N, lh, lw, w); }
+    bool have_t1 = false;   // the previous block's launch has written this block's t1
+    for (int b = 0; b < nb; ++b) {
+        const ResBlock& bk = blocks[b];
+        Tensor y = b == nb - 1 ? tap : slot[b & 1];               // never the buffer `cur` lives in (slot[(b-1)&1] or the previous tap)
+        const size_t block_mark = r.arena.mark();
+        if (fused_layer && bk.tail) {
+            OCRVI_TRY(fused_bottleneck(r, bk, cur, y, t1pp[b & 1], have_t1, t1pp[(b + 1) & 1]));
+            have_t1 = bk.tail_c;
+        } else if (h.basic) {
+            OCRVI_TRY(basic_block(r, bk, cur, y, w));
+        } else {
+            OCRVI_TRY(bottleneck(r, bk, cur, y, w));
         }
-        r.arena.release(slot_mark);  // both slots are dead once the layer's last block has written the tap
-        feats[li] = cur;
-        h->tap_c[li] = cur;
+        r.arena.release(block_mark);  // the block's temporaries are dead
+        cur = y;
     }
-    // ---- FPN top-down (neck.py:26-41)
+    r.arena.release(slot_mark);  // both slots are dead once the layer's last block has written the tap
+    *x = cur;
+    return OCRVI_OK;
+}
+
+// ---- neck: FPN top-down (neck.py:26-41) and adaptive scale fusion (neck.py:57-79)
+static int det_neck(const ocrvi_det& h, Runner& r, const Tensor* feats, Tensor* fused) {
+    const int N = feats[0].n;
     Tensor inner[4], p[4];
     for (int i = 3; i >= 0; --i) {
         inner[i] = r.alloc(N, feats[i].h, feats[i].w, 256);
         ConvOpts o;
         if (i < 3) { o.res = &inner[i + 1]; o.res_mode = RES_UP2; }  // lateral + nearest-2x(last_inner)
-        OCRVI_TRY(conv(r, h->lat[i], feats[i], inner[i], o));
+        OCRVI_TRY(conv(r, h.lat[i], feats[i], inner[i], o));
         p[i] = r.alloc(N, feats[i].h, feats[i].w, 256);
-        ConvOpts o3;
-        o3.pad = 1; o3.act = ACT_RELU;
-        OCRVI_TRY(conv(r, h->fpn[i], inner[i], p[i], o3));
+        OCRVI_TRY(conv(r, h.fpn[i], inner[i], p[i], conv_opts(1, 1, ACT_RELU)));
     }
-    // ---- adaptive scale fusion (neck.py:57-79)
-    Tensor fused = r.alloc(N, p[0].h, p[0].w, 256);
+    *fused = r.alloc(N, p[0].h, p[0].w, 256);
     float* asf_scratch = (float*)r.arena.alloc(asf_scratch_bytes(N, p[0].h, p[0].w));
-    if (!r.dry()) OCRVI_TRY(k_asf(dt, p[0].p, p[1].p, p[2].p, p[3].p, h->asf_w, h->asf_b, asf_scratch, fused.p, N, p[0].h, p[0].w, r.stream));
-    h->tap_fused = fused;
-    if (binary_head) {
-        // ---- DB head, binarise branch only (head.py:34; the page loop reads preds['binary'] and nothing else, pipeline2.py:318).  Both
-        // layers are VIEWS of the weights the two-branch head is packed into, not a second pack: fold_det puts the binarise branch's 64
-        // output channels first, so the first 64 rows (and biases) of head_conv are its 3x3 conv, and group 0 of head_dc1 is its deconv1.
-        // Same packed bits and same f16x2 layer scale as the five-map path, hence the same binary map.
-        ConvLayer hconv = h->head_conv, hdc = h->head_dc1;
-        hconv.N_g = hconv.Np = 64;
-        hdc.groups = 1;
-        Tensor hc1 = r.alloc(N, fused.h, fused.w, 64);
-        {
-            ConvOpts o;
-            o.pad = 1; o.act = ACT_RELU;
-            OCRVI_TRY(conv(r, hconv, fused, hc1, o));
-        }
-        // deconv1 (+BN+ReLU), deconv2 (64 -> 1) and the sigmoid in ONE GEMM: neither the deconv1 activation nor a logit map is written
-        Tensor bm; bm.p = binary; bm.n = N; bm.h = H; bm.w = W; bm.c = 1; bm.f32 = true;
-        ConvOpts o;
-        o.store_mode = ST_DB_BIN; o.offs = h->dc2_wb;
-        return conv(r, hdc, hc1, bm, o);
-    }
-    // ---- DB head (head.py:32-48): both branches' 3x3 convs as one 256->128 conv, both deconv1 as one grouped pixel-shuffle GEMM
-    Tensor hc = r.alloc(N, fused.h, fused.w, 128);
-    {
-        ConvOpts o;
-        o.pad = 1; o.act = ACT_RELU;
-        OCRVI_TRY(conv(r, h->head_conv, fused, hc, o));
-    }
-    // deconv1 (+BN+ReLU) and deconv2 (64 -> 1) of both branches in ONE GEMM: the 1.26 GB deconv1 activation is never materialised
-    const size_t map_elems = (size_t)N * H * W;
-    float* bl = blog ? blog : (float*)r.arena.alloc(map_elems * 4);
-    float* tl = tlog ? tlog : (float*)r.arena.alloc(map_elems * 4);
-    {
-        Tensor lm; lm.p = bl; lm.n = N; lm.h = H; lm.w = W; lm.c = 1; lm.f32 = true;
-        ConvOpts o;
-        o.store_mode = ST_DB_TAIL; o.out2 = tl; o.offs = h->dc2_wb;
-        OCRVI_TRY(conv(r, h->head_dc1, hc, lm, o));
-    }
-    if (!r.dry()) OCRVI_TRY(k_db_maps(bl, tl, h->cfg.k, binary, thresh, tbin, map_elems, r.stream));
+    if (!r.dry())
+        OCRVI_TRY(k_asf(h.cfg.dtype, p[0].p, p[1].p, p[2].p, p[3].p, h.asf_w, h.asf_b, asf_scratch, fused->p, N, p[0].h, p[0].w, r.stream));
     return OCRVI_OK;
 }
 
-extern "C" int ocrvi_det_workspace_bytes(const ocrvi_det* h, int N, int H, int W, size_t* bytes) {
-    OCRVI_CHECK(bytes, OCRVI_EINVAL, "det_workspace_bytes: null out");
-    OCRVI_TRY(check_det_shape(h, N, H, W));
-    Runner r(h->cfg.dtype, nullptr, nullptr, 0);
-    OCRVI_TRY(det_run(const_cast<ocrvi_det*>(h), r, nullptr, N, H, W, nullptr, nullptr, nullptr, nullptr, nullptr));
-    *bytes = r.arena.peak + 256;
+// the caller's (N,1,H,W) fp32 output maps; all but `binary` are optional
+struct DetMaps { float *binary = nullptr, *thresh = nullptr, *tbin = nullptr, *blog = nullptr, *tlog = nullptr; };
+
+// ---- DB head (head.py:32-48): both branches' 3x3 convs as one 256->128 conv, both deconv1 as one grouped pixel-shuffle GEMM
+static int det_head(const ocrvi_det& h, Runner& r, const Tensor& fused, int H, int W, const DetMaps& m) {
+    const int N = fused.n;
+    Tensor hc = r.alloc(N, fused.h, fused.w, 128);
+    OCRVI_TRY(conv(r, h.head_conv, fused, hc, conv_opts(1, 1, ACT_RELU)));
+    // deconv1 (+BN+ReLU) and deconv2 (64 -> 1) of both branches in ONE GEMM: the 1.26 GB deconv1 activation is never materialised.
+    // Planning counts both logit maps whatever the caller passes: the size does not depend on which outputs a forward asks for.
+    const size_t map_elems = (size_t)N * H * W;
+    float* bl = m.blog && !r.dry() ? m.blog : (float*)r.arena.alloc(map_elems * 4);
+    float* tl = m.tlog && !r.dry() ? m.tlog : (float*)r.arena.alloc(map_elems * 4);
+    ConvOpts o;
+    o.store_mode = ST_DB_TAIL; o.out2 = tl; o.offs = h.dc2_wb;
+    OCRVI_TRY(conv(r, h.head_dc1, hc, wrap(bl, N, H, W, 1, true), o));
+    if (!r.dry()) OCRVI_TRY(k_db_maps(bl, tl, h.cfg.k, m.binary, m.thresh, m.tbin, map_elems, r.stream));
     return OCRVI_OK;
+}
+
+// ---- DB head, binarise branch only (head.py:34; the page loop reads preds['binary'] and nothing else, pipeline2.py:318): the head of
+// ocrvi_det_forward_binary.  Both layers are VIEWS of the weights the two-branch head is packed into, not a second pack: fold_det puts the
+// binarise branch's 64 output channels first, so the first 64 rows (and biases) of head_conv are its 3x3 conv, and group 0 of head_dc1 is
+// its deconv1.  Same packed bits and same f16x2 layer scale as the five-map path, hence the same binary map.
+static int det_head_binary(const ocrvi_det& h, Runner& r, const Tensor& fused, int H, int W, float* binary) {
+    ConvLayer hconv = h.head_conv, hdc = h.head_dc1;
+    hconv.N_g = hconv.Np = 64;
+    hdc.groups = 1;
+    Tensor hc1 = r.alloc(fused.n, fused.h, fused.w, 64);
+    OCRVI_TRY(conv(r, hconv, fused, hc1, conv_opts(1, 1, ACT_RELU)));
+    // deconv1 (+BN+ReLU), deconv2 (64 -> 1) and the sigmoid in ONE GEMM: neither the deconv1 activation nor a logit map is written
+    ConvOpts o;
+    o.store_mode = ST_DB_BIN; o.offs = h.dc2_wb;
+    return conv(r, hdc, hc1, wrap(binary, fused.n, H, W, 1, true), o);
+}
+
+// Backbone, FPN and ASF are the same launches with either head.
+static int det_run(ocrvi_det* h, Runner& r, const float* x, int N, int H, int W, const DetMaps& m, bool binary_head) {
+    Tensor cur, fused;
+    OCRVI_TRY(det_stem(*h, r, x, N, H, W, &cur));
+    for (int li = 0; li < 4; ++li) {
+        OCRVI_TRY(det_layer(*h, r, li, &cur));
+        h->tap_c[li] = cur;
+    }
+    OCRVI_TRY(det_neck(*h, r, h->tap_c, &fused));
+    h->tap_fused = fused;
+    return binary_head ? det_head_binary(*h, r, fused, H, W, m.binary) : det_head(*h, r, fused, H, W, m);
+}
+
+static int det_plan(const char* what, const ocrvi_det* h, int N, int H, int W, bool binary_head, size_t* bytes) {
+    return plan_workspace(what, h, bytes, [&] { return check_det_shape(h, N, H, W); },
+                          [&](Runner& r) { return det_run(const_cast<ocrvi_det*>(h), r, nullptr, N, H, W, DetMaps{}, binary_head); });
+}
+static int det_forward(const char* what, ocrvi_det* h, const float* x, int N, int H, int W, const DetMaps& m, bool binary_head, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    return run_forward(what, h, x && m.binary && workspace, "x, binary and workspace are required", workspace, workspace_bytes, stream,
+                       [&] { return check_det_shape(h, N, H, W); }, [&](Runner& r) { return det_run(h, r, x, N, H, W, m, binary_head); });
+}
+
+extern "C" int ocrvi_det_workspace_bytes(const ocrvi_det* h, int N, int H, int W, size_t* bytes) {
+    return det_plan("det_workspace_bytes", h, N, H, W, false, bytes);
 }
 
 extern "C" int ocrvi_det_forward(ocrvi_det* h, const float* x, int N, int H, int W, float* binary, float* thresh, float* thresh_binary,
                                  float* bin_logits, float* thresh_logits, void* workspace, size_t workspace_bytes, void* stream) {
-    OCRVI_TRY(check_det_shape(h, N, H, W));
-    OCRVI_CHECK(x && binary && workspace, OCRVI_EINVAL, "det_forward: x, binary and workspace are required");
-    DeviceGuard dg(h->device);  // launches go to the handle's device whatever the caller's current device is
-    OCRVI_HIP(dg.err);
-    size_t need = 0;
-    OCRVI_TRY(ocrvi_det_workspace_bytes(h, N, H, W, &need));
-    OCRVI_CHECK(workspace_bytes >= need, OCRVI_ENOMEM, "det_forward: workspace %zu < %zu bytes", workspace_bytes, need);
-    OCRVI_CHECK(((uintptr_t)workspace & 255) == 0, OCRVI_EINVAL, "det_forward: workspace must be 256-byte aligned");
-    Runner r(h->cfg.dtype, (hipStream_t)stream, workspace, workspace_bytes);
-    OCRVI_TRY(det_run(h, r, x, N, H, W, binary, thresh, thresh_binary, bin_logits, thresh_logits));
-    OCRVI_CHECK(!r.arena.overflow, OCRVI_ENOMEM, "det_forward: workspace overflow");
-    return h->range.snapshot((hipStream_t)stream);
+    DetMaps m;
+    m.binary = binary; m.thresh = thresh; m.tbin = thresh_binary; m.blog = bin_logits; m.tlog = thresh_logits;
+    return det_forward("det_forward", h, x, N, H, W, m, false, workspace, workspace_bytes, stream);
 }
 
 extern "C" int ocrvi_det_binary_workspace_bytes(const ocrvi_det* h, int N, int H, int W, size_t* bytes) {
-    OCRVI_CHECK(bytes, OCRVI_EINVAL, "det_binary_workspace_bytes: null out");
-    OCRVI_TRY(check_det_shape(h, N, H, W));
-    Runner r(h->cfg.dtype, nullptr, nullptr, 0);
-    OCRVI_TRY(det_run(const_cast<ocrvi_det*>(h), r, nullptr, N, H, W, nullptr, nullptr, nullptr, nullptr, nullptr, true));
-    *bytes = r.arena.peak + 256;
-    return OCRVI_OK;
+    return det_plan("det_binary_workspace_bytes", h, N, H, W, true, bytes);
 }
 
 extern "C" int ocrvi_det_forward_binary(ocrvi_det* h, const float* x, int N, int H, int W, float* binary, void* workspace, size_t workspace_bytes,
                                         void* stream) {
-    OCRVI_TRY(check_det_shape(h, N, H, W));
-    OCRVI_CHECK(x && binary && workspace, OCRVI_EINVAL, "det_forward_binary: x, binary and workspace are required");
-    DeviceGuard dg(h->device);
-    OCRVI_HIP(dg.err);
-    size_t need = 0;
-    OCRVI_TRY(ocrvi_det_binary_workspace_bytes(h, N, H, W, &need));
-    OCRVI_CHECK(workspace_bytes >= need, OCRVI_ENOMEM, "det_forward_binary: workspace %zu < %zu bytes", workspace_bytes, need);
-    OCRVI_CHECK(((uintptr_t)workspace & 255) == 0, OCRVI_EINVAL, "det_forward_binary: workspace must be 256-byte aligned");
-    Runner r(h->cfg.dtype, (hipStream_t)stream, workspace, workspace_bytes);
-    OCRVI_TRY(det_run(h, r, x, N, H, W, binary, nullptr, nullptr, nullptr, nullptr, true));
-    OCRVI_CHECK(!r.arena.overflow, OCRVI_ENOMEM, "det_forward_binary: workspace overflow");
-    return h->range.snapshot((hipStream_t)stream);
+    DetMaps m;
+    m.binary = binary;
+    return det_forward("det_forward_binary", h, x, N, H, W, m, true, workspace, workspace_bytes, stream);
 }
 
 extern "C" int ocrvi_det_status(const ocrvi_det* h) {

@@ -44,6 +44,12 @@ struct Tensor {  // NHWC view
     bool f32 = false;
     size_t pixels() const { return (size_t)n * h * w; }
 };
+// a view of memory the graph did not get from Runner::alloc: a caller's output map, a shared arena buffer under another shape
+inline Tensor wrap(void* p, int n, int h, int w, int c, bool f32) {
+    Tensor t;
+    t.p = p; t.n = n; t.h = h; t.w = w; t.c = c; t.f32 = f32;
+    return t;
+}
 
 struct Runner {
     int dtype;
@@ -53,10 +59,7 @@ struct Runner {
     bool dry() const { return arena.planning(); }
     size_t esz(bool f32) const { return f32 ? 4 : dtype_size(dtype); }
     Tensor alloc(int n, int h, int w, int c, bool f32 = false) {
-        Tensor t;
-        t.n = n; t.h = h; t.w = w; t.c = c; t.f32 = f32;
-        t.p = arena.alloc((size_t)n * h * w * c * esz(f32));
-        return t;
+        return wrap(arena.alloc((size_t)n * h * w * c * esz(f32)), n, h, w, c, f32);
     }
 };
 
@@ -75,5 +78,43 @@ struct ConvOpts {
 };
 // y must be pre-shaped (n,h,w,c, f32) and allocated; x likewise.
 int conv(Runner& r, const ConvLayer& L, const Tensor& x, const Tensor& y, const ConvOpts& o);
+
+// ---------------------------------------------------------------- what every model handle's C entries share
+// A handle has `device`, `cfg.dtype` and a RangeWatch `range`.  `check()` validates the handle and the shape; `run(Runner&)` walks the
+// graph once: on a planning arena it only measures, on the caller's workspace it launches.  `what` prefixes the messages.
+
+// The end of a *_create: the ring GEMM's scratch pages are allocated now, so that no forward (possibly under graph capture) ever
+// allocates; an f16x2 handle gets its view of the device's range flag.  On the handle's device.
+int finish_create(int dtype, RangeWatch& range);
+
+// *_workspace_bytes: the peak of the graph's arena use.
+template <typename Handle, typename Check, typename Run>
+int plan_workspace(const char* what, const Handle* h, size_t* bytes, Check&& check, Run&& run) {
+    OCRVI_CHECK(bytes, OCRVI_EINVAL, "%s: null out", what);
+    OCRVI_TRY(check());
+    Runner r(h->cfg.dtype, nullptr, nullptr, 0);
+    OCRVI_TRY(run(r));
+    *bytes = r.arena.peak + 256;
+    return OCRVI_OK;
+}
+
+// *_forward: `have_args` / `args_msg` is the entry's own null check, made after the shape check.
+template <typename Handle, typename Check, typename Run>
+int run_forward(const char* what, Handle* h, bool have_args, const char* args_msg, void* workspace, size_t workspace_bytes, void* stream,
+                Check&& check, Run&& run) {
+    OCRVI_TRY(check());
+    OCRVI_CHECK(have_args, OCRVI_EINVAL, "%s: %s", what, args_msg);
+    DeviceGuard dg(h->device);  // launches go to the handle's device whatever the caller's current device is
+    OCRVI_HIP(dg.err);
+    Runner plan(h->cfg.dtype, nullptr, nullptr, 0);
+    OCRVI_TRY(run(plan));
+    const size_t need = plan.arena.peak + 256;
+    OCRVI_CHECK(workspace_bytes >= need, OCRVI_ENOMEM, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
+    OCRVI_CHECK(((uintptr_t)workspace & 255) == 0, OCRVI_EINVAL, "%s: workspace must be 256-byte aligned", what);
+    Runner r(h->cfg.dtype, (hipStream_t)stream, workspace, workspace_bytes);
+    OCRVI_TRY(run(r));
+    OCRVI_CHECK(!r.arena.overflow, OCRVI_ENOMEM, "%s: workspace overflow", what);
+    return h->range.snapshot((hipStream_t)stream);
+}
 
 }  // namespace ocrvi

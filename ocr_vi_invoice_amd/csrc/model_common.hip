@@ -1,5 +1,7 @@
 #include "model.h"
 
+#include "gemm_ring.h"
+
 namespace ocrvi {
 
 int upload_packed(DeviceStore& st, const PackedConv& pc, int amode, ConvLayer* L) {
@@ -73,6 +75,14 @@ int conv(Runner& r, const ConvLayer& L, const Tensor& x, const Tensor& y, const 
     }
     if (r.dry()) return OCRVI_OK;
     return launch_conv_dt(r.dtype, p, L.amode, r.stream);
+}
+
+int finish_create(int dtype, RangeWatch& range) {
+    const void* zero_page;
+    void* dump_page;
+    OCRVI_TRY(ring_pages(&zero_page, &dump_page));
+    if (dtype == OCRVI_F16X2) OCRVI_TRY(range.init());
+    return OCRVI_OK;
 }
 
 }  // namespace ocrvi

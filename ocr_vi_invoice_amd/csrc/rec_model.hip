@@ -6,7 +6,6 @@
 #include <algorithm>
 #include <memory>
 
-#include "gemm_ring.h"
 #include "model.h"
 
 using namespace ocrvi;
@@ -129,11 +128,7 @@ extern "C" int ocrvi_rec_create(int device, const void* blob_p, size_t blob_byte
     OCRVI_TRY(load_mlp(st, blob, "frm.v_mlp", d, dt, &h->v_mlp));
     OCRVI_TRY(load_vec(st, blob, "frm.vq", d, &h->vq));
     OCRVI_TRY(load_lin(st, blob, "head", cfg->num_classes, d, dt, &h->head));
-    {   // scratch pages of the ring GEMM: allocate now so no forward (possibly under graph capture) ever allocates
-        const void* z; void* d;
-        OCRVI_TRY(ring_pages(&z, &d));
-    }
-    if (dt == OCRVI_F16X2) OCRVI_TRY(h->range.init());
+    OCRVI_TRY(finish_create(dt, h->range));
     *out = h.release();
     return OCRVI_OK;
 }
@@ -162,10 +157,15 @@ static int ln(Runner& r, const Tensor& x, const Tensor& y, const LNw& w) {
     if (r.dry()) return OCRVI_OK;
     return k_layernorm(r.dtype, x.p, x.f32, y.p, y.f32, w.g, w.b, (int)x.pixels(), x.c, r.stream);
 }
-static Tensor view(const Tensor& t, int n, int h, int w, int c) {
-    Tensor v = t;
-    v.n = n; v.h = h; v.w = w; v.c = c;
-    return v;
+static Tensor view(const Tensor& t, int n, int h, int w, int c) { return wrap(t.p, n, h, w, c, t.f32); }
+// Multi-head self-attention over `seqs` sequences of `len` tokens, qkv -> out.  Sequences beyond 512 keys in the 4-byte modes go through
+// per-chunk partial rows that are merged: their scratch comes from the arena for the duration of the call.
+static int attention(Runner& r, const Tensor& qkv, const Tensor& out, int seqs, int len, int heads) {
+    const size_t mk = r.arena.mark(), sb = attention_scratch_bytes(r.dtype, seqs, len, heads);
+    void* asc = sb ? r.arena.alloc(sb) : nullptr;
+    if (!r.dry()) OCRVI_TRY(k_attention(r.dtype, qkv.p, out.p, seqs, len, heads, r.stream, asc));
+    r.arena.release(mk);
+    return OCRVI_OK;
 }
 
 // y = x + fc2(gelu(fc1(LN(x))))   (svtrv2.py:38-39,100).  `next`: what the caller needs in xn afterwards -- nullptr: nothing; a norm:
@@ -227,8 +227,7 @@ static int rec_run(ocrvi_rec* h, Runner& r, const float* x, int B, int H, int W,
         OCRVI_TRY(conv(r, h->stem1, xpad, s1, o));
     }
     int cur = 0;
-    Tensor xs;
-    xs.p = X[cur]; xs.n = B; xs.h = Hs; xs.w = Ws; xs.c = c.dims[0]; xs.f32 = true;
+    Tensor xs = wrap(X[cur], B, Hs, Ws, c.dims[0], true);
     {
         ConvOpts o;
         o.sh = o.sw = 2; o.pad = 1; o.act = ACT_GELU;
@@ -237,9 +236,7 @@ static int rec_run(ocrvi_rec* h, Runner& r, const float* x, int B, int H, int W,
     for (int s = 0; s < 3; ++s) {
         const int d = c.dims[s];
         const int rows = B * Hs * Ws;
-        Tensor xn; xn.p = XN; xn.n = B; xn.h = Hs; xn.w = Ws; xn.c = d; xn.f32 = false;
-        Tensor t1 = xn; t1.p = T1;
-        Tensor big; big.p = BIG; big.n = rows; big.h = big.w = 1; big.c = 4 * d; big.f32 = false;
+        const Tensor xn = wrap(XN, B, Hs, Ws, d, false), t1 = wrap(T1, B, Hs, Ws, d, false), big = wrap(BIG, rows, 1, 1, 4 * d, false);
         bool xn_ready = false;   // the previous block's fused MLP already wrote LN(x; norm1) (or the cast the merge needs) into xn
         const int nblk = (int)h->blocks[s].size();
         for (int bi = 0; bi < nblk; ++bi) {
@@ -254,12 +251,7 @@ static int rec_run(ocrvi_rec* h, Runner& r, const float* x, int B, int H, int W,
             } else {  // x + proj(MHSA(qkv(LN x)))  (svtrv2.py:77-86,98)
                 ConvOpts o;
                 OCRVI_TRY(conv(r, bw.qkv, view(xn, rows, 1, 1, d), view(big, rows, 1, 1, 3 * d), o));
-                {   // (sequences beyond 512 keys in the 4-byte modes: per-chunk partial rows, merged; scratch from the arena)
-                    const size_t mk = r.arena.mark(), sb = attention_scratch_bytes(dt, B, Hs * Ws, d / 32);
-                    void* asc = sb ? r.arena.alloc(sb) : nullptr;
-                    if (!r.dry()) OCRVI_TRY(k_attention(dt, big.p, t1.p, B, Hs * Ws, d / 32, r.stream, asc));
-                    r.arena.release(mk);
-                }
+                OCRVI_TRY(attention(r, big, t1, B, Hs * Ws, d / 32));
                 o.res = &xs; o.res_mode = RES_SAME;
                 OCRVI_TRY(conv(r, bw.proj, view(t1, rows, 1, 1, d), view(xs, rows, 1, 1, d), o));
             }
@@ -273,8 +265,7 @@ static int rec_run(ocrvi_rec* h, Runner& r, const float* x, int B, int H, int W,
             } else {
                 src = xs; src.f32 = false;
             }
-            Tensor nx;
-            nx.p = X[cur ^ 1]; nx.n = B; nx.h = Hs / 2; nx.w = Ws; nx.c = c.dims[s + 1]; nx.f32 = true;
+            Tensor nx = wrap(X[cur ^ 1], B, Hs / 2, Ws, c.dims[s + 1], true);
             ConvOpts o;
             o.sh = 2; o.sw = 1; o.pad = 1;
             OCRVI_TRY(conv(r, h->merge[s], src, nx, o));
@@ -285,23 +276,16 @@ static int rec_run(ocrvi_rec* h, Runner& r, const float* x, int B, int H, int W,
     }
     // ---- backbone_norm (svtrv2.py:500) -> FRM (svtrv2.py:192-247)
     const int rows = B * Hs * Ws;
-    Tensor bn; bn.p = X[cur ^ 1]; bn.n = rows; bn.h = bn.w = 1; bn.c = d2; bn.f32 = true;
+    const Tensor bn = wrap(X[cur ^ 1], rows, 1, 1, d2, true);
     OCRVI_TRY(ln(r, view(xs, rows, 1, 1, d2), bn, h->backbone_norm));
     h->tap_bn = bn.p;
-    Tensor xr; xr.p = X[cur]; xr.n = rows; xr.h = xr.w = 1; xr.c = d2; xr.f32 = true;  // stage output no longer needed
-    Tensor xn; xn.p = XN; xn.n = rows; xn.h = xn.w = 1; xn.c = d2; xn.f32 = false;
-    Tensor t1 = xn; t1.p = T1;
-    Tensor big; big.p = BIG; big.n = rows; big.h = big.w = 1; big.c = 4 * d2; big.f32 = false;
+    const Tensor xr = wrap(X[cur], rows, 1, 1, d2, true);  // stage output no longer needed
+    const Tensor xn = wrap(XN, rows, 1, 1, d2, false), t1 = wrap(T1, rows, 1, 1, d2, false), big = wrap(BIG, rows, 1, 1, 4 * d2, false);
     OCRVI_TRY(ln(r, bn, xn, h->h_norm));
     {
         ConvOpts o;
         OCRVI_TRY(conv(r, h->h_qkv, xn, view(big, rows, 1, 1, 3 * d2), o));
-        {   // one sequence per image row
-            const size_t mk = r.arena.mark(), sb = attention_scratch_bytes(dt, B * Hs, Ws, d2 / 32);
-            void* asc = sb ? r.arena.alloc(sb) : nullptr;
-            if (!r.dry()) OCRVI_TRY(k_attention(dt, big.p, t1.p, B * Hs, Ws, d2 / 32, r.stream, asc));
-            r.arena.release(mk);
-        }
+        OCRVI_TRY(attention(r, big, t1, B * Hs, Ws, d2 / 32));  // one sequence per image row
         o.res = &bn; o.res_mode = RES_SAME;
         OCRVI_TRY(conv(r, h->h_proj, t1, xr, o));
     }
@@ -309,9 +293,8 @@ static int rec_run(ocrvi_rec* h, Runner& r, const float* x, int B, int H, int W,
     OCRVI_TRY(mlp_block(r, xr, xn, big, h->h_norm2, h->h_mlp, d2, &h->v_norm_kv, &xn_ready));
     if (!xn_ready) OCRVI_TRY(ln(r, xr, xn, h->v_norm_kv));
     const int cols = B * Ws;
-    Tensor tq; tq.p = bn.p; tq.n = cols; tq.h = tq.w = 1; tq.c = d2; tq.f32 = true;
-    // note: tq would alias the backbone_norm tap; use a fresh buffer so the tap survives
-    tq.p = r.arena.alloc((size_t)cols * d2 * 4);
+    // (a fresh buffer, not bn's: the backbone_norm tap survives)
+    const Tensor tq = wrap(r.arena.alloc((size_t)cols * d2 * 4), cols, 1, 1, d2, true);
     {
         ConvOpts o;
         OCRVI_TRY(conv(r, h->v_kv, xn, view(big, rows, 1, 1, 2 * d2), o));
@@ -340,28 +323,16 @@ static int rec_run(ocrvi_rec* h, Runner& r, const float* x, int B, int H, int W,
 }
 
 extern "C" int ocrvi_rec_workspace_bytes(const ocrvi_rec* h, int B, int H, int W, size_t* bytes) {
-    OCRVI_CHECK(bytes, OCRVI_EINVAL, "rec_workspace_bytes: null out");
-    OCRVI_TRY(check_rec_shape(h, B, H, W));
-    Runner r(h->cfg.dtype, nullptr, nullptr, 0);
-    OCRVI_TRY(rec_run(const_cast<ocrvi_rec*>(h), r, nullptr, B, H, W, nullptr, nullptr, nullptr, nullptr));
-    *bytes = r.arena.peak + 256;
-    return OCRVI_OK;
+    return plan_workspace("rec_workspace_bytes", h, bytes, [&] { return check_rec_shape(h, B, H, W); }, [&](Runner& r) {
+        return rec_run(const_cast<ocrvi_rec*>(h), r, nullptr, B, H, W, nullptr, nullptr, nullptr, nullptr);
+    });
 }
 
 extern "C" int ocrvi_rec_forward(ocrvi_rec* h, const float* x, int B, int H, int W, float* log_probs, int32_t* argmax_ids, int32_t* ids,
                                  int32_t* lens, void* workspace, size_t workspace_bytes, void* stream) {
-    OCRVI_TRY(check_rec_shape(h, B, H, W));
-    OCRVI_CHECK(x && workspace, OCRVI_EINVAL, "rec_forward: null input/workspace");
-    DeviceGuard dg(h->device);  // launches go to the handle's device whatever the caller's current device is
-    OCRVI_HIP(dg.err);
-    size_t need = 0;
-    OCRVI_TRY(ocrvi_rec_workspace_bytes(h, B, H, W, &need));
-    OCRVI_CHECK(workspace_bytes >= need, OCRVI_ENOMEM, "rec_forward: workspace %zu < %zu bytes", workspace_bytes, need);
-    OCRVI_CHECK(((uintptr_t)workspace & 255) == 0, OCRVI_EINVAL, "rec_forward: workspace must be 256-byte aligned");
-    Runner r(h->cfg.dtype, (hipStream_t)stream, workspace, workspace_bytes);
-    OCRVI_TRY(rec_run(h, r, x, B, H, W, log_probs, argmax_ids, ids, lens));
-    OCRVI_CHECK(!r.arena.overflow, OCRVI_ENOMEM, "rec_forward: workspace overflow");
-    return h->range.snapshot((hipStream_t)stream);
+    return run_forward("rec_forward", h, x && workspace, "null input/workspace", workspace, workspace_bytes, stream,
+                       [&] { return check_rec_shape(h, B, H, W); },
+                       [&](Runner& r) { return rec_run(h, r, x, B, H, W, log_probs, argmax_ids, ids, lens); });
 }
 
 extern "C" int ocrvi_rec_status(const ocrvi_rec* h) {

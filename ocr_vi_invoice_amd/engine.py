@@ -5,11 +5,14 @@ Pages are grouped into **buckets**: the pages that ``resize_image_for_det`` (pip
 A page is never padded into a larger shape (that would change the detector's output near its edges).  Each bucket runs through the
 detector in chunks of up to ``det_chunk`` pages; the crops of every page of every bucket then share recogniser batches.
 
-Per detector chunk, on the detector stream: the chunk's page table -> device, ``ocrvi_resize_normalize_pages`` + ``ocrvi_det_forward``
-(binary map only; ``ocrvi_det_forward_binary`` with ``binary_head=True``; one captured graph per (H, W, n), kept in an LRU of ``graph_cache``), the optional ``prob_hook``, the map -> a pinned
+Per detector chunk, on the detector stream: the chunk's page table -> device, ``ocrvi_resize_normalize_pages`` + the detector's
+``enqueue_forward`` (``ocrvi_det_forward``, binary map only; ``enqueue_forward_binary`` / ``ocrvi_det_forward_binary`` with
+``binary_head=True``; one captured graph per (H, W, n), kept in an LRU of ``graph_cache``), the optional ``prob_hook``, the map -> a pinned
 host slot of two, an event.  The host post-processes chunk c (``ocrvi_db_boxes_pages``) while the device runs chunk c + 1.  Rectangles
 accumulate across chunks and buckets; each full ``rec_batch`` goes out on the recogniser stream: rectangles -> device,
-``ocrvi_crop_resize_normalize_pages`` + ``ocrvi_rec_forward`` (one captured graph), ids / lens -> a pinned host slot, an event.
+``ocrvi_crop_resize_normalize_pages`` + the recogniser's ``enqueue_forward`` (``ocrvi_rec_forward``; one captured graph), ids / lens -> a
+pinned host slot, an event.  The models' enqueue methods are the only call sites of the model entries: the engine passes its own
+buffers and workspaces to them and never touches a handle.
 
 Every result equals ``pipeline.detect_and_recognize`` run on that page alone in the f32 and f16x2 modes ("Batched engine":
 in bf16 / f16 a kernel choice depends on the batch's row count, so a page inside a chunk may be computed differently from alone).
@@ -17,7 +20,6 @@ in bf16 / f16 a kernel choice depends on the batch's row count, so a page inside
 from __future__ import annotations
 
 import collections
-import ctypes as C
 import math
 import os
 import time
@@ -161,9 +163,7 @@ class Engine:
         self.h_map = [torch.empty(self.det_chunk * L * L, dtype=torch.float32).pin_memory() for _ in range(2)]
         self.ev_map = [torch.cuda.Event() for _ in range(2)]
         # ---- recogniser: one batch shape, one workspace, one graph
-        n = C.c_size_t()
-        _lib.check(self.lib.ocrvi_rec_workspace_bytes(rec_model._handle, self.rec_batch, rh, rw, C.byref(n)))
-        self.rec_ws = torch.empty(max(n.value, 1), dtype=torch.uint8, **d)
+        self.rec_ws = torch.empty(max(rec_model.workspace_bytes(self.rec_batch, rh, rw), 1), dtype=torch.uint8, **d)
         T = rw // 4
         self.d_rects = torch.zeros((self.rec_batch, 5), dtype=torch.int32, **d)
         self.d_crops = torch.empty((self.rec_batch, 3, rh, rw), dtype=torch.float32, **d)
@@ -217,20 +217,16 @@ class Engine:
 
     # ------------------------------------------------------------------------------------------------ device work (enqueue-only)
     def _det_ws_bytes(self, n, h, w) -> int:
-        b = C.c_size_t()
-        fn = self.lib.ocrvi_det_binary_workspace_bytes if self.binary_head else self.lib.ocrvi_det_workspace_bytes
-        _lib.check(fn(self.det._handle, n, h, w, C.byref(b)))
-        return b.value
+        return self.det.workspace_bytes(n, h, w, "binary" if self.binary_head else "forward")
 
     def _det_calls(self, n, H, W):
         st = self.s_det.cuda_stream
         _lib.check(self.lib.ocrvi_resize_normalize_pages(self.devi, self.d_det_table.data_ptr(), n, H, W, self.d_x.data_ptr(), st))
+        x, out, ws = self.d_x.data_ptr(), self.d_bin.data_ptr(), self.det_ws
         if self.binary_head:
-            _lib.check(self.lib.ocrvi_det_forward_binary(self.det._handle, self.d_x.data_ptr(), n, H, W, self.d_bin.data_ptr(),
-                                                         self.det_ws.data_ptr(), self.det_ws.numel(), st))
-            return
-        _lib.check(self.lib.ocrvi_det_forward(self.det._handle, self.d_x.data_ptr(), n, H, W, self.d_bin.data_ptr(), None, None, None, None,
-                                              self.det_ws.data_ptr(), self.det_ws.numel(), st))
+            self.det.enqueue_forward_binary(x, n, H, W, out, ws.data_ptr(), ws.numel(), st)
+        else:
+            self.det.enqueue_forward(x, n, H, W, (out, None, None, None, None), ws.data_ptr(), ws.numel(), st)
 
     def _rec_calls(self):
         st = self.s_rec.cuda_stream
@@ -242,8 +238,8 @@ class Engine:
         else:
             _lib.check(self.lib.ocrvi_crop_resize_normalize_pages(self.devi, self.d_rec_table.data_ptr(), self.max_pages, self.d_rects.data_ptr(),
                                                                   self.rec_batch, rh, rw, self.d_crops.data_ptr(), st))
-        _lib.check(self.lib.ocrvi_rec_forward(self.rec._handle, self.d_crops.data_ptr(), self.rec_batch, rh, rw, None, self.d_am.data_ptr(),
-                                              self.d_ids.data_ptr(), self.d_lens.data_ptr(), self.rec_ws.data_ptr(), self.rec_ws.numel(), st))
+        self.rec.enqueue_forward(self.d_crops.data_ptr(), self.rec_batch, rh, rw, None, self.d_am.data_ptr(), self.d_ids.data_ptr(),
+                                 self.d_lens.data_ptr(), self.rec_ws.data_ptr(), self.rec_ws.numel(), st)
 
     def _run_det(self, n, H, W):
         """Steps 2 and 3 of a chunk on the detector stream: the cached graph of (H, W, n), or an eager launch that is captured after it."""
@@ -636,9 +632,9 @@ class Engine:
         finally:
             self.s_det.synchronize()
             self.s_rec.synchronize()
-        rc = self.lib.ocrvi_det_status(self.det._handle)
+        rc = self.det.range_status()
         if rc == 0:
-            rc = self.lib.ocrvi_rec_status(self.rec._handle)
+            rc = self.rec.range_status()
         if rc != 0:
             msg = _lib.last_error()
             _lib.check(self.lib.ocrvi_range_reset(self.devi, self.s_det.cuda_stream))

@@ -204,6 +204,32 @@ def test_forward_binary_is_graph_capturable():
     assert not torch.equal(m.forward_binary(_pages(N, H, W, 5).cuda()), m.forward_binary(_pages(N, H, W, 9).cuda()))
 
 
+def test_forward_binary_leaves_a_captured_forward_its_workspace():
+    """A captured graph of ``forward`` holds its workspace's address: ``forward_binary``, at the same shape and at another, must neither
+    free nor replace that buffer (the workspace cache keeps one resident shape per forward kind, each kind's apart)."""
+    from ocr_vi_invoice_amd import DBNetPP, weights
+    m = DBNetPP("resnet18", dcn=False, state_dict=weights.make_det_state_dict(seed=21, backbone="resnet18", dcn=False), dtype="f32")
+    x = _pages(1, 64, 64).cuda()
+    m(x)                                                  # warm-up: the workspace is allocated before the capture
+    ws = m._workspace(1, 64, 64)
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=side):
+        out = m(x)
+    torch.cuda.synchronize()
+    m.forward_binary(x)
+    m.forward_binary(_pages(1, 64, 96).cuda())
+    torch.cuda.synchronize()
+    out["binary"].zero_()
+    g.replay()
+    torch.cuda.synchronize()
+    got = out["binary"].clone()
+    assert m._workspace(1, 64, 64) is ws
+    assert torch.equal(got, m(x)["binary"])
+
+
 # ---------------------------------------------------------------------------------------------------------------- 7. range flag
 def test_forward_binary_reports_an_f16x2_overflow_like_forward():
     from ocr_vi_invoice_amd import DBNetPP, weights
