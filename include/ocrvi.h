@@ -780,6 +780,18 @@ int ocrvi_test_deform_conv(int device, int dtype, const float* x, const float* o
 int ocrvi_test_deform_conv_res(int device, int dtype, const float* x, const float* offset, const float* mask,
                                const float* weight_host, const float* bias_host, const float* res, int N, int C, int H, int W, int Co,
                                int stride, int relu, float* out, int iters, float* avg_ms);
+/* ocrvi_test_deform_conv_res with res optional (NULL: no residual) and the output buffer owned by the caller: out_raw is a DEVICE buffer
+ * of at least N*Ho*Wo rows of Co `dtype` elements (NHWC) that the kernel writes directly (the caller pre-fills it, and any rows past the
+ * last, and reads the bytes back); only its first N*Ho*Wo rows are converted to out, float32 NCHW [N,Co,Ho,Wo] DEVICE. */
+int ocrvi_test_deform_conv_raw(int device, int dtype, const float* x, const float* offset, const float* mask,
+                               const float* weight_host, const float* bias_host, const float* res, int N, int C, int H, int W, int Co,
+                               int stride, int relu, void* out_raw, float* out);
+/* Host-only (no GPU): which kernel the deformable convolution of ocrvi_test_deform_conv takes on a device of n_cu compute units and how
+ * it tiles the map, from the same functions the launchers use.  plan = {1: the pipelined kernel (csrc/dcn_pipe.h), 0: conv_gemm's
+ * deformable mode; rows of a tile (128; conv_gemm: 32 or 64); columns of a tile (128 or 256); pipelined kernel: log2 of the pixel
+ * patch's width, a tile being (128 >> lw) x (1 << lw) output pixels (conv_gemm: 0); tiles; workgroups; most tiles one workgroup walks;
+ * K-steps per tile}. */
+int ocrvi_test_dcn_plan(int dtype, int N, int C, int H, int W, int Co, int stride, int n_cu, int32_t plan[8]);
 /* Plain conv2d (groups, stride (sh,sw), square kernel 1 or 3, pad = k/2) + bias + activation
  * (0 none, 1 ReLU, 2 exact GELU).  Same conventions as above. */
 int ocrvi_test_conv(int device, int dtype, const float* x, const float* weight_host, const float* bias_host,

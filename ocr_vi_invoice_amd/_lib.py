@@ -43,6 +43,7 @@ EXPORTS = [
     "ocrvi_jpeg_quant_tables", "ocrvi_jpeg_encode_header", "ocrvi_jpeg_encode_sizes", "ocrvi_jpeg_encode_table_entry", "ocrvi_jpeg_encode_pages",
     "ocrvi_test_gemm_raw", "ocrvi_test_ring_plan",
     "ocrvi_overlay_segments", "ocrvi_overlay_pages",
+    "ocrvi_test_deform_conv_raw", "ocrvi_test_dcn_plan",
 ]
 PAGE_ENTRY = 4          # int64 fields of one page-table entry: (device address, height, width, 0) -- OCRVI_PAGE_ENTRY
 # ocrvi_det_eval's record: 13 slots of 8 bytes (OCRVI_DET_EVAL_*), the first six int64, the rest float64
@@ -150,6 +151,8 @@ def load() -> C.CDLL:
     lib.ocrvi_test_gemm.argtypes = [i32, i32, f32p, vp, vp, f32p, i32, i32, i32, i32, i32, i32, f32p, i32, C.POINTER(C.c_float)]
     lib.ocrvi_test_gemm_raw.argtypes = [i32, i32, f32p, vp, vp, f32p, i32, i32, i32, i32, i32, i32, vp, f32p]
     lib.ocrvi_test_ring_plan.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int32)]
+    lib.ocrvi_test_deform_conv_raw.argtypes = [i32, i32, f32p, f32p, f32p, vp, vp, f32p, i32, i32, i32, i32, i32, i32, i32, vp, f32p]
+    lib.ocrvi_test_dcn_plan.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int32)]
     lib.ocrvi_test_stem_pool.argtypes = [i32, i32, f32p, vp, vp, i32, i32, i32, i32, f32p, i32, C.POINTER(C.c_float)]
     lib.ocrvi_test_attention.argtypes = [i32, i32, f32p, i32, i32, i32, f32p, i32, C.POINTER(C.c_float)]
     lib.ocrvi_test_mlp.argtypes = [i32, i32, f32p, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32p, i32, C.POINTER(C.c_float)]

@@ -91,9 +91,11 @@ int timed(Scratch& sc, int iters, float* avg_ms, F&& launch) {
 }  // namespace
 
 // res: null, or device float32 NCHW [N, Co, Ho, Wo] added in the epilogue before the activation (RES_SAME)
+// out_raw: the caller's own device output buffer (NHWC [>= N Ho Wo][Co] of `dtype` elements, ocrvi_test_deform_conv_raw), or null for one
+// of exactly N Ho Wo rows allocated here
 static int test_deform_conv(int device, int dtype, const float* x, const float* offset, const float* mask, const float* weight_host,
-                            const float* bias_host, const float* res, int N, int C, int H, int W, int Co, int stride, int relu, float* out,
-                            int iters, float* avg_ms) {
+                            const float* bias_host, const float* res, int N, int C, int H, int W, int Co, int stride, int relu, void* out_raw,
+                            float* out, int iters, float* avg_ms) {
     OCRVI_CHECK(x && offset && mask && weight_host && out && (stride == 1 || stride == 2), OCRVI_EINVAL, "test_deform_conv: bad argument");
     OCRVI_HIP(hipSetDevice(device));
     Scratch sc;
@@ -103,9 +105,9 @@ static int test_deform_conv(int device, int dtype, const float* x, const float* 
     ConvLayer L;
     PackedConv pc = pack_conv(weight_host, bias_host, Co, C, 3, 3, 1, AM_DCN, dtype);
     OCRVI_TRY(upload_packed(st, pc, AM_DCN, &L));
-    void *xn = nullptr, *yn = nullptr, *offs = nullptr;
+    void *xn = nullptr, *yn = out_raw, *offs = nullptr;
     OCRVI_TRY(sc.alloc((size_t)N * H * W * C * dtype_size(dtype), &xn));
-    OCRVI_TRY(sc.alloc((size_t)N * Ho * Wo * Co * dtype_size(dtype), &yn));
+    if (!yn) OCRVI_TRY(sc.alloc((size_t)N * Ho * Wo * Co * dtype_size(dtype), &yn));
     OCRVI_TRY(sc.alloc((size_t)N * Ho * Wo * 32 * 4, &offs));
     OCRVI_TRY(to_nhwc(dtype, x, xn, N, C, H * W, sc.s));
     hipLaunchKernelGGL(pack_offsets_kernel, dim3(1024), dim3(256), 0, sc.s, offset, mask, (float*)offs, N, Ho * Wo);
@@ -132,14 +134,52 @@ static int test_deform_conv(int device, int dtype, const float* x, const float* 
 extern "C" int ocrvi_test_deform_conv(int device, int dtype, const float* x, const float* offset, const float* mask,
                                       const float* weight_host, const float* bias_host, int N, int C, int H, int W, int Co, int stride,
                                       int relu, float* out, int iters, float* avg_ms) {
-    return test_deform_conv(device, dtype, x, offset, mask, weight_host, bias_host, nullptr, N, C, H, W, Co, stride, relu, out, iters, avg_ms);
+    return test_deform_conv(device, dtype, x, offset, mask, weight_host, bias_host, nullptr, N, C, H, W, Co, stride, relu, nullptr, out, iters,
+                            avg_ms);
 }
 
 extern "C" int ocrvi_test_deform_conv_res(int device, int dtype, const float* x, const float* offset, const float* mask,
                                           const float* weight_host, const float* bias_host, const float* res, int N, int C, int H, int W,
                                           int Co, int stride, int relu, float* out, int iters, float* avg_ms) {
     OCRVI_CHECK(res, OCRVI_EINVAL, "test_deform_conv_res: res is required");
-    return test_deform_conv(device, dtype, x, offset, mask, weight_host, bias_host, res, N, C, H, W, Co, stride, relu, out, iters, avg_ms);
+    return test_deform_conv(device, dtype, x, offset, mask, weight_host, bias_host, res, N, C, H, W, Co, stride, relu, nullptr, out, iters, avg_ms);
+}
+
+extern "C" int ocrvi_test_deform_conv_raw(int device, int dtype, const float* x, const float* offset, const float* mask,
+                                          const float* weight_host, const float* bias_host, const float* res, int N, int C, int H, int W,
+                                          int Co, int stride, int relu, void* out_raw, float* out) {
+    OCRVI_CHECK(out_raw, OCRVI_EINVAL, "test_deform_conv_raw: out_raw is null");
+    return test_deform_conv(device, dtype, x, offset, mask, weight_host, bias_host, res, N, C, H, W, Co, stride, relu, out_raw, out, 0, nullptr);
+}
+
+// Host only: what launch_conv would do with the deformable 3x3 (pad 1) that ocrvi_test_deform_conv runs, on a device of n_cu compute
+// units.  No device is touched.
+extern "C" int ocrvi_test_dcn_plan(int dtype, int N, int C, int H, int W, int Co, int stride, int n_cu, int32_t plan[8]) {
+    OCRVI_CHECK(plan && dtype_valid(dtype) && N > 0 && C > 0 && H > 0 && W > 0 && Co > 0 && (stride == 1 || stride == 2) && n_cu > 0,
+                OCRVI_EINVAL, "test_dcn_plan: bad argument");
+    const int bke = conv_bke(dtype);
+    OCRVI_CHECK(C % bke == 0 && Co > 64, OCRVI_EINVAL, "test_dcn_plan: needs C %% %d == 0 and Co > 64 (got %d, %d)", bke, C, Co);
+    const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
+    ConvParams p;   // as conv() fills it for pack_conv's layer; the pointers are only tested for being there
+    p.x = p.w = (const void*)256; p.out = (void*)256; p.offs = (const float*)256;
+    p.n_img = N; p.H = H; p.W = W; p.OH = Ho; p.OW = Wo; p.M = N * Ho * Wo;
+    p.KH = 3; p.SH = p.SW = stride; p.PH = p.PW = 1;
+    p.Cin = p.Cin_g = C;
+    p.N_g = Co; p.Np = cdiv(Co, 128) * 128; p.Kp = 9 * C;
+    p.ldo = Co;
+    const bool pipe = dcn_pipe_eligible(p, dtype);
+    OCRVI_CHECK(pipe || !dcn_pipe_packing(dtype, C), OCRVI_EINVAL, "test_dcn_plan: packed for the pipelined kernel but not eligible for it");
+    if (pipe) {
+        const DcnPipePlan pl = dcn_pipe_plan((int)dtype_size(dtype), N, Ho, Wo, p.Np, C, n_cu);
+        plan[0] = 1; plan[1] = 128; plan[2] = pl.bn; plan[3] = pl.patch_lw;
+        plan[4] = pl.total; plan[5] = pl.grid; plan[6] = cdiv(pl.total, pl.grid); plan[7] = pl.nk;
+    } else {   // conv_gemm's AM_DCN mode: one tile per workgroup (OCRVI_DCN_TILE_M, the test knob of the launcher, is not looked at)
+        const int bn = p.Np % 256 == 0 ? 256 : 128, bm = dcn_gemm_tile_m(p.M, p.Np, n_cu);
+        const int total = cdiv(p.M, bm) * (p.Np / bn);
+        plan[0] = 0; plan[1] = bm; plan[2] = bn; plan[3] = 0;
+        plan[4] = total; plan[5] = total; plan[6] = 1; plan[7] = p.Kp / bke;
+    }
+    return OCRVI_OK;
 }
 
 extern "C" int ocrvi_test_stem_pool(int device, int dtype, const float* x, const float* weight_host, const float* bias_host, int N, int H, int W,

@@ -154,6 +154,12 @@ int launch_gemm_ring(const ConvParams& p_in, int amode, hipStream_t stream) {
     return launch_ring_cfg<T, 128, 8, 2>(p, amode, grid, stream);  // MI = 2: one group
 }
 
+// Row tile of conv_gemm's AM_DCN mode (launch_mode below; ocrvi_test_dcn_plan reports it): 64 rows, or 32 where the layer has 256-column
+// tiles and 64-row ones would leave the second round of the chip's 2 x CUs workgroup slots mostly empty.
+inline int dcn_gemm_tile_m(int M, int Np, int n_cu) {
+    return (Np % 256 == 0 && cdiv(M, 64) * (Np / 256) < 3 * n_cu) ? 32 : 64;
+}
+
 template <typename T, int AMODE>
 static int launch_mode(const ConvParams& p, hipStream_t stream) {
     const int bn = conv_bn_for(p.N_g);
@@ -167,7 +173,7 @@ static int launch_mode(const ConvParams& p, hipStream_t stream) {
         if (p.Np % 256 == 0) {
             int n_cu = 0;
             OCRVI_TRY(device_cus(&n_cu));
-            bool small = cdiv(p.M, 64) * (p.Np / 256) < 3 * n_cu;
+            bool small = dcn_gemm_tile_m(p.M, p.Np, n_cu) == 32;
             const char* fe = getenv("OCRVI_DCN_TILE_M");   // test knob (read per launch so that a test can sweep it): 32 or 64 rows
             const int force = fe ? atoi(fe) : 0;
             if (force == 32 || force == 64) small = force == 32;

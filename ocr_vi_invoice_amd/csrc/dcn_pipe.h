@@ -408,24 +408,39 @@ static inline bool dcn_pipe_eligible(const ConvParams& p, int dtype) {
            p.ldo % 8 == 0 && p.out_coff % 8 == 0 && p.offs != nullptr && (size_t)p.n_img * p.H * p.W * p.Cin * esz < ((size_t)1 << 32);
 }
 
-template <typename T>
-static int launch_dcn_pipe(const ConvParams& p_in, hipStream_t stream) {
-    ConvParams p = p_in;
-    int n_cu = 0;
-    OCRVI_TRY(device_cus(&n_cu));
-    const bool wide = p.Np % 256 == 0;
-    const int bn = wide ? 256 : 128;
+// Column tile, patch shape and grid of a launch: a pure function of the shape and the CU count.  launch_dcn_pipe launches on it and
+// ocrvi_test_dcn_plan reports it, so a test can assert the patch and the tile walk it means to reach.
+struct DcnPipePlan {
+    int bn, patch_lw;          // column tile; log2 of the patch width: a tile is (128 >> lw) rows x (1 << lw) columns of output pixels
+    int total, grid, nk;       // tiles (pixel patches x column tiles), workgroups, K-steps per tile
+};
+inline DcnPipePlan dcn_pipe_plan(int esz, int n_img, int OH, int OW, int Np, int Cin_g, int n_cu) {
+    DcnPipePlan r;
+    r.bn = Np % 256 == 0 ? 256 : 128;
     // patch shape: the (rows x columns) = (128 >> lw) x (1 << lw) that wastes the fewest pixels on this map; ties go to the squarer one
     int best_lw = 4;
     long best = -1;
     for (int lw : {4, 3, 5, 2, 6, 7}) {
         const int pw = 1 << lw, ph = 128 >> lw;
-        const long covered = (long)cdiv(p.OH, ph) * ph * cdiv(p.OW, pw) * pw;
+        const long covered = (long)cdiv(OH, ph) * ph * cdiv(OW, pw) * pw;
         if (best < 0 || covered < best) { best = covered; best_lw = lw; }
     }
-    p.patch_lw = best_lw;
-    const int total = p.n_img * cdiv(p.OH, 128 >> best_lw) * cdiv(p.OW, 1 << best_lw) * (p.Np / bn);
-    const int grid = cdiv(total, cdiv(total, std::min(total, n_cu)));   // one persistent workgroup per CU, equal tile counts
+    r.patch_lw = best_lw;
+    r.total = n_img * cdiv(OH, 128 >> best_lw) * cdiv(OW, 1 << best_lw) * (Np / r.bn);
+    r.grid = cdiv(r.total, cdiv(r.total, std::min(r.total, n_cu)));   // one persistent workgroup per CU, equal tile counts
+    r.nk = 9 * (Cin_g / (128 / esz));
+    return r;
+}
+
+template <typename T>
+static int launch_dcn_pipe(const ConvParams& p_in, hipStream_t stream) {
+    ConvParams p = p_in;
+    int n_cu = 0;
+    OCRVI_TRY(device_cus(&n_cu));
+    const DcnPipePlan pl = dcn_pipe_plan((int)sizeof(T), p.n_img, p.OH, p.OW, p.Np, p.Cin_g, n_cu);
+    const bool wide = pl.bn == 256;
+    const int bn = pl.bn, total = pl.total, grid = pl.grid;
+    p.patch_lw = pl.patch_lw;
     const int smem = 3 * bn * 128 + 2 * 128 * 128 + 9 * 128 * 20;
 #ifdef OCRVI_RING_PROF_BUILD
     static const bool prof = getenv("OCRVI_RING_PROF") && atoi(getenv("OCRVI_RING_PROF"));

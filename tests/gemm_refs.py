@@ -44,7 +44,7 @@ def gemm_ref(a, w, b, res, act, res_post):
     return y
 
 
-def gemm_bound(a, w, b, res, act, res_post, dt, out_f32):
+def gemm_bound(a, w, b, res, act, res_post, dt, out_f32, a_err=None):
     """Bound on |kernel - gemm_ref| per element for element type `dt` and output type out_type(dt, out_f32).  a, w must be exact in `dt`
     and res in the output type (the case builders pre-round them), so the hook's casts are exact.  With u = 2^-24, step by step:
       products  16-bit and f16x2: exact in fp32 (at most 11 x 11 significant bits per partial product).  f16x2 has three partial products
@@ -57,15 +57,18 @@ def gemm_bound(a, w, b, res, act, res_post, dt, out_f32):
       bias      one rounding, u |pre| (the 16-bit builds add it in the epilogue; charged to all);
       residual  one fp32 addition, u |pre + res|;
       act       ReLU is 1-Lipschitz; GELU: mlp_refs._gelu_err (the image of the error interval plus the error of common.h's gelu_erf);
-      output    half an ulp of the output type at |y| + e (aux_refs.half_ulp), nothing for raw fp32."""
-    for t, name in ((a, "a"), (w, "w")):
+      output    half an ulp of the output type at |y| + e (aux_refs.half_ulp), nothing for raw fp32.
+    a_err (tests/dcn_refs.py): the kernel builds its A operand itself and a is that operand in float64, known only to within a_err >= 0 per
+    element.  What the kernel multiplies is some a' with |a' - a| <= a_err, exact in `dt`: S is taken over |a| + a_err, and
+    a_err |W|^T -- the error of a itself, carried through the weights -- is added."""
+    for t, name in ((a, "a"), (w, "w")) if a_err is None else ((w, "w"),):
         assert torch.equal(round_to(t.float(), dt), t.float()), f"{name} must be exact in {dt}"
     ot = out_type(dt, out_f32)
     if res is not None:
         assert torch.equal(round_to(res.float(), ot), res.float()), "res must be exact in the output type"
     A, W = a.double(), w.double()
     bd = b.double()
-    S = A.abs() @ W.abs().t()
+    S = (A.abs() if a_err is None else A.abs() + a_err.double()) @ W.abs().t()
     K = a.shape[1]
     if dt in ("f32", "f16x2"):
         S = S + bd.abs()
@@ -75,6 +78,8 @@ def gemm_bound(a, w, b, res, act, res_post, dt, out_f32):
         terms = 3 if dt == "f16x2" else 1
         n = int(((A != 0).double() @ (W != 0).double().t()).max()) * terms + (1 if dt == "f16x2" else 0)
         e = (2 * max(n - 1, 0) * U32 + (4 * U32 if dt == "f16x2" else 0.0)) * S
+    if a_err is not None:
+        e = e + a_err.double() @ W.abs().t()
     pre = A @ W.t() + bd
     e = e + U32 * (pre.abs() + e)
     if res is not None and not res_post:
