@@ -838,6 +838,23 @@ int ocrvi_test_gemm_raw(int device, int dtype, const float* a, const float* weig
  * (0 / 1), tile rows BM, tile columns BN, 16-row slices per slice group SPS, fp32-output build (0 / 1), workgroups, fewest row tiles
  * one workgroup walks, most row tiles one workgroup walks}; entries 1..7 describe the ring launch whether or not entry 0 is set. */
 int ocrvi_test_ring_plan(int dtype, int amode, int M, int K, int N, int out_f32, int has_res, int n_cu, int32_t plan[8]);
+/* ocrvi_test_conv (grouped, strided; square kernel 1 or 3, pad = k/2) with the recogniser's epilogues and the output buffer owned by the
+ * caller.  res: NULL, or float32 NCHW DEVICE [N,Co,Ho,Wo], added before the activation (res_post = 0) or after it (res_post = 1); it is
+ * kept in fp32 when the output is fp32 (out_f32 set, or `dtype` OCRVI_F32) and cast to `dtype` otherwise.  out_raw: a DEVICE buffer of at
+ * least N Ho Wo rows of Co output elements (NHWC; float32 or `dtype` elements) that the kernel writes directly; the caller pre-fills it, and
+ * any rows past N Ho Wo, and reads the bytes back.  in_place (needs res and an fp32 output): the residual is copied into out_raw and that
+ * one buffer is passed as residual and as output, as the recogniser runs LocalMixing's second convolution on its residual stream.  Only
+ * the first N Ho Wo rows are converted to out, float32 NCHW DEVICE [N,Co,Ho,Wo]. */
+int ocrvi_test_conv_raw(int device, int dtype, const float* x, const float* weight_host, const float* bias_host, const float* res, int N,
+                        int C, int H, int W, int Co, int ksize, int sh, int sw, int groups, int act, int res_post, int out_f32, int in_place,
+                        void* out_raw, float* out);
+/* Host-only (no GPU): which kernel the 3x3 (pad 1) convolution of ocrvi_test_conv_raw takes on a device of n_cu compute units, from the
+ * functions the launcher dispatches on.  has_res: a residual of the output's shape and element type.  plan = {kernel: 0 conv_gemm, 1
+ * gconv32, 2 another (conv3_halo, ring GEMM); conv_gemm's tile rows BM and columns BN (0 otherwise); gconv32's output rows per tile th,
+ * 16-pixel blocks per tile row nbx, tiles down an image bands_y and across it bands_x (0 otherwise); grid.x; fewest and most tiles one
+ * workgroup walks; grid.y = groups; 128-byte K-steps of the packed weights}. */
+int ocrvi_test_gconv_plan(int dtype, int N, int C, int H, int W, int Co, int sh, int sw, int groups, int out_f32, int has_res, int n_cu,
+                          int32_t plan[12]);
 /* Multi-head self-attention on a packed qkv tensor [B, N, 3*heads*32] float32 (layout of
  * qkv.reshape(B,N,3,heads,32), svtrv2.py:80) -> out [B, N, heads*32] float32 (svtrv2.py:82-85). */
 /* The detector's stem: conv 7x7 stride 2 pad 3 (3 -> 64 channels) + bias + ReLU + max-pool 3x3 stride 2 pad 1 (torchvision resnet50's

@@ -44,6 +44,7 @@ EXPORTS = [
     "ocrvi_test_gemm_raw", "ocrvi_test_ring_plan",
     "ocrvi_overlay_segments", "ocrvi_overlay_pages",
     "ocrvi_test_deform_conv_raw", "ocrvi_test_dcn_plan",
+    "ocrvi_test_conv_raw", "ocrvi_test_gconv_plan",
 ]
 PAGE_ENTRY = 4          # int64 fields of one page-table entry: (device address, height, width, 0) -- OCRVI_PAGE_ENTRY
 # ocrvi_det_eval's record: 13 slots of 8 bytes (OCRVI_DET_EVAL_*), the first six int64, the rest float64
@@ -153,6 +154,8 @@ def load() -> C.CDLL:
     lib.ocrvi_test_ring_plan.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int32)]
     lib.ocrvi_test_deform_conv_raw.argtypes = [i32, i32, f32p, f32p, f32p, vp, vp, f32p, i32, i32, i32, i32, i32, i32, i32, vp, f32p]
     lib.ocrvi_test_dcn_plan.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int32)]
+    lib.ocrvi_test_conv_raw.argtypes = [i32, i32, f32p, vp, vp, f32p] + [i32] * 13 + [vp, f32p]
+    lib.ocrvi_test_gconv_plan.argtypes = [i32] * 12 + [C.POINTER(C.c_int32)]
     lib.ocrvi_test_stem_pool.argtypes = [i32, i32, f32p, vp, vp, i32, i32, i32, i32, f32p, i32, C.POINTER(C.c_float)]
     lib.ocrvi_test_attention.argtypes = [i32, i32, f32p, i32, i32, i32, f32p, i32, C.POINTER(C.c_float)]
     lib.ocrvi_test_mlp.argtypes = [i32, i32, f32p, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32p, i32, C.POINTER(C.c_float)]

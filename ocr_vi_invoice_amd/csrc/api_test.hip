@@ -292,6 +292,87 @@ extern "C" int ocrvi_test_conv_res(int device, int dtype, const float* x, const 
     return OCRVI_OK;
 }
 
+// A 3x3 (pad 1) or 1x1 convolution, grouped and strided, with the recogniser's epilogues, written straight into the caller's buffer.
+// res: null, or device float32 NCHW [N, Co, Ho, Wo]; it keeps fp32 when the output is fp32 (out_f32, or an fp32 model) and is cast to the
+// compute type otherwise.  in_place: the residual is copied into out_raw and that one buffer is residual and output, as LocalMixing's
+// second convolution runs on the residual stream (rec_model.hip).  The weights are packed in the chunk form (dense stride-1 f16x2 layers
+// that a loader packs for conv3_halo are ocrvi_test_conv's).
+extern "C" int ocrvi_test_conv_raw(int device, int dtype, const float* x, const float* weight_host, const float* bias_host, const float* res, int N,
+                                   int C, int H, int W, int Co, int ksize, int sh, int sw, int groups, int act, int res_post, int out_f32,
+                                   int in_place, void* out_raw, float* out) {
+    OCRVI_CHECK(x && weight_host && out && out_raw && (ksize == 1 || ksize == 3) && N > 0 && H > 0 && W > 0 && sh > 0 && sw > 0 && groups >= 1 &&
+                    C > 0 && Co > 0 && C % groups == 0 && Co % groups == 0 && dtype_valid(dtype),
+                OCRVI_EINVAL, "test_conv_raw: bad argument");
+    OCRVI_CHECK(act == ACT_NONE || act == ACT_RELU || act == ACT_GELU, OCRVI_EINVAL, "test_conv_raw: unknown activation %d", act);
+    const bool f32o = out_f32 || dtype == OCRVI_F32;
+    OCRVI_CHECK(!in_place || (res && f32o), OCRVI_EINVAL, "test_conv_raw: in_place needs a residual and an fp32 output");
+    OCRVI_HIP(hipSetDevice(device));
+    Scratch sc;
+    OCRVI_TRY(sc.init());
+    const int pad = ksize / 2;
+    const int Ho = (H + 2 * pad - ksize) / sh + 1, Wo = (W + 2 * pad - ksize) / sw + 1;
+    const int amode = ksize == 1 ? AM_CONV1 : AM_CONV3;
+    DeviceStore st;
+    ConvLayer L;
+    PackedConv pc = pack_conv(weight_host, bias_host, Co, C / groups, ksize, ksize, groups, amode, dtype);
+    OCRVI_TRY(upload_packed(st, pc, amode, &L));
+    void* xn = nullptr;
+    OCRVI_TRY(sc.alloc((size_t)N * H * W * C * dtype_size(dtype), &xn));
+    OCRVI_TRY(to_nhwc(dtype, x, xn, N, C, H * W, sc.s));
+    Runner r(dtype, sc.s, (void*)256, 0);
+    Tensor tx; tx.p = xn; tx.n = N; tx.h = H; tx.w = W; tx.c = C;
+    Tensor ty; ty.p = out_raw; ty.n = N; ty.h = Ho; ty.w = Wo; ty.c = Co; ty.f32 = f32o;
+    Tensor tr = ty;
+    ConvOpts o;
+    o.sh = sh; o.sw = sw; o.pad = pad; o.act = act;
+    if (res) {   // the residual has the output's shape and element type
+        const int rdt = f32o ? OCRVI_F32 : dtype;
+        void* rn = out_raw;
+        if (!in_place) OCRVI_TRY(sc.alloc((size_t)N * Ho * Wo * Co * dtype_size(rdt), &rn));
+        OCRVI_TRY(to_nhwc(rdt, res, rn, N, Co, Ho * Wo, sc.s));
+        tr.p = rn;
+        o.res = &tr; o.res_mode = RES_SAME; o.res_post = res_post;
+    }
+    OCRVI_TRY(conv(r, L, tx, ty, o));
+    OCRVI_TRY(k_nhwc_to_nchw_f32(f32o ? OCRVI_F32 : dtype, out_raw, out, N, Ho, Wo, Co, Co, 0, sc.s));
+    OCRVI_HIP(hipStreamSynchronize(sc.s));
+    return OCRVI_OK;
+}
+
+// Host only: which kernel launch_conv gives the 3x3 (pad 1) convolution that ocrvi_test_conv_raw runs, on a device of n_cu compute units,
+// and gconv32's tiling from the function its launcher uses.  No device is touched.
+extern "C" int ocrvi_test_gconv_plan(int dtype, int N, int C, int H, int W, int Co, int sh, int sw, int groups, int out_f32, int has_res,
+                                     int n_cu, int32_t plan[12]) {
+    OCRVI_CHECK(plan && dtype_valid(dtype) && N > 0 && H > 0 && W > 0 && sh > 0 && sw > 0 && groups >= 1 && C > 0 && Co > 0 && C % groups == 0 &&
+                    Co % groups == 0 && n_cu > 0,
+                OCRVI_EINVAL, "test_gconv_plan: bad argument");
+    const int bke = conv_bke(dtype), bn = conv_bn_for(Co / groups);
+    const bool f32o = out_f32 || dtype == OCRVI_F32;
+    ConvParams p;   // as conv() fills it for pack_conv's layer; the pointers are only tested for alignment
+    p.x = p.w = (const void*)256; p.out = (void*)256; p.bias = (const float*)256;
+    p.n_img = N; p.H = H; p.W = W; p.OH = (H - 1) / sh + 1; p.OW = (W - 1) / sw + 1; p.M = N * p.OH * p.OW;
+    p.KH = 3; p.SH = sh; p.SW = sw; p.PH = p.PW = 1;
+    p.Cin = C; p.Cin_g = C / groups; p.groups = groups;
+    p.N_g = Co / groups; p.Np = cdiv(p.N_g, bn) * bn; p.Kp = cdiv(9 * p.Cin_g, bke) * bke;
+    p.ldo = Co; p.out_f32 = f32o ? 1 : 0;
+    if (has_res) { p.res = (const void*)256; p.res_mode = RES_SAME; p.ldr = Co; p.res_f32 = f32o ? 1 : 0; }
+    for (int i = 0; i < 12; ++i) plan[i] = 0;
+    plan[10] = groups; plan[11] = p.Kp / bke;
+    if (dtype_size(dtype) == 2 && gconv32_eligible(p, AM_CONV3, 2)) {
+        const Gconv32Plan pl = gconv32_plan(N, H, W, groups, n_cu);
+        plan[0] = 1; plan[3] = pl.th; plan[4] = pl.nbx; plan[5] = pl.bands_y; plan[6] = pl.bands_x;
+        plan[7] = pl.grid_x; plan[8] = pl.tiles_min; plan[9] = pl.tiles_max;
+        return OCRVI_OK;
+    }
+    if ((dtype == OCRVI_F16X2 && conv3_halo_eligible(p, AM_CONV3, dtype)) || gemm_ring_eligible(p, AM_CONV3, dtype)) {
+        plan[0] = 2;   // conv3_halo or the ring GEMM: not this hook's to describe
+        return OCRVI_OK;
+    }
+    plan[1] = 128; plan[2] = bn;                                    // launch_mode: conv_gemm, one tile per workgroup
+    plan[7] = cdiv(p.M, 128) * (p.Np / bn); plan[8] = plan[9] = 1;
+    return OCRVI_OK;
+}
+
 // The fused ResNet-50 layer1 chain (bneck_tail.h), f16x2: t1 [N,64,H,W] -> conv2 3x3 + ReLU -> conv3 1x1 + identity [N,256,H,W] + ReLU = y
 // -> (unless no_phase_c) the next block's conv1 1x1 + ReLU = t1n [N,64,H,W].  Weights as the detector's loader packs them.
 extern "C" int ocrvi_test_bneck_tail(int device, const float* t1, const float* identity, const float* w2_host, const float* b2_host,

@@ -14,6 +14,20 @@ constexpr int GC_PS = 96;        // LDS bytes per halo pixel / weight row
 constexpr int GC_TH = 4;         // output rows per tile
 constexpr int GC_NBX = 5;        // 16-pixel blocks per tile row (tile width 80)
 
+// The kernel splits a halo pixel index into (row, column) by a multiplication: pix / HW == (pix * (65536 / HW + 1)) >> 16 with HW = 16 nbx + 2
+// the halo width.  That holds only up to a limit that depends on HW (at HW = 82 it first fails at pix = 1065); the kernel needs it for every
+// pix < (GC_TH + 2) * HW (at most 492), at each nbx the launcher can choose.  Checked here, so that a larger tile cannot outgrow it unnoticed.
+constexpr unsigned gc_hw_magic(int hw) { return 65536u / (unsigned)hw + 1; }
+constexpr bool gc_hw_magic_exact() {
+    for (int nbx = 1; nbx <= GC_NBX; ++nbx) {
+        const int hw = 16 * nbx + 2;
+        for (int pix = 0; pix < (GC_TH + 2) * hw; ++pix)
+            if ((int)(((unsigned)pix * gc_hw_magic(hw)) >> 16) != pix / hw) return false;
+    }
+    return true;
+}
+static_assert(gc_hw_magic_exact(), "gconv32: the halo-index multiplication is not exact for every pixel of a (GC_TH + 2) x (16 GC_NBX + 2) tile");
+
 template <typename T, bool F32O>
 __global__ __launch_bounds__(256, 2) void gconv32_kernel(const ConvParams p, int TH, int nbx, int bands_y, int bands_x, unsigned hw_magic) {
     constexpr int PS = GC_PS, MB = (GC_TH * GC_NBX + 3) / 4;  // M-blocks per wave (TH <= GC_TH rows per tile)
@@ -192,18 +206,40 @@ static inline bool gconv32_eligible(const ConvParams& p, int amode, int esz) {
     return p.res_mode == RES_NONE;
 }
 
+// Tiling and grid of a gconv32 launch: a pure function of the shape and the CU count.  launch_gconv32 launches what it says and
+// ocrvi_test_gconv_plan reports it, so a test can assert the tiling it means to reach.
+struct Gconv32Plan {
+    int th, nbx;               // output rows and 16-pixel blocks per tile
+    int bands_y, bands_x;      // tiles down and across one image
+    int ntile, grid_x;         // tiles per group; workgroups per group (grid.y = groups)
+    int tiles_min, tiles_max;  // tiles the workgroups walk
+    int smem;
+    unsigned hw_magic;         // gc_hw_magic of the halo width
+};
+inline Gconv32Plan gconv32_plan(int n_img, int H, int W, int groups, int n_cu) {
+    Gconv32Plan r;
+    r.nbx = std::min(GC_NBX, cdiv(W, 16));
+    r.th = H % 4 == 0 ? 4 : (H % 3 == 0 ? 3 : (H < 4 ? H : 4));   // rows per tile: avoid a mostly empty last band
+    r.bands_x = cdiv(W, 16 * r.nbx);
+    r.bands_y = cdiv(H, r.th);
+    r.smem = (r.th + 2) * (16 * r.nbx + 2) * GC_PS + 9 * 32 * GC_PS;
+    r.hw_magic = gc_hw_magic(16 * r.nbx + 2);  // pix / HW == (pix * magic) >> 16 for every pix of the halo tile (gc_hw_magic_exact)
+    r.ntile = n_img * r.bands_y * r.bands_x;
+    const int per_group = std::max(1, 2 * n_cu / groups);        // two persistent workgroups per CU over all groups
+    r.grid_x = cdiv(r.ntile, cdiv(r.ntile, per_group));          // equal tile counts
+    r.tiles_min = r.ntile / r.grid_x;
+    r.tiles_max = cdiv(r.ntile, r.grid_x);
+    return r;
+}
+
 template <typename T>
 static int launch_gconv32(const ConvParams& p, hipStream_t stream) {
-    const int nbx = std::min(GC_NBX, cdiv(p.W, 16));
-    const int th = p.H % 4 == 0 ? 4 : (p.H % 3 == 0 ? 3 : (p.H < 4 ? p.H : 4));   // rows per tile: avoid a mostly empty last band
-    const int bands_x = cdiv(p.W, 16 * nbx), bands_y = cdiv(p.H, th);
-    const int smem = (th + 2) * (16 * nbx + 2) * GC_PS + 9 * 32 * GC_PS;
-    const unsigned hw_magic = 65536u / (unsigned)(16 * nbx + 2) + 1;  // pix / HW == (pix * magic) >> 16 for pix < 2^11
     int n_cu = 0;
     OCRVI_TRY(device_cus(&n_cu));
-    const int ntile = p.n_img * bands_y * bands_x;
-    const int per_group = std::max(1, 2 * n_cu / p.groups);                  // two persistent workgroups per CU over all groups
-    const dim3 grid(cdiv(ntile, cdiv(ntile, per_group)), p.groups);          // equal tile counts
+    const Gconv32Plan pl = gconv32_plan(p.n_img, p.H, p.W, p.groups, n_cu);
+    const int th = pl.th, nbx = pl.nbx, bands_y = pl.bands_y, bands_x = pl.bands_x, smem = pl.smem;
+    const unsigned hw_magic = pl.hw_magic;
+    const dim3 grid(pl.grid_x, p.groups);
     if (p.out_f32) {
         auto k = gconv32_kernel<T, true>;
         OCRVI_TRY(ensure_max_smem((const void*)k, 80 * 1024));
