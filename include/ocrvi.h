@@ -413,6 +413,80 @@ int ocrvi_jpeg_decode_pages(int device, const void* records_dev, const int64_t* 
                             size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * PNG decode: the other format the reference's loop reads with cv2.imread (src/pipeline/pipeline2.py:264-268, :284-288; its dataloaders
+ * take .png too, src/det/dataloader.py:307-311, src/rec2/dataloader.py:188).  The host half is what is serial per file: the chunk list,
+ * CRC-32, inflate (written here: no zlib, no libpng) and Adler-32.  The host uploads what the file holds, not pixels; undoing the row
+ * filters, unpacking bits, the palette lookup, dropping alpha and 16 -> 8 bit run on the device, batched over pages.
+ * Accepted: all 15 legal pairs of colour type and bit depth (grey 1 2 4 8 16, RGB 8 16, palette 1 2 4 8, grey + alpha 8 16, RGBA 8 16);
+ * any number of IDAT chunks, empty ones included; stored, fixed and dynamic deflate blocks; ancillary chunks (tRNS gAMA cHRM sRGB iCCP
+ * bKGD pHYs eXIf tEXt ..., and APNG's acTL fcTL fdAT: the default image is decoded) are skipped by length, their CRC unread; bytes in
+ * the IDAT data after the end of the zlib stream are ignored.
+ * Refused with OCRVI_EINVAL and a message naming the feature, never guessed and never decoded by other means: Adam7 interlace, a
+ * compression or filter method other than 0, an illegal type / depth pair, a side of 0 or above 65500, a colour-type-3 file without PLTE
+ * before IDAT, a PLTE length that is no multiple of 3 or above 256 entries, an unknown critical chunk (Apple's CgBI among them), IDAT
+ * chunks that are not consecutive.  The bytes are untrusted; each of these is OCRVI_EINVAL too: a truncated file, a wrong CRC on IHDR,
+ * PLTE, IDAT or IEND (IDAT's is checked by ocrvi_png_parse, the others by ocrvi_png_info as well), a bad zlib header (CM != 8, a window
+ * above 32 K, FCHECK, a preset dictionary), a reserved block type, a stored-block length whose complement does not match, an
+ * over-subscribed code-length set, an incomplete one other than the single one-bit code zlib accepts (or no distance code at all), a code
+ * with no symbol, a distance reaching before the start of the output, a wrong Adler-32, a missing IEND, output shorter or longer than
+ * stream_bytes, a filter byte above 4.
+ * Stream (what ocrvi_png_parse writes): for colour type 3 first a 1024-byte palette, 256 x (R, G, B, 0), zero beyond the file's PLTE
+ * entries; then, for every colour type, the inflated scanlines exactly as the file holds them, height x (1 + row_bytes) bytes, each row
+ * led by its filter byte; row_bytes = ceil(width x channels x bit_depth / 8).
+ * The arithmetic is the library's own definition, stated here; tests/png_ref.py restates it in NumPy.  It equals PIL's
+ * Image.open().convert("RGB") bit for bit for 14 of the 15 pairs (pinned by tests/golden/png_cases.npz); 16-bit grey (PIL maps it
+ * differently) and palette indices beyond PLTE are pinned to tests/png_ref.py only; parity with cv2.imread is UNPINNED (cv2 absent).
+ *   unfilter    bpp = max(1, channels x bit_depth / 8); a = the reconstructed byte bpp to the left, b = the byte above, c = the byte
+ *               above-left (each 0 outside the row or the image); every reconstructed byte is (x + p) & 255 with p = 0, a, b,
+ *               (a + b) >> 1 or Paeth for filter bytes 0 .. 4
+ *   Paeth       q = a + b - c; a if |q - a| <= |q - b| and |q - a| <= |q - c|; else b if |q - b| <= |q - c|; else c
+ *   samples     packed most significant bit first; grey samples of depth 1, 2, 4 scale by 255, 85, 17; a 16-bit sample gives its high
+ *               byte; grey goes to all three channels; palette index i gives palette row i, rows beyond the file's PLTE are (0, 0, 0)
+ *   ignored     alpha is dropped, never composited; tRNS, gamma, colour profiles and the eXIf orientation are not applied
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t width, height, bit_depth, colour_type;
+    int32_t channels;                       /* samples per pixel: 1 (grey, palette), 2 (grey + alpha), 3 (RGB), 4 (RGBA) */
+    int32_t row_bytes;                      /* ceil(width x channels x bit_depth / 8), without the filter byte */
+    int32_t out_height, out_width;          /* of the decoded page (= height, width: no orientation is applied) */
+    int32_t palette_entries;                /* of the file's PLTE, colour type 3 only; 0 otherwise */
+    int32_t reserved;
+    uint64_t idat_bytes;                    /* compressed bytes, all IDAT chunks together */
+    uint64_t stream_bytes;                  /* the exact size of the page's stream */
+    uint64_t workspace_bytes;               /* device bytes of the page's line between bands: 0 for a page of one band, a multiple of 256 */
+    char reason[160];                       /* the message when the call fails (also ocrvi_last_error) */
+} ocrvi_png_info_t;
+/* Host only, needs no GPU.  Checks the signature, parses IHDR and walks the chunk list up to IEND.  On OCRVI_EINVAL the geometry fields
+ * are filled when IHDR was reached.  Takes no lock and no interpreter state, like ocrvi_png_parse: calls from a thread pool run in
+ * parallel. */
+int ocrvi_png_info(const void* data, size_t n, ocrvi_png_info_t* info);
+/* Host only.  Joins the IDAT chunks and inflates them into the page's stream at out[0 .. cap) (pinned memory when it is to be uploaded);
+ * *used = info.stream_bytes.  Never writes past cap: OCRVI_ENOMEM when cap < info.stream_bytes. */
+int ocrvi_png_parse(const void* data, size_t n, void* out, size_t cap, size_t* used);
+/* Host only.  Fills one entry of the table ocrvi_png_decode_pages reads, int64 [OCRVI_PNG_ENTRY]: (0 stream offset, 1 stream bytes,
+ * 2 width, 3 height, 4 bit depth, 5 colour type, 6 palette entries, 7 destination offset, 8 destination row stride, 9 workspace offset,
+ * 10..15 zero).  Offsets are in bytes from streams_dev (a multiple of 4), dst_base (signed: pages of one launch may lie in different
+ * buffers either side of dst_base) and workspace (a multiple of 4); dst_stride >= 3 out_width. */
+#define OCRVI_PNG_ENTRY 16
+int ocrvi_png_table_entry(const ocrvi_png_info_t* info, size_t used, int64_t stream_offset, int64_t dst_offset, int64_t dst_stride,
+                          int64_t workspace_offset, int64_t* entry);
+/* Host only.  What the kernel will do for the page: it walks the page in *bands bands of *band_rows rows (thread = row); inside a band
+ * the rows run skewed by one step, a step reconstructing one chunk of *chunk_bytes bytes per row, so a band of r rows and c chunks per
+ * row takes c + r - 1 steps; *steps = their sum over the bands.  Any of the four pointers may be null. */
+int ocrvi_png_plan(const ocrvi_png_info_t* info, int* band_rows, int* chunk_bytes, int* bands, int* steps);
+/* Decodes n_pages pages in one launch (png_unfilter_kernel, one workgroup per page) into uint8 HWC RGB [height, width, 3] at dst_base +
+ * destination offset, rows dst_stride bytes apart; bytes between rows are not written.  streams_dev: the pages' streams, table_dev: int64
+ * [n_pages][OCRVI_PNG_ENTRY], both DEVICE memory and read when the kernel runs, so a captured graph survives rewritten tables and
+ * streams; the streams are not modified.  Enqueue-only on `stream`: no allocation, no synchronisation.  The pages' workspace regions must
+ * not overlap (workspace may be null when workspace_bytes is 0: no page of more than one band).  An entry whose fields are out of range
+ * or inconsistent -- stream bytes other than what width, height, depth and type imply, an illegal type / depth pair, a side of 0 or above
+ * 65500, a stride below 3 width, a line that does not fit workspace_bytes -- is skipped and never dereferenced.  A filter byte above 4
+ * met on the device counts as 0 (the host has refused such files; the rule only keeps a rewritten stream from mattering).  A destination
+ * that is 4-byte aligned with a 4-byte aligned stride is written in words, any other in bytes. */
+int ocrvi_png_decode_pages(int device, const void* streams_dev, const int64_t* table_dev, int n_pages, void* dst_base, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * JPEG encode: replaces the cv2.imwrite at the end of the reference's loop (src/pipeline/pipeline2.py:397-400, and the det-only CLI in
  * src/det/test.py) for baseline JPEG.  The host writes the header; colour conversion, down-sampling, forward DCT, quantisation, Huffman
  * coding, bit packing and byte stuffing run on the device, batched over pages, and only the compressed bytes leave it.  Input is uint8

@@ -45,6 +45,7 @@ EXPORTS = [
     "ocrvi_overlay_segments", "ocrvi_overlay_pages",
     "ocrvi_test_deform_conv_raw", "ocrvi_test_dcn_plan",
     "ocrvi_test_conv_raw", "ocrvi_test_gconv_plan",
+    "ocrvi_png_info", "ocrvi_png_parse", "ocrvi_png_table_entry", "ocrvi_png_plan", "ocrvi_png_decode_pages",
 ]
 PAGE_ENTRY = 4          # int64 fields of one page-table entry: (device address, height, width, 0) -- OCRVI_PAGE_ENTRY
 # ocrvi_det_eval's record: 13 slots of 8 bytes (OCRVI_DET_EVAL_*), the first six int64, the rest float64
@@ -59,6 +60,7 @@ DB_TARGET_GT, DB_TARGET_MASK, DB_TARGET_THRESH = 0, 1, 2   # OCRVI_DB_TARGET_*: 
 DB_TARGET_JOB = 8               # int32 fields of one fill job -- OCRVI_DB_TARGET_JOB
 DB_TARGET_MAX_SIDE = 16384      # OCRVI_DB_TARGET_MAX_SIDE
 JPEG_ENTRY = 64                 # int64 fields of one ocrvi_jpeg_decode_pages table entry -- OCRVI_JPEG_ENTRY
+PNG_ENTRY = 16                  # int64 fields of one ocrvi_png_decode_pages table entry -- OCRVI_PNG_ENTRY
 JPEG_ENC_ENTRY = 64             # int64 fields of one ocrvi_jpeg_encode_pages table entry -- OCRVI_JPEG_ENC_ENTRY
 JPEG_HEADER_MAX = 640           # OCRVI_JPEG_HEADER_MAX
 OVERLAY_SEG = 8                 # int32 fields of one overlay segment -- OCRVI_OVERLAY_SEG
@@ -83,6 +85,14 @@ class JpegInfo(C.Structure):
                 ("restart_interval", C.c_int32), ("orientation", C.c_int32), ("out_height", C.c_int32), ("out_width", C.c_int32),
                 ("reserved", C.c_int32), ("blocks", C.c_int64), ("stream_bytes", C.c_uint64), ("workspace_bytes", C.c_uint64),
                 ("quant", (C.c_uint16 * 64) * 3), ("reason", C.c_char * 160)]
+
+
+class PngInfo(C.Structure):
+    """ocrvi_png_info_t"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("bit_depth", C.c_int32), ("colour_type", C.c_int32), ("channels", C.c_int32),
+                ("row_bytes", C.c_int32), ("out_height", C.c_int32), ("out_width", C.c_int32), ("palette_entries", C.c_int32),
+                ("reserved", C.c_int32), ("idat_bytes", C.c_uint64), ("stream_bytes", C.c_uint64), ("workspace_bytes", C.c_uint64),
+                ("reason", C.c_char * 160)]
 
 
 _lib: Optional[C.CDLL] = None
@@ -186,6 +196,11 @@ def load() -> C.CDLL:
     lib.ocrvi_jpeg_parse.argtypes = [vp, sz, vp, sz, C.POINTER(sz)]
     lib.ocrvi_jpeg_table_entry.argtypes = [C.POINTER(JpegInfo), sz, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp]
     lib.ocrvi_jpeg_decode_pages.argtypes = [i32, vp, vp, i32, vp, vp, sz, vp]
+    lib.ocrvi_png_info.argtypes = [vp, sz, C.POINTER(PngInfo)]
+    lib.ocrvi_png_parse.argtypes = [vp, sz, vp, sz, C.POINTER(sz)]
+    lib.ocrvi_png_table_entry.argtypes = [C.POINTER(PngInfo), sz, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp]
+    lib.ocrvi_png_plan.argtypes = [C.POINTER(PngInfo), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    lib.ocrvi_png_decode_pages.argtypes = [i32, vp, vp, i32, vp, vp, sz, vp]
     lib.ocrvi_jpeg_quant_tables.argtypes = [i32, vp, vp]
     lib.ocrvi_jpeg_encode_header.argtypes = [i32, i32, i32, i32, i32, vp, sz, C.POINTER(sz)]
     lib.ocrvi_jpeg_encode_sizes.argtypes = [i32, i32, i32, i32, C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]

@@ -4,7 +4,7 @@ from polygon annotations.
 
 Per batch: the polygon geometry of all its images in one host call (``ocrvi_db_target_jobs``: validity, area, perimeter, Clipper's
 shrinking and dilating offset), one upload of the fill jobs, and two kernels -- ``ocrvi_db_target_maps`` (``gt``, ``mask``, ``thresh_map``,
-``thresh_mask``) and ``ocrvi_resize_normalize_pad_pages`` (``image``).  JPEG files are decoded on the device by ``pipeline.imdecode``.
+``thresh_mask``) and ``ocrvi_resize_normalize_pad_pages`` (``image``).  JPEG and PNG files are decoded on the device by ``pipeline.imdecode``.
 Augmentation (dataloader.py:200-234) is training and is not here.  include/ocrvi.h ("DB ground truth") states the arithmetic."""
 from __future__ import annotations
 
@@ -12,6 +12,7 @@ import ctypes as C
 import glob
 import json
 import os
+import re
 from typing import Dict, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -22,7 +23,7 @@ from . import pipeline
 
 MAPS = ("gt", "mask", "thresh_map", "thresh_mask")
 # what cv2.imread decodes and this library does not: such a file must not be blanked silently
-_FOREIGN = ((b"\x89PNG\r\n\x1a\n", "PNG"), (b"BM", "BMP"), (b"II*\x00", "TIFF"), (b"MM\x00*", "TIFF"), (b"RIFF", "WebP / RIFF"),
+_FOREIGN = ((b"BM", "BMP"), (b"II*\x00", "TIFF"), (b"MM\x00*", "TIFF"), (b"RIFF", "WebP / RIFF"),
             (b"\x00\x00\x00\x0cjP  ", "JPEG 2000"), (b"P5", "PGM"), (b"P6", "PPM"))
 
 
@@ -80,7 +81,7 @@ class DetectionDataset:
     """``DetectionDataset(data_dir)`` reads the reference's layout: the sorted ``*.json`` files of ``data_dir``, each with
     ``annotations[].polygon`` (polygons of at least 3 points are kept) and its image beside it (``.jpg``, then ``.png``).
     ``DetectionDataset(samples=[(image, polygons), ...])`` takes images directly: a uint8 HxWx3 RGB array or tensor, or the bytes of a
-    baseline JPEG file.
+    baseline JPEG file or of a PNG file.
 
     ``len(ds)``, ``ds[i]`` (the reference's dict of ``image`` [3,S,S] and ``gt``, ``mask``, ``thresh_map``, ``thresh_mask`` [1,S,S], float32
     on ``device``) and ``ds.batches(batch_size)`` (dicts of [B,...] tensors, in order, the last one short).  ``thresh_maps=True`` fills the
@@ -88,8 +89,8 @@ class DetectionDataset:
     so ``thresh_min`` is kept for the signature only.
 
     A sample the reference would replace by ``_blank_sample()`` -- an unreadable image, a broken annotation, a side that resizes to 0 --
-    yields that blank sample and is recorded in ``ds.blank`` as (index, reason).  A file cv2 would read and this library cannot (PNG,
-    progressive JPEG, ...) raises ValueError naming it."""
+    yields that blank sample and is recorded in ``ds.blank`` as (index, reason).  A file cv2 would read and this library cannot (BMP,
+    progressive JPEG, an interlaced PNG, ...) and a JPEG or PNG file the library finds corrupt raise ValueError naming it."""
 
     def __init__(self, data_dir: Optional[str] = None, samples: Optional[Sequence] = None, image_size: int = 640, shrink_ratio: float = 0.4,
                  thresh_min: float = 0.3, thresh_max: float = 0.7, thresh_maps: bool = False, device: str = "cuda:0"):
@@ -128,7 +129,7 @@ class DetectionDataset:
         return out
 
     def _read_file(self, json_path: str):
-        """-> (JPEG bytes, polygons); an Exception here is what the reference turns into a blank sample, a ValueError from
+        """-> (path, JPEG or PNG bytes, polygons); an Exception here is what the reference turns into a blank sample, a ValueError from
         ``_foreign`` is not."""
         with open(json_path, "r", encoding="utf-8") as f:
             annotation = json.load(f)
@@ -142,14 +143,15 @@ class DetectionDataset:
                 continue
             for magic, fmt in _FOREIGN:
                 if data.startswith(magic):
-                    raise _Foreign(f"{path}: a {fmt} file; only baseline JPEG is decoded here")
-            if data.startswith(b"\xff\xd8"):
+                    raise _Foreign(f"{path}: a {fmt} file; only baseline JPEG and PNG are decoded here")
+            if data.startswith(b"\xff\xd8") or data.startswith(pipeline.PNG_SIGNATURE):
                 return path, data, self._polygons(a["polygon"] for a in annotation.get("annotations", []))
             data = None                                       # neither cv2 nor this library reads it: try the next name
         raise OSError(f"Cannot read image for {os.path.basename(json_path)}")
 
     def _load(self, idx: int):
-        """-> (image source, polygons, (h, w)) or None for a blank sample.  The source is a device/host uint8 tensor or JPEG bytes."""
+        """-> (image source, polygons, (h, w, new_h, new_w), name) or None for a blank sample.  The source is a device/host uint8 tensor or
+        the bytes of a JPEG or PNG file."""
         item = self.samples[idx]
         name = f"sample {idx}"
         try:
@@ -162,14 +164,14 @@ class DetectionDataset:
         except Exception as e:                                # dataloader.py:281-286
             self._note_blank(idx, f"{type(e).__name__}: {e}")
             return None
-        if isinstance(image, pipeline.JPEG_BYTES):
-            info = pipeline.jpeg_info_struct(image, name)     # ValueError naming the file for what the library refuses
+        if isinstance(image, pipeline.IMAGE_BYTES):            # ValueError naming the file for what the library refuses
+            info = (pipeline.png_info_struct if pipeline.is_png(image) else pipeline.jpeg_info_struct)(image, name)
             h, w = info.out_height, info.out_width
         else:
             if isinstance(image, np.ndarray):
                 image = torch.from_numpy(np.ascontiguousarray(image))
             if not (isinstance(image, torch.Tensor) and image.dtype == torch.uint8 and image.dim() == 3 and image.shape[2] == 3):
-                raise ValueError(f"{name}: an image is a uint8 HxWx3 array or tensor, or JPEG bytes")
+                raise ValueError(f"{name}: an image is a uint8 HxWx3 array or tensor, or JPEG or PNG bytes")
             h, w = int(image.shape[0]), int(image.shape[1])
         if h < 1 or w < 1:
             self._note_blank(idx, f"empty image ({h} x {w})")
@@ -180,7 +182,7 @@ class DetectionDataset:
         if new_h < 1 or new_w < 1:                            # cv2.resize raises on an empty destination
             self._note_blank(idx, f"{h} x {w} resizes to {new_h} x {new_w}")
             return None
-        return image, polygons, (h, w, new_h, new_w)
+        return image, polygons, (h, w, new_h, new_w), name
 
     # ---------------------------------------------------------------------------------------------- batches
     def _batch(self, indices: Sequence[int]) -> Dict[str, torch.Tensor]:
@@ -193,10 +195,17 @@ class DetectionDataset:
         sizes = np.maximum(rows[:, :2], 1)                    # a blank sample has no polygons; its size is not read
         jobs, points = target_jobs(sizes, [item[1] if item is not None else [] for item in loaded], self.shrink_ratio, self.thresh_maps)
         with torch.cuda.device(dev):
-            jpegs = [k for k, item in enumerate(loaded) if item is not None and isinstance(item[0], pipeline.JPEG_BYTES)]
+            files = [k for k, item in enumerate(loaded) if item is not None and isinstance(item[0], pipeline.IMAGE_BYTES)]
             pages: List[Optional[torch.Tensor]] = [None] * n
-            if jpegs:
-                for k, page in zip(jpegs, pipeline.imdecode([loaded[k][0] for k in jpegs], str(dev))):
+            if files:
+                try:
+                    decoded = pipeline.imdecode([loaded[k][0] for k in files], str(dev))
+                except ValueError as e:                       # a corrupt file, found while decoding: named by its file, not its index
+                    m = re.match(r"imdecode: file (\d+): (.*)", str(e), re.S)
+                    if m is None:
+                        raise
+                    raise ValueError(f"{loaded[files[int(m.group(1))]][3]}: {m.group(2)}") from None
+                for k, page in zip(files, decoded):
                     pages[k] = page
             for k, item in enumerate(loaded):
                 if item is not None and pages[k] is None:

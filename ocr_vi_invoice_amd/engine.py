@@ -29,8 +29,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .pipeline import (JPEG_BYTES, DBPostProcessor, _check_crop, db_boxes_pages, enhance_init, enhance_workspace_bytes, four_point_geometry,
-                       jpeg_info_struct, jpeg_parse_into, jpeg_table_entry, overlay_paint_, overlay_segments, quad_crops)
+from .pipeline import (IMAGE_BYTES, DBPostProcessor, _check_crop, db_boxes_pages, enhance_init, enhance_workspace_bytes, four_point_geometry,
+                       is_png, jpeg_info_struct, jpeg_parse_into, jpeg_table_entry, overlay_paint_, overlay_segments, png_info_struct,
+                       png_parse_into, png_table_entry, quad_crops)
 
 _ARENA_ALIGN = 256
 _STREAMS: Dict[int, Tuple[torch.cuda.Stream, torch.cuda.Stream]] = {}
@@ -114,7 +115,11 @@ class Engine:
     (``ocrvi_jpeg_parse``) before any device work, so a bad file raises ValueError naming its page and leaves nothing in flight; its
     coefficient stream goes through pinned staging with its chunk and ``ocrvi_jpeg_decode_pages`` decodes it straight into its arena
     slot (into the raw region when it has a quad), ahead of the chunk's warp and enhancement.  The results are those of the same page
-    passed as the array ``pipeline.imdecode`` returns.
+    passed as the array ``pipeline.imdecode`` returns.  A page may equally be the bytes of a PNG file (told apart by its signature): its
+    size comes from ``ocrvi_png_info``, it is inflated on the same host pool in the same stage (``ocrvi_png_parse``), its stream -- the
+    filtered scanlines, for grey, palette and bilevel pages 1/3 to 1/24 of the RGB bytes -- goes through the same pinned staging, and one
+    ``ocrvi_png_decode_pages`` launch per chunk decodes it into the same place.  ``stats`` counts ``jpeg`` / ``png`` pages, their
+    ``*_stream_bytes`` and ``*_parse_s``.
     ``annotate=True`` (the constructor's argument, or the attribute set between runs; ``run``'s own parameters stay as they were): each
     page's result is a 4-tuple ``(boxes, scores, texts, annotated)``; ``annotated`` is a
     new device uint8 tensor: the page as the detector saw it (rectified and enhanced where asked for, as the reference draws on its
@@ -203,6 +208,9 @@ class Engine:
         self.d_jws = torch.empty(0, dtype=torch.uint8, **d)
         self.d_jtab = torch.zeros((self.det_chunk, _lib.JPEG_ENTRY), dtype=torch.int64, **d)
         self.h_jtab = [torch.zeros((self.det_chunk, _lib.JPEG_ENTRY), dtype=torch.int64).pin_memory() for _ in range(2)]
+        # ---- PNG pages share the stream region, its pinned slots and the workspace (there: the lines between bands); their table
+        self.d_ptab = torch.zeros((self.det_chunk, _lib.PNG_ENTRY), dtype=torch.int64, **d)
+        self.h_ptab = [torch.zeros((self.det_chunk, _lib.PNG_ENTRY), dtype=torch.int64).pin_memory() for _ in range(2)]
         # one stream pair per device for every engine of the process: each new HIP stream takes the next hardware queue round-robin
         if self.devi not in _STREAMS:
             _STREAMS[self.devi] = (torch.cuda.Stream(self.dev), torch.cuda.Stream(self.dev))
@@ -210,7 +218,7 @@ class Engine:
         self._det_graphs: "collections.OrderedDict[tuple, torch.cuda.CUDAGraph]" = collections.OrderedDict()
         self._rec_graph = None
         self._rec_warm = False
-        self._pool = None                          # host threads of the JPEG entropy decoder, started with the first file
+        self._pool = None                          # host threads of the JPEG entropy decoder and of inflate, started with the first file
         self.annotate = bool(annotate)             # read at the start of every run; may be switched between runs
         self._annotate, self._annotated = False, []   # the running call's switch and its painted copies of the pages
         self.stats = {}
@@ -275,23 +283,26 @@ class Engine:
     # ------------------------------------------------------------------------------------------------ input
     @staticmethod
     def _check_page(i, p, info=None):
-        if isinstance(p, JPEG_BYTES):             # a JPEG file: its size after orientation (ValueError naming the page for a bad header)
-            info = jpeg_info_struct(p, f"page {i}") if info is None else info
+        if isinstance(p, IMAGE_BYTES):            # a JPEG file: its size after orientation; a PNG file: its size (ValueError naming the page)
+            if info is None:
+                info = (png_info_struct if is_png(p) else jpeg_info_struct)(p, f"page {i}")
             return int(info.out_height), int(info.out_width)
         if isinstance(p, np.ndarray):
             ok = p.dtype == np.uint8
         elif isinstance(p, torch.Tensor):
             ok = p.dtype == torch.uint8
         else:
-            raise ValueError(f"page {i}: expected an RGB uint8 HxWx3 numpy array or tensor, or JPEG bytes, got {type(p).__name__}")
+            raise ValueError(f"page {i}: expected an RGB uint8 HxWx3 numpy array or tensor, or JPEG or PNG bytes, got {type(p).__name__}")
         if not ok or p.ndim != 3 or p.shape[2] != 3:
             raise ValueError(f"page {i}: expected an RGB uint8 HxWx3 array, got dtype {p.dtype} shape {tuple(p.shape)}")
         return int(p.shape[0]), int(p.shape[1])
 
     def _parse_jpegs(self, pages, infos):
-        """Entropy-decodes every JPEG page of the call on the engine's host pool (``post_threads`` threads, the budget of the box stage,
-        which never runs at the same time): {page index: (info, uint32 stream, bytes used)}.  ValueError naming the first bad page;
-        nothing has touched the device by then.
+        """Entropy-decodes every JPEG page and inflates every PNG page of the call on the engine's host pool (``post_threads`` threads,
+        the budget of the box stage, which never runs at the same time): {page index: (info, uint32 stream, bytes used)}; the info is a
+        ``JpegInfo`` or a ``PngInfo``.  ValueError naming the first bad page; nothing has touched the device by then.  ``jpeg_parse_s``
+        and ``png_parse_s`` are the wall time from the start of this stage until the last file of that format was done (the two
+        overlap when a call holds both).
         A stream waits in pageable memory until its chunk is staged and is dropped there.  It cannot be decoded into the pinned slot it
         is uploaded from: the two slots belong to the chunks in flight, while a corrupt scan must be found, for every file of the call,
         before the first chunk is launched; pinned room for a whole call would be hundreds of megabytes for a folder of pages.  The
@@ -301,8 +312,13 @@ class Engine:
         t0 = time.perf_counter()
 
         def one(i):
-            buf = np.empty(infos[i].stream_bytes // 4, np.uint32)
-            return infos[i], buf, jpeg_parse_into(pages[i], buf.ctypes.data, buf.nbytes, f"page {i}")
+            if isinstance(infos[i], _lib.PngInfo):
+                buf = np.empty((infos[i].stream_bytes + 3) // 4, np.uint32)
+                used = png_parse_into(pages[i], buf.ctypes.data, buf.nbytes, f"page {i}")
+            else:
+                buf = np.empty(infos[i].stream_bytes // 4, np.uint32)
+                used = jpeg_parse_into(pages[i], buf.ctypes.data, buf.nbytes, f"page {i}")
+            return infos[i], buf, used, time.perf_counter()
 
         if self._pool is None:
             import concurrent.futures
@@ -311,35 +327,50 @@ class Engine:
         out, err = {}, None
         for i, f in futs:                         # every job is waited for, the first failure in page order is raised
             try:
-                out[i] = f.result()
+                info, buf, used, done = f.result()
+                out[i] = (info, buf, used)
+                key = "png_parse_s" if isinstance(infos[i], _lib.PngInfo) else "jpeg_parse_s"
+                self.stats[key] = max(self.stats[key], done - t0)
             except Exception as e:               # noqa: BLE001
                 err = err or e
         if err is not None:
             raise err
-        self.stats["jpeg_parse_s"] = time.perf_counter() - t0
         return out
 
     def _decode_jpegs(self, wave, lo, hi, s, targets):
-        """The JPEG pages of chunk wave[lo:hi] -> ``targets`` [(page index, destination address)], one ``ocrvi_jpeg_decode_pages`` launch
-        on the detector stream: streams and table through pinned slot ``s``."""
-        tab = self.h_jtab[s].numpy()
+        """The JPEG and PNG pages of chunk wave[lo:hi] -> ``targets`` [(page index, destination address)], one ``ocrvi_jpeg_decode_pages``
+        and one ``ocrvi_png_decode_pages`` launch (whichever format the chunk holds) on the detector stream: streams and tables through
+        pinned slot ``s``; the two formats share the stream region and the workspace."""
+        jtab, ptab = self.h_jtab[s].numpy(), self.h_ptab[s].numpy()
         stage = self.h_jrec[s].numpy()
         base = self.arena.data_ptr()
-        soff = woff = 0
-        for k, (i, dst_ptr) in enumerate(targets):
+        soff = woff = nj = npng = 0
+        for i, dst_ptr in targets:
             info, buf, used = self._jpeg[i]
-            stage[soff:soff + used].view(np.uint32)[:] = buf[:used // 4]
+            stage[soff:soff + used] = buf.view(np.uint8)[:used]
             self._jpeg[i] = (info, None, used)     # the host copy has served: only its sizes are still read
-            jpeg_table_entry(info, used, soff, dst_ptr - base, 3 * info.out_width, woff, tab[k])
+            if isinstance(info, _lib.PngInfo):
+                png_table_entry(info, used, soff, dst_ptr - base, 3 * info.out_width, woff, ptab[npng])
+                npng += 1
+                self.stats["png_stream_bytes"] += used
+            else:
+                jpeg_table_entry(info, used, soff, dst_ptr - base, 3 * info.out_width, woff, jtab[nj])
+                nj += 1
+                self.stats["jpeg_stream_bytes"] += used
             soff += (used + _ARENA_ALIGN - 1) // _ARENA_ALIGN * _ARENA_ALIGN
             woff += info.workspace_bytes
-        n = len(targets)
         self.d_jrec[:soff].copy_(self.h_jrec[s][:soff], non_blocking=True)
-        self.d_jtab[:n].copy_(self.h_jtab[s][:n], non_blocking=True)
-        _lib.check(self.lib.ocrvi_jpeg_decode_pages(self.devi, self.d_jrec.data_ptr(), self.d_jtab.data_ptr(), n, base, self.d_jws.data_ptr(),
-                                                    self.d_jws.numel(), self.s_det.cuda_stream))
-        self.stats["jpeg"] += n
-        self.stats["jpeg_stream_bytes"] += sum(self._jpeg[i][2] for i, _ in targets)
+        if nj:
+            self.d_jtab[:nj].copy_(self.h_jtab[s][:nj], non_blocking=True)
+            _lib.check(self.lib.ocrvi_jpeg_decode_pages(self.devi, self.d_jrec.data_ptr(), self.d_jtab.data_ptr(), nj, base, self.d_jws.data_ptr(),
+                                                        self.d_jws.numel(), self.s_det.cuda_stream))
+        if npng:
+            self.d_ptab[:npng].copy_(self.h_ptab[s][:npng], non_blocking=True)
+            _lib.check(self.lib.ocrvi_png_decode_pages(self.devi, self.d_jrec.data_ptr(), self.d_ptab.data_ptr(), npng, base,
+                                                       self.d_jws.data_ptr() if self.d_jws.numel() else None, self.d_jws.numel(),
+                                                       self.s_det.cuda_stream))
+        self.stats["jpeg"] += nj
+        self.stats["png"] += npng
 
     def _stage(self, pages, wave, lo, hi, s=0):
         """Pages wave[lo:hi] (consecutive arena slots) -> the arena, on the detector stream.  A page with a quad is warped into its slot
@@ -580,8 +611,8 @@ class Engine:
     def run(self, pages: Sequence, quads: Sequence = None, enhance=None) -> List[Tuple[list, list, list]]:
         pages = list(pages)
         self._annotate, self._annotated = bool(self.annotate), [None] * len(pages)
-        t_start = time.perf_counter()              # (total_s includes the host entropy decode of JPEG pages)
-        infos = {i: jpeg_info_struct(p, f"page {i}") for i, p in enumerate(pages) if isinstance(p, JPEG_BYTES)}
+        t_start = time.perf_counter()              # (total_s includes the host entropy decode of JPEG pages and the inflate of PNG pages)
+        infos = {i: (png_info_struct if is_png(p) else jpeg_info_struct)(p, f"page {i}") for i, p in enumerate(pages) if isinstance(p, IMAGE_BYTES)}
         raw_sizes = [self._check_page(i, p, infos.get(i)) for i, p in enumerate(pages)]
         # (every ValueError -- pages, quads, sizes that round to 0 -- is raised here, before any GPU work)
         sizes, mats, shapes, scales, buckets = plan_rectified(raw_sizes, quads, self.det_size)
@@ -606,7 +637,7 @@ class Engine:
             self.stats["quad_s"] = 0.0             # host time of ocrvi_min_area_quads + ocrvi_quad_crops (not part of post_s)
         if not pages:
             return []
-        self.stats.update(jpeg=0, jpeg_stream_bytes=0, jpeg_parse_s=0.0)
+        self.stats.update(jpeg=0, jpeg_stream_bytes=0, jpeg_parse_s=0.0, png=0, png_stream_bytes=0, png_parse_s=0.0)
         self._jpeg = self._parse_jpegs(pages, infos)      # (a corrupt scan raises here: still before any GPU work)
         self._sizes, self._shapes, self._scales = sizes, shapes, scales
         self._raw_sizes, self._mats, self._keep = raw_sizes, mats, []

@@ -660,19 +660,74 @@ def _align(v: int, a: int = 256) -> int:
     return (v + a - 1) // a * a
 
 
-def imdecode(data, device: str = "cuda:0"):
-    """cv2.imdecode / cv2.imread + cvtColor(BGR2RGB) (src/pipeline/pipeline2.py:284-288) for baseline JPEG: ``data`` is the bytes of one file
-    (-> one uint8 [h, w, 3] RGB tensor on ``device``) or a list of them (-> a list of tensors, decoded in one batched launch).  Entropy
-    decoding runs on the host (a thread per file), everything else in ``ocrvi_jpeg_decode_pages`` on the current stream; the EXIF
-    orientation is applied.  ValueError for an unsupported or corrupt file (naming its index in a list); there is no host decoder behind
-    this one.  The arithmetic is stated in include/ocrvi.h: PIL / libjpeg-turbo's output for encoder-produced files, cv2 parity unpinned."""
-    single = isinstance(data, JPEG_BYTES)
-    files = [data] if single else list(data)
-    if not files:
-        return []
-    names = ["imdecode" if single else f"imdecode: file {i}" for i in range(len(files))]
-    infos = [jpeg_info_struct(f, w) for f, w in zip(files, names)]
-    dev = torch.device(device)
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+IMAGE_BYTES = JPEG_BYTES                          # what an encoded page may be: the bytes of a baseline JPEG file or of a PNG file
+
+
+def is_png(data) -> bool:
+    """Whether ``data`` (``IMAGE_BYTES``) starts with the PNG signature; everything else is handed to the JPEG decoder, whose messages
+    name what is wrong with it."""
+    return isinstance(data, IMAGE_BYTES) and _jpeg_view(data)[:8].tobytes() == PNG_SIGNATURE
+
+
+def png_info_struct(data, what: str = "png") -> "_lib.PngInfo":
+    """``ocrvi_png_info`` (host only); ValueError ``what: message`` for a file the library refuses or cannot read."""
+    a = _jpeg_view(data)
+    info = _lib.PngInfo()
+    rc = _lib.load().ocrvi_png_info(a.ctypes.data if a.size else None, a.size, ctypes.byref(info))
+    if rc == -1:
+        raise ValueError(f"{what}: {info.reason.decode('utf-8', 'replace')}")
+    _lib.check(rc)
+    return info
+
+
+def png_info(data) -> dict:
+    """What ``ocrvi_png_info`` reports about a PNG file (host only, needs no GPU).  ValueError naming the feature for an unsupported
+    file, or the fault of a corrupt one."""
+    info = png_info_struct(data)
+    return {k: getattr(info, k) for k in ("width", "height", "bit_depth", "colour_type", "channels", "row_bytes", "out_height", "out_width",
+                                          "palette_entries", "idat_bytes", "stream_bytes", "workspace_bytes")}
+
+
+def png_parse_into(data, out_ptr: int, cap: int, what: str = "png") -> int:
+    """``ocrvi_png_parse`` into ``cap`` bytes at ``out_ptr``; returns the bytes used.  The error is read on the calling thread (it is
+    thread-local): ValueError for a corrupt file, MemoryError for a short buffer."""
+    a = _jpeg_view(data)
+    used = ctypes.c_size_t()
+    rc = _lib.load().ocrvi_png_parse(a.ctypes.data if a.size else None, a.size, out_ptr, cap, ctypes.byref(used))
+    if rc == -1:
+        raise ValueError(f"{what}: {_lib.last_error()}")
+    _lib.check(rc)
+    return used.value
+
+
+def png_parse(data) -> np.ndarray:
+    """The stream of a file as uint8 (host only; include/ocrvi.h states the format)."""
+    info = png_info_struct(data)
+    buf = np.empty(info.stream_bytes, np.uint8)
+    return buf[:png_parse_into(data, buf.ctypes.data, buf.nbytes)]
+
+
+def png_table_entry(info, used: int, stream_offset: int, dst_offset: int, dst_stride: int, workspace_offset: int, entry: np.ndarray) -> None:
+    """``ocrvi_png_table_entry`` into ``entry`` (int64 [PNG_ENTRY], contiguous)."""
+    assert entry.dtype == np.int64 and entry.size == _lib.PNG_ENTRY and entry.flags.c_contiguous
+    _lib.check(_lib.load().ocrvi_png_table_entry(ctypes.byref(info), used, stream_offset, dst_offset, dst_stride, workspace_offset,
+                                                 entry.ctypes.data))
+
+
+def png_plan(info) -> dict:
+    """``ocrvi_png_plan`` (host only): ``band_rows``, ``chunk_bytes``, ``bands`` and ``steps`` of the kernel's walk over the page."""
+    v = [ctypes.c_int() for _ in range(4)]
+    _lib.check(_lib.load().ocrvi_png_plan(ctypes.byref(info), *[ctypes.byref(x) for x in v]))
+    return dict(zip(("band_rows", "chunk_bytes", "bands", "steps"), (x.value for x in v)))
+
+
+def _imdecode_group(files, names, dev, png: bool):
+    """The files of one format -> pages, in one batched launch (``ocrvi_png_decode_pages`` / ``ocrvi_jpeg_decode_pages``)."""
+    lib = _lib.load()
+    info_of, parse_into, entry_of, width = ((png_info_struct, png_parse_into, png_table_entry, _lib.PNG_ENTRY) if png else
+                                            (jpeg_info_struct, jpeg_parse_into, jpeg_table_entry, _lib.JPEG_ENTRY))
+    infos = [info_of(f, w) for f, w in zip(files, names)]
     devi = _dev_index(dev)
     s_off, w_off, d_off = [0], [0], [0]
     for info in infos:
@@ -683,12 +738,12 @@ def imdecode(data, device: str = "cuda:0"):
     base = h_rec.data_ptr()
     jobs = [(f, base + s_off[i], infos[i].stream_bytes, names[i]) for i, f in enumerate(files)]
     if len(files) > 1:
-        used = list(jpeg_pool().map(lambda j: jpeg_parse_into(*j), jobs))
+        used = list(jpeg_pool().map(lambda j: parse_into(*j), jobs))
     else:
-        used = [jpeg_parse_into(*jobs[0])]
-    table = np.zeros((len(files), _lib.JPEG_ENTRY), np.int64)
+        used = [parse_into(*jobs[0])]
+    table = np.zeros((len(files), width), np.int64)
     for i, info in enumerate(infos):
-        jpeg_table_entry(info, used[i], s_off[i], d_off[i], 3 * info.out_width, w_off[i], table[i])
+        entry_of(info, used[i], s_off[i], d_off[i], 3 * info.out_width, w_off[i], table[i])
     with torch.cuda.device(dev):
         d_rec = torch.empty(s_off[-1], dtype=torch.uint8, device=dev)
         for i in range(len(files)):            # only the bytes each stream uses cross the bus
@@ -696,17 +751,43 @@ def imdecode(data, device: str = "cuda:0"):
         d_tab = torch.from_numpy(table).pin_memory().to(dev, non_blocking=True)
         ws = torch.empty(max(w_off[-1], 8), dtype=torch.uint8, device=dev)
         out = torch.empty(d_off[-1], dtype=torch.uint8, device=dev)
-        _lib.check(_lib.load().ocrvi_jpeg_decode_pages(devi, d_rec.data_ptr(), d_tab.data_ptr(), len(files), out.data_ptr(), ws.data_ptr(),
-                                                       ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
-    pages = [out[d_off[i]:d_off[i] + info.out_height * info.out_width * 3].view(info.out_height, info.out_width, 3)
-             for i, info in enumerate(infos)]
+        decode = lib.ocrvi_png_decode_pages if png else lib.ocrvi_jpeg_decode_pages
+        _lib.check(decode(devi, d_rec.data_ptr(), d_tab.data_ptr(), len(files), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                          torch.cuda.current_stream(dev).cuda_stream))
+    return [out[d_off[i]:d_off[i] + info.out_height * info.out_width * 3].view(info.out_height, info.out_width, 3)
+            for i, info in enumerate(infos)]
+
+
+def imdecode(data, device: str = "cuda:0"):
+    """cv2.imdecode / cv2.imread + cvtColor(BGR2RGB) (src/pipeline/pipeline2.py:284-288) for baseline JPEG and PNG: ``data`` is the bytes
+    of one file (-> one uint8 [h, w, 3] RGB tensor on ``device``) or a list of them (-> a list of tensors in the caller's order).  The
+    decoder is chosen per file by its signature (the PNG signature against FF D8); a list may mix the two formats and costs one batched
+    launch per format.  What is serial per file runs on the host, a thread per file (JPEG: entropy decoding; PNG: inflate), everything else
+    in ``ocrvi_jpeg_decode_pages`` / ``ocrvi_png_decode_pages`` on the current stream; a JPEG's EXIF orientation is applied.  ValueError for
+    an unsupported or corrupt file (naming its index in a list); there is no host decoder behind these.  The arithmetic is stated in
+    include/ocrvi.h: PIL's output for encoder-produced JPEG files and for PNG (16-bit grey aside), cv2 parity unpinned."""
+    single = isinstance(data, IMAGE_BYTES)
+    files = [data] if single else list(data)
+    if not files:
+        return []
+    names = ["imdecode" if single else f"imdecode: file {i}" for i in range(len(files))]
+    dev = torch.device(device)
+    png = [is_png(f) for f in files]
+    for i, f in enumerate(files):              # every header is read (a bad one named, in the caller's order) before anything is decoded
+        (png_info_struct if png[i] else jpeg_info_struct)(f, names[i])
+    pngs, jpegs = [i for i, p in enumerate(png) if p], [i for i, p in enumerate(png) if not p]
+    pages = [None] * len(files)
+    for group, as_png in ((jpegs, False), (pngs, True)):
+        if group:
+            for i, page in zip(group, _imdecode_group([files[i] for i in group], [names[i] for i in group], dev, as_png)):
+                pages[i] = page
     return pages[0] if single else pages
 
 
 def imread(path: str, device: str = "cuda:0") -> torch.Tensor:
-    """``cv2.imread(path)`` + ``cvtColor(BGR2RGB)`` of the reference's loop (pipeline2.py:284-288) for a baseline JPEG file: the file's bytes
-    through ``imdecode``.  OSError for an unreadable file (the reference gets ``None`` and skips the image), ValueError for one that is
-    not a supported JPEG."""
+    """``cv2.imread(path)`` + ``cvtColor(BGR2RGB)`` of the reference's loop (pipeline2.py:284-288) for a baseline JPEG or a PNG file: the file's
+    bytes through ``imdecode``.  OSError for an unreadable file (the reference gets ``None`` and skips the image), ValueError for one that
+    is neither a supported JPEG nor a supported PNG."""
     with open(path, "rb") as f:
         return imdecode(f.read(), device)
 
@@ -1038,7 +1119,7 @@ def detect_and_recognize(original_image, det_model, rec_model, post_processor: D
     """Steps 2 and 3 of the reference's per-image loop (pipeline2.py:306-352) with every stage on this library: resize + normalise on the
     device -> ``det_model`` -> ``post_processor`` on the host copy of the binary map -> boxes rescaled to the original image -> the
     bounding rectangle of each box cropped, resized and normalised on the device straight from the uploaded page -> ``rec_model`` greedy
-    CTC in batches of ``rec_batch_size``.  ``original_image``: RGB uint8 HxWx3 (numpy or device tensor), or the bytes of a baseline JPEG file
+    CTC in batches of ``rec_batch_size``.  ``original_image``: RGB uint8 HxWx3 (numpy or device tensor), or the bytes of a baseline JPEG or a PNG file
     (``bytes`` / ``bytearray`` / ``memoryview``: ``imdecode`` first, the reference's cv2.imread, pipeline2.py:284-288).
     ``binary_head``: call ``det_model.forward_binary`` (the binarise branch alone; same map in f32 / f16x2) instead of ``det_model(...)``.
     ``quad``: the document's four corners in ``original_image`` (step 1, pipeline2.py:291-302): the page is rectified first
@@ -1049,7 +1130,7 @@ def detect_and_recognize(original_image, det_model, rec_model, post_processor: D
     recogniser instead of its bounding rectangle (``quad_crops``, ``preprocess_crops_quad``); boxes and scores do not change.
     Returns (rescaled_boxes [int32 (n_i, 2)], scores, texts); empty crops decode the all-zero tensor as pipeline2.py:154-156 does."""
     _check_crop(crop)
-    if isinstance(original_image, JPEG_BYTES):               # a JPEG file's bytes: decoded on the device (``imdecode``)
+    if isinstance(original_image, IMAGE_BYTES):              # a JPEG or PNG file's bytes: decoded on the device (``imdecode``)
         original_image = imdecode(original_image, device)
     page = original_image if isinstance(original_image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(original_image))
     page = page.to(device).contiguous()
