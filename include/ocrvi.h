@@ -567,6 +567,96 @@ int ocrvi_jpeg_encode_pages(int device, const void* src_base, const int64_t* tab
                             void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * PNG encode: the lossless way out of the device -- pages for the readers that take .png (DetectionDataset, the reference's recognition
+ * loader, src/rec2/dataloader.py:188), annotated pages whose thin outlines JPEG rings around, crops saved for labelling.  Row filtering,
+ * deflate, Adler-32, CRC-32 and the assembly of the file all run on the device, batched over pages; only the file's bytes leave it.
+ * Input is uint8 RGB (3 bytes per pixel) or uint8 grey (1 byte per pixel).  Written: bit depth 8, colour type 2 or 0, no interlace, and
+ * exactly the chunks IHDR, one IDAT, IEND.  Not built: palette, 16-bit or alpha output, Adam7, ancillary chunks, detection of R = G = B.
+ * The arithmetic is the library's own definition, stated here; tests/pngenc_ref.py restates it in NumPy.  Any inflater reads the result
+ * (zlib, PIL and ocrvi_png_parse are pinned by the tests); no other encoder writes the same bytes.  All values are integers.
+ *   filters     bpp = components; x = the raw byte, a = the raw byte bpp to the left, b = the raw byte above, c = the raw byte above-left
+ *               (each 0 outside the row or the image: the predictors are raw neighbours, so rows are independent); filtered byte =
+ *               (x - p) & 255 with p = 0, a, b, (a + b) >> 1 or Paeth(a, b, c) (as under "PNG decode") for filters 0 .. 4
+ *   adaptive    libpng's heuristic: the cost of a filter is the sum of min(v, 256 - v) over the row's filtered bytes (the filter byte is
+ *               not counted); the smallest cost wins, ties go to the lower filter number.  A fixed mode gives every row that filter
+ *   stream      height x (1 + row_bytes) bytes, every row led by its filter byte; row_bytes = width x components
+ *   deflate     the strategy zlib calls Z_RLE: matches at distance 1 only, every block with the cheapest of the three codings.  The
+ *               stream is cut into blocks of OCRVI_PNG_ENC_BLOCK bytes (the last may be shorter); no match crosses a block's end
+ *   eq          eq[i] = i > 0 and s[i] == s[i - 1] over the whole page stream.  Inside a block a RUN is a maximal set of consecutive
+ *               positions with eq = 1; it ends where the block ends, and a block whose first byte has eq = 1 begins with a run (whose
+ *               matches reach back into the previous block, whatever its type)
+ *   tokens      a byte with eq = 0 is a literal.  A run of L bytes is floor(L / 258) matches of length 258, then its remainder r = L mod
+ *               258: one match of length r when r >= 3, else r literals.  Every match has distance 1
+ *   counts      per block, of the literal / length symbols 0..285 (RFC 1951, 3.2.5); the end-of-block symbol 256 is counted once
+ *   code        lengths from counts, by Huffman's algorithm and a deterministic overflow repair: a symbol of count 0 gets length 0; when
+ *               fewer than two symbols have a count, the lowest-numbered symbols of count 0 are given count 1 until two have; the m used
+ *               symbols are sorted by (count, symbol) ascending; the tree is built from two queues (the sorted leaves, and the internal
+ *               nodes in the order they are made), always taking the lighter head and the leaf on a tie; n[l] = the leaves at depth l,
+ *               depths above the limit counted at the limit; while the sum of n[l] 2^(limit - l) exceeds 2^limit: n[limit] -= 1, then for
+ *               the largest l < limit with n[l] > 0: n[l] -= 1 and n[l + 1] += 2; finally the lengths are dealt out along the sorted list:
+ *               the first n[limit] symbols get the limit, the next n[limit - 1] get limit - 1, and so on.  The code is complete (its
+ *               Kraft sum is exactly 1) and canonical (RFC 1951, 3.2.2).  Limit 15 for the literal / length code, 7 for the code-length
+ *               code.  The distance code of a dynamic block is always symbols 0 and 1 at one bit each (complete; HDIST = 2)
+ *   dynamic     HLIT = max(257, 1 + the last literal / length symbol of non-zero length).  The HLIT + 2 lengths, taken as one sequence,
+ *               are cut into maximal runs of equal values.  A run of zeros: repeatedly c = min(left, 138): symbol 18 (c - 11 in 7 bits)
+ *               when c >= 11, symbol 17 (c - 3 in 3 bits) when c >= 3, else c symbols 0.  A run of v > 0: symbol v, then while at least 3
+ *               are left c = min(left, 6): symbol 16 (c - 3 in 2 bits), then the rest as symbols v.  The code-length code is built from
+ *               the counts of these symbols; HCLEN = max(4, 1 + the last position of non-zero length in the order 16 17 18 0 8 7 9 6 10 5
+ *               11 4 12 3 13 2 14 1 15)
+ *   block type  the bits of a block as stored (3 + the padding to a byte boundary after those 3 bits at the block's position + 32 +
+ *               8 n), fixed (3 + the tokens and the end-of-block symbol in RFC 1951's fixed codes, a match costing its length code, its
+ *               extra bits and 5) and dynamic (3 + 14 + 3 HCLEN + the code-length symbols with their extra bits + the tokens and the
+ *               end-of-block symbol, a match costing its length code, its extra bits and 1); the smallest wins, ties go to the earlier of
+ *               stored, fixed, dynamic.  The last block carries BFINAL
+ *   checksums   Adler-32 of the stream from per-block partials (A = the sum of the block's n bytes, B = the sum of (n - i) x byte i,
+ *               both mod 65521): s2 = (s2 + n s1 + B) mod 65521, then s1 = (s1 + A) mod 65521, from s1 = 1, s2 = 0.  CRC-32 of IDAT's type
+ *               and data from raw partials (register 0 at the start, nothing inverted, the first four bytes of the type inverted instead)
+ *               of the file's 4096-byte segments [4096 k, 4096 (k + 1)), each multiplied by x^(8 x the bytes that follow it) mod the CRC
+ *               polynomial, XORed, inverted
+ *   file        the signature; IHDR (width, height, 8, colour type 2 or 0, 0, 0, 0); IDAT = 78 01, the blocks, the Adler-32; IEND
+ * Bound: a block never takes more bits than as stored, and a stored block ends on a byte boundary, so
+ * file <= 33 + 12 + 2 + sum over blocks (5 + block bytes) + 4 + 12 = 63 + 5 blocks + stream bytes: the output capacity.
+ * ------------------------------------------------------------------------------------------------ */
+#define OCRVI_PNG_ENC_BLOCK 16384
+#define OCRVI_PNG_FILTER_ADAPTIVE 5        /* filter modes: 0 none, 1 sub, 2 up, 3 average, 4 paeth on every row; 5 adaptive */
+/* Host only.  For a page's geometry: *stream_bytes = height x (1 + width x components), *blocks = its deflate blocks, *workspace_bytes =
+ * the device bytes ocrvi_png_encode_pages needs for it (a multiple of 256, about 1.13 x the stream), *out_capacity = bytes its file never
+ * exceeds (the bound above).  offsets (9 values, may be NULL as may the other outputs): the byte offsets of the page's regions in its
+ * workspace, for tests and tools -- 0 the filter of every row uint8 [height]; 1 the filtered stream; 2 histograms uint32 [blocks][288]
+ * (0..285 the counts, 286 the matches, 287 zero); 3 code lengths uint8 [blocks][320] (0..285 literal / length, 288..306 the code-length
+ * code by symbol, the rest zero; filled for every block, whatever its type); 4 the code-length symbols uint16 [blocks][320] (symbol |
+ * extra value << 8, zero beyond their count); 5 block records uint32 [blocks][8]: (0 bytes, 1 bits as fixed, 2 bits as dynamic, 3 HLIT,
+ * 4 HCLEN, 5 the count of code-length symbols, 6 the type 0 stored 1 fixed 2 dynamic, 7 Adler partials A | B << 16); 6 bit offsets of the
+ * blocks from the first bit of the deflate data, uint64 [blocks + 1]; 7 raw CRC partials uint32, one per 4096-byte segment of the file
+ * from segment 0 (the one IDAT's type lies in); 8 uint64 [4]: the deflate data's bytes, the Adler-32, the CRC-32, the file's bytes.
+ * OCRVI_EINVAL for sides outside 1..65500, other component counts, or a page whose IDAT could exceed 2^31 - 1 bytes. */
+int ocrvi_png_encode_sizes(int width, int height, int components, uint64_t* stream_bytes, int64_t* blocks, uint64_t* workspace_bytes,
+                           uint64_t* out_capacity, uint64_t* offsets);
+/* Host only.  Fills one entry of the table ocrvi_png_encode_pages reads, int64 [OCRVI_PNG_ENC_ENTRY]: (0 source offset, 1 source row
+ * stride, 2 width, 3 height, 4 components, 5 filter mode, 6 output offset, 7 output capacity, 8 workspace offset, 9..15 zero).  Offsets
+ * are in bytes from src_base and out_base (signed; the output offset a multiple of 16) and from workspace (a multiple of 256);
+ * src_stride >= width x components; out_capacity >= the output capacity. */
+#define OCRVI_PNG_ENC_ENTRY 16
+int ocrvi_png_encode_table_entry(int width, int height, int components, int filter, int64_t src_offset, int64_t src_stride, int64_t out_offset,
+                                 int64_t out_capacity, int64_t workspace_offset, int64_t* entry);
+/* Encodes n_pages pages in six launches (png_filter_kernel: filters, costs, the filtered stream; png_analyse_kernel: tokens, counts,
+ * both codes and the bits of every block; png_scan_kernel: block types, bit offsets, Adler-32, the file's first 43 bytes;
+ * png_pack_kernel: the blocks ORed in at those offsets; png_crc_kernel, png_finish_kernel: CRC-32, IEND).  Page i's whole file is
+ * written at out_base + its output offset and its byte count to lengths_dev[i] (int64; 0 for a skipped page).  table_dev: int64
+ * [n_pages][OCRVI_PNG_ENC_ENTRY], DEVICE memory like the pixels, read when the kernels run, so a captured graph survives rewritten
+ * tables.  Enqueue-only on `stream`: no allocation, no synchronisation.  workspace and out_base: 16-byte aligned; the pages' regions of
+ * them must not overlap.  An entry whose fields are out of range, whose regions do not fit workspace_bytes or whose capacity is below the
+ * output capacity is skipped and never dereferenced.  Source rows may be src_stride apart.  The host builds no code and sees no
+ * histogram.  The bytes are the same on every run (integer arithmetic; the atomics are adds into LDS histograms and ORs into zeroed
+ * words). */
+int ocrvi_png_encode_pages(int device, const void* src_base, const int64_t* table_dev, int n_pages, void* out_base, int64_t* lengths_dev,
+                           void* workspace, size_t workspace_bytes, void* stream);
+/* Test hook: runs the device's code-construction routine ("code" above) on n_codes histograms of n_symbols (2..288) counts each, uint32
+ * [n_codes][n_symbols] in DEVICE memory (every histogram's counts must sum below 2^32), with the length limit `limit` (1..15, n_symbols
+ * <= 2^limit); lengths_dev: uint8 [n_codes][n_symbols].  Enqueue-only on `stream`. */
+int ocrvi_test_png_code_lengths(int device, const uint32_t* counts_dev, int n_codes, int n_symbols, int limit, uint8_t* lengths_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Result overlay: the page `--save_result` writes.  Replaces draw_boxes_with_text (src/pipeline/pipeline2.py:173-190) as the per-image
  * loop calls it (:358-360) ahead of cv2.imwrite (:397-400): every box outlined, its 1-based index written beside it.  cv2.drawContours
  * and cv2.putText are not reproduced (cv2 and its Hershey glyphs are absent from the build container; its thick lines are fixed-point

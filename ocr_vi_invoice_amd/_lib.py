@@ -46,6 +46,7 @@ EXPORTS = [
     "ocrvi_test_deform_conv_raw", "ocrvi_test_dcn_plan",
     "ocrvi_test_conv_raw", "ocrvi_test_gconv_plan",
     "ocrvi_png_info", "ocrvi_png_parse", "ocrvi_png_table_entry", "ocrvi_png_plan", "ocrvi_png_decode_pages",
+    "ocrvi_png_encode_sizes", "ocrvi_png_encode_table_entry", "ocrvi_png_encode_pages", "ocrvi_test_png_code_lengths",
 ]
 PAGE_ENTRY = 4          # int64 fields of one page-table entry: (device address, height, width, 0) -- OCRVI_PAGE_ENTRY
 # ocrvi_det_eval's record: 13 slots of 8 bytes (OCRVI_DET_EVAL_*), the first six int64, the rest float64
@@ -63,6 +64,8 @@ JPEG_ENTRY = 64                 # int64 fields of one ocrvi_jpeg_decode_pages ta
 PNG_ENTRY = 16                  # int64 fields of one ocrvi_png_decode_pages table entry -- OCRVI_PNG_ENTRY
 JPEG_ENC_ENTRY = 64             # int64 fields of one ocrvi_jpeg_encode_pages table entry -- OCRVI_JPEG_ENC_ENTRY
 JPEG_HEADER_MAX = 640           # OCRVI_JPEG_HEADER_MAX
+PNG_ENC_ENTRY = 16              # int64 fields of one ocrvi_png_encode_pages table entry -- OCRVI_PNG_ENC_ENTRY
+PNG_ENC_BLOCK = 16384           # bytes of one deflate block -- OCRVI_PNG_ENC_BLOCK
 OVERLAY_SEG = 8                 # int32 fields of one overlay segment -- OCRVI_OVERLAY_SEG
 OVERLAY_PRIM = 8                # int32 fields of one overlay primitive -- OCRVI_OVERLAY_PRIM
 OVERLAY_MAX_COORD = 16384       # OCRVI_OVERLAY_MAX_COORD: page sides 1..16384, endpoints within +-16384
@@ -206,6 +209,10 @@ def load() -> C.CDLL:
     lib.ocrvi_jpeg_encode_sizes.argtypes = [i32, i32, i32, i32, C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]
     lib.ocrvi_jpeg_encode_table_entry.argtypes = [i32, i32, i32, i32, i32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp]
     lib.ocrvi_jpeg_encode_pages.argtypes = [i32, vp, vp, i32, vp, vp, vp, sz, vp]
+    lib.ocrvi_png_encode_sizes.argtypes = [i32, i32, i32, C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]
+    lib.ocrvi_png_encode_table_entry.argtypes = [i32, i32, i32, i32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp]
+    lib.ocrvi_png_encode_pages.argtypes = [i32, vp, vp, i32, vp, vp, vp, sz, vp]
+    lib.ocrvi_test_png_code_lengths.argtypes = [i32, vp, i32, i32, i32, vp, vp]
     lib.ocrvi_overlay_segments.argtypes = [vp, vp, vp, vp, vp, i32, C.c_uint32, C.c_uint32, i32, vp, C.c_int64, vp, C.c_int64, vp,
                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.ocrvi_overlay_pages.argtypes = [i32, vp, i32, vp, vp, vp, i32, i32, vp]

@@ -953,10 +953,157 @@ def imencode(image, quality: int = 95, subsampling: str = "4:2:0", device: str =
     return JpegEncodeJob([image], quality, subsampling, device, "imencode").launch().collect()[0]
 
 
-def imwrite(path: str, image, quality: int = 95, subsampling: str = "4:2:0", device: str = "cuda:0") -> bool:
-    """``cv2.imwrite(path, image)`` of the reference's loop (pipeline2.py:397-400) for an RGB page and a ``.jpg`` path: ``imencode`` into
-    the file.  True when the file was written, False when it could not be (cv2's convention); ValueError as ``imencode``."""
-    data = imencode(image, quality, subsampling, device)
+PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}      # name -> filter mode (OCRVI_PNG_FILTER_*)
+PNG_ENC_REGIONS = ("filters", "stream", "hist", "lens", "cl_tokens", "records", "bit_offsets", "crc_partials", "info")
+
+
+def png_encode_sizes(height: int, width: int, components: int) -> dict:
+    """``ocrvi_png_encode_sizes`` (host only): ``stream_bytes``, ``blocks``, ``workspace_bytes``, ``out_capacity`` and the workspace
+    ``offsets`` of a page."""
+    stream, blocks, wsb, cap = ctypes.c_uint64(), ctypes.c_int64(), ctypes.c_uint64(), ctypes.c_uint64()
+    offs = np.zeros(9, np.uint64)
+    _lib.check(_lib.load().ocrvi_png_encode_sizes(int(width), int(height), int(components), ctypes.byref(stream), ctypes.byref(blocks),
+                                                  ctypes.byref(wsb), ctypes.byref(cap), offs.ctypes.data))
+    return {"stream_bytes": stream.value, "blocks": blocks.value, "workspace_bytes": wsb.value, "out_capacity": cap.value,
+            "offsets": [int(v) for v in offs]}
+
+
+class PngEncodeJob:
+    """The pages of one ``ocrvi_png_encode_pages`` call, shaped like ``JpegEncodeJob``: validated and laid out by the constructor
+    (ValueError before anything touches the device), uploaded and enqueued by ``launch`` (one page table, one set of launches, no
+    synchronisation), read back by ``collect`` (the lengths, then only the files' bytes).  ``stage(i)`` reads page i's workspace regions
+    for the tests.  ``imencode_png_pages`` is ``PngEncodeJob(...).launch().collect()``."""
+
+    def __init__(self, images, filters: str = "adaptive", device="cuda:0", what: str = "imencode_png"):
+        if filters not in PNG_FILTERS:
+            raise ValueError(f"{what}: filters {filters!r}: expected one of {sorted(PNG_FILTERS)}")
+        self.images = list(images)
+        self.filters = filters
+        self.dev = torch.device(device)
+        self.geom = []                          # (h, w, components)
+        for i, im in enumerate(self.images):
+            if not isinstance(im, (np.ndarray, torch.Tensor)):
+                raise ValueError(f"{what}: page {i}: expected a numpy array or a tensor, got {type(im).__name__}")
+            if im.dtype not in (np.uint8, torch.uint8):
+                raise ValueError(f"{what}: page {i}: dtype {im.dtype} (uint8 expected)")
+            shape = tuple(im.shape)
+            if not (len(shape) == 2 or (len(shape) == 3 and shape[2] == 3)):
+                raise ValueError(f"{what}: page {i}: shape {shape} (H x W x 3 RGB or H x W grey expected)")
+            if not (1 <= shape[0] <= 65500 and 1 <= shape[1] <= 65500):
+                raise ValueError(f"{what}: page {i}: sides {shape[0]} x {shape[1]} outside 1..65500")
+            self.geom.append((shape[0], shape[1], 1 if len(shape) == 2 else 3))
+        lib = _lib.load()
+        self.w_off, self.o_off, self.caps, self.offsets = [0], [0], [], []
+        for i, (h, w, nc) in enumerate(self.geom):
+            wsb, cap = ctypes.c_uint64(), ctypes.c_uint64()
+            offs = np.zeros(9, np.uint64)
+            rc = lib.ocrvi_png_encode_sizes(w, h, nc, None, None, ctypes.byref(wsb), ctypes.byref(cap), offs.ctypes.data)
+            if rc == -1:
+                raise ValueError(f"{what}: page {i}: {_lib.last_error()}")
+            _lib.check(rc)
+            self.caps.append(_align(cap.value))
+            self.offsets.append([int(v) for v in offs] + [wsb.value])
+            self.w_off.append(self.w_off[-1] + wsb.value)
+            self.o_off.append(self.o_off[-1] + self.caps[-1])
+        self.lengths = self.out = None
+
+    def launch(self) -> "PngEncodeJob":
+        n = len(self.images)
+        if n == 0:
+            return self
+        dev, lib = self.dev, _lib.load()
+        with torch.cuda.device(dev):
+            # host pages travel in one pinned buffer and one copy; device pages are read where they lie
+            host = [i for i, im in enumerate(self.images) if isinstance(im, np.ndarray) or not im.is_cuda]
+            h_off = [0]
+            for i in host:
+                h, w, nc = self.geom[i]
+                h_off.append(h_off[-1] + _align(h * w * nc))
+            src = [None] * n
+            if host:
+                stage = torch.empty(h_off[-1], dtype=torch.uint8).pin_memory()
+                for k, i in enumerate(host):
+                    im = self.images[i]
+                    flat = torch.from_numpy(np.ascontiguousarray(im)) if isinstance(im, np.ndarray) else im.contiguous()
+                    stage[h_off[k]:h_off[k] + flat.numel()].copy_(flat.reshape(-1))
+                d_stage = stage.to(dev, non_blocking=True)
+                for k, i in enumerate(host):
+                    src[i] = d_stage[h_off[k]:]
+            for i, im in enumerate(self.images):
+                if src[i] is None:
+                    src[i] = im.to(dev).contiguous()
+            base = src[0].data_ptr()
+            table = np.zeros((n, _lib.PNG_ENC_ENTRY), np.int64)
+            for i, (h, w, nc) in enumerate(self.geom):
+                _lib.check(lib.ocrvi_png_encode_table_entry(w, h, nc, PNG_FILTERS[self.filters], src[i].data_ptr() - base, w * nc, self.o_off[i],
+                                                            self.caps[i], self.w_off[i], table[i].ctypes.data))
+            self._src = src                     # kept alive until collect
+            d_tab = torch.from_numpy(table).pin_memory().to(dev, non_blocking=True)
+            self._ws = torch.empty(self.w_off[-1], dtype=torch.uint8, device=dev)
+            self.out = torch.empty(self.o_off[-1], dtype=torch.uint8, device=dev)
+            self.lengths = torch.empty(n, dtype=torch.int64, device=dev)
+            self._tab, self._base = d_tab, base
+            self.enqueue()
+        return self
+
+    def enqueue(self) -> None:
+        """The six launches alone, on the current stream (what tools/png_encode_bench.py times as "kernels")."""
+        _lib.check(_lib.load().ocrvi_png_encode_pages(_dev_index(self.dev), self._base, self._tab.data_ptr(), len(self.images), self.out.data_ptr(),
+                                                      self.lengths.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
+                                                      torch.cuda.current_stream(self.dev).cuda_stream))
+
+    def stage(self, i: int) -> dict:
+        """Page i's workspace regions as uint8 arrays on the host, by the names of ``PNG_ENC_REGIONS`` (include/ocrvi.h states what each
+        holds); for the tests."""
+        o = self.offsets[i]
+        ws = self._ws[self.w_off[i]:self.w_off[i] + o[9]].cpu().numpy()
+        return {name: ws[o[k]:o[k + 1]] for k, name in enumerate(PNG_ENC_REGIONS)}
+
+    def collect(self) -> List[bytes]:
+        """Waits for the lengths, then copies the files' bytes alone to the host."""
+        n = len(self.images)
+        if n == 0:
+            return []
+        lens = [int(v) for v in self.lengths.cpu()]
+        for i, ln in enumerate(lens):
+            if not 0 < ln <= self.caps[i]:
+                raise RuntimeError(f"png encode: page {i} was skipped by the device (length {ln})")
+        packed = torch.cat([self.out[self.o_off[i]:self.o_off[i] + lens[i]] for i in range(n)]) if n > 1 else self.out[:lens[0]]
+        host = packed.cpu().numpy()
+        ends = np.cumsum([0] + lens)
+        return [host[ends[i]:ends[i + 1]].tobytes() for i in range(n)]
+
+
+def imencode_png_pages(images, filters: str = "adaptive", device: str = "cuda:0") -> List[bytes]:
+    """``imencode_png`` for a list of pages of any sizes, grey and colour mixed: one upload of a page table and one set of launches
+    (``ocrvi_png_encode_pages``) serve the whole list; only the files' bytes come back."""
+    return PngEncodeJob(images, filters, device, "imencode_png_pages").launch().collect()
+
+
+def imencode_png(image, filters: str = "adaptive", device: str = "cuda:0") -> bytes:
+    """``cv2.imencode(".png", image)`` for an RGB page: the bytes of a PNG file (bit depth 8, colour type 2, or 0 for a grey page, no
+    interlace, the chunks IHDR, one IDAT, IEND).  ``image`` is uint8 [h, w, 3] RGB or uint8 [h, w] grey, a numpy array or a tensor on the
+    host or the device.  ``filters``: "adaptive" (libpng's heuristic per row) or one of "none", "sub", "up", "average", "paeth" for every
+    row.  Filtering, deflate (distance-1 matches, the cheapest of stored, fixed and dynamic codes per 16 KiB block), both checksums and the
+    file's assembly run on the device; the arithmetic is stated in include/ocrvi.h.  Lossless: ``imdecode`` (and zlib, PIL) read the pixels
+    back exactly.  ValueError for other dtypes, shapes or filters, sides outside 1..65500, or a page whose IDAT could exceed 2^31 - 1 bytes."""
+    return PngEncodeJob([image], filters, device, "imencode_png").launch().collect()[0]
+
+
+IMWRITE_FORMATS = (None, "png")
+
+
+def _check_format(format, what: str) -> None:
+    if format not in IMWRITE_FORMATS:
+        raise ValueError(f"{what}: format {format!r}: expected None (JPEG) or 'png'")
+
+
+def imwrite(path: str, image, quality: int = 95, subsampling: str = "4:2:0", device: str = "cuda:0", format=None, filters: str = "adaptive") -> bool:
+    """``cv2.imwrite(path, image)`` of the reference's loop (pipeline2.py:397-400) for an RGB page: ``imencode`` into the file -- JPEG
+    whatever the suffix of ``path`` says -- or, with ``format="png"``, ``imencode_png`` (``quality`` and ``subsampling`` are then ignored).
+    True when the file was written, False when it could not be (cv2's convention); ValueError as ``imencode`` / ``imencode_png``."""
+    _check_format(format, "imwrite")
+    data = imencode_png(image, filters, device) if format == "png" else imencode(image, quality, subsampling, device)
     try:
         with open(path, "wb") as f:
             f.write(data)
@@ -1107,10 +1254,11 @@ def draw_boxes_with_text(image, boxes, texts=None, color=(0, 255, 0), label_colo
     return draw_boxes_pages([image], [boxes], None if texts is None else [texts], color, label_color, thickness, device)[0]
 
 
-def save_result(path: str, image, boxes, texts=None, quality: int = 95, device: str = "cuda:0") -> bool:
-    """The reference's ``--save_result`` (pipeline2.py:358-360 + :397-400): ``draw_boxes_with_text`` then ``imwrite``; only the JPEG bytes
-    leave the device.  Returns what ``imwrite`` returns."""
-    return imwrite(path, draw_boxes_with_text(image, boxes, texts, device=device), quality, device=device)
+def save_result(path: str, image, boxes, texts=None, quality: int = 95, device: str = "cuda:0", format=None) -> bool:
+    """The reference's ``--save_result`` (pipeline2.py:358-360 + :397-400): ``draw_boxes_with_text`` then ``imwrite``; only the file's
+    bytes leave the device -- JPEG, or with ``format="png"`` a PNG, which keeps the thin outlines exact.  Returns what ``imwrite`` returns."""
+    _check_format(format, "save_result")
+    return imwrite(path, draw_boxes_with_text(image, boxes, texts, device=device), quality, device=device, format=format)
 
 
 def detect_and_recognize(original_image, det_model, rec_model, post_processor: DBPostProcessor, device: str = "cuda:0", det_size: int = 640,
