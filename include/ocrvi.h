@@ -180,8 +180,8 @@ int ocrvi_crop_resize_normalize_pages(int device, const int64_t* pages, int n_pa
 
 /* ------------------------------------------------------------------------------------------------
  * Four-point page rectification: the geometric half of the reference's stage 1, `--preprocess` (src/pipeline/pipeline2.py:291-302 ->
- * preprocess_image, src/preprocess/scanner.py:168-196 -> four_point_transform, scanner.py:29-53).  Finding the document's corners (the
- * rembg network, scanner.py:78-132) is the caller's business; enhance_document (scanner.py:55-76) is below (the pipeline passes
+ * preprocess_image, src/preprocess/scanner.py:168-196 -> four_point_transform, scanner.py:29-53).  Finding the document's corners (scanner.py:78-132)
+ * is "Document finder" below: the rembg network stays out, its contour half and a mask of the library's own are built; enhance_document (scanner.py:55-76) is below (the pipeline passes
  * enhance=False).
  * ------------------------------------------------------------------------------------------------ */
 /* Host only, needs no GPU.  Replaces order_points (scanner.py:13-27), the output size (scanner.py:36-42), the destination corners
@@ -1071,6 +1071,64 @@ int ocrvi_test_db_maps(int device, const float* bin_logits, const float* thresh_
  * C classes into log_probs [T][B][C] and its per-step argmax into argmax_ids [B][T] (first index wins ties; 0 for a row whose log-probs
  * are NaN, as ocrvi_ctc_greedy gives).  Either output may be NULL.  C <= 1024, ld >= C. */
 int ocrvi_test_ctc_logsoftmax(int device, const float* logits, int ld, int B, int T, int C, float* log_probs, int32_t* argmax_ids);
+
+/* ------------------------------------------------------------------------------------------------
+ * Document finder: the corners that four-point rectification takes, found from the page (find_document_contour_dl,
+ * src/preprocess/scanner.py:78-132).  The reference gets its mask from the rembg U-2-Net, whose weights are a download and stay out;
+ * what is built is (A) its mask-to-corners half, scanner.py:104-132, for any mask the caller has (rembg's alpha included), and (B) a mask of
+ * the library's own, computed on the device from the page's luminance.  (B) separates a document from its background by brightness only:
+ * a white receipt on a white table gives the frame, a rectangle or nothing.  cv2 is absent from the build container: parity with cv2
+ * (findContours' order, boxPoints' rounding) is UNPINNED; tests/docfind_ref.py restates both halves and must agree to the last bit.
+ * ------------------------------------------------------------------------------------------------ */
+/* (A) Host only, needs no GPU.  mask: uint8 [h] rows of w pixels, `stride` bytes apart (sides 1 .. 16384); quad int32 [4][2] (x, y) in mask
+ * coordinates; *found = 0 none (quad zeroed), 1 a four-point polygon, 2 the rectangle fallback.
+ *   foreground  mask != 0, as cv2.findContours sees it
+ *   contours    RETR_EXTERNAL, CHAIN_APPROX_SIMPLE: the outer borders (Suzuki-Abe border following, as ocrvi_db_postprocess) of the
+ *               8-connected components that no other component encloses; hole borders and components inside a hole are dropped.  Their
+ *               order is that of the RETR_LIST scan, last found first, restricted to these.
+ *   candidates  sorted by contourArea (shoelace) in descending order, stable; the first five
+ *   polygon     the first candidate whose approxPolyDP(cnt, 0.02 * arcLength(cnt, True), True) has exactly four points, in its order
+ *   fallback    otherwise the minimum-area rectangle of the largest contour as ocrvi_min_area_quads defines it (a degenerate hull gives the
+ *               bounding-box corners), each coordinate truncated toward zero (np.int32(cv2.boxPoints(...))) */
+int ocrvi_document_contour(const uint8_t* mask, int h, int w, int64_t stride, int32_t* quad /*[4][2]*/, int32_t* found);
+/* The same on the bit mask (B) produces: bit x & 31 of word y * ((w + 31) / 32) + (x >> 5). */
+int ocrvi_document_contour_bits(const uint32_t* bits, int h, int w, int32_t* quad /*[4][2]*/, int32_t* found);
+
+/* (B) The library's own mask.  Integer arithmetic except where stated; work_h (8 .. 512) is the working image's height, 500 in the reference.
+ *   size      ratio = H / (double)work_h;  ww = int(W / ratio) in IEEE double (scanner.py:85-86);  8 <= ww <= 8192, page sides <= 16384
+ *   grey      working pixel (i, j) covers source rows [i H / work_h, max(that + 1, (i + 1) H / work_h)) (floor divisions) and columns
+ *             likewise with W and ww; luma = (77 R + 150 G + 29 B + 128) >> 8 per source pixel; G = (sum + n / 2) / n over the box's n pixels
+ *   smooth    [1 4 6 4 1] along x and along y, replicate border; S = (sum + 128) >> 8
+ *   histogram 256 bins of S
+ *   Otsu      N = sum h, mT = sum v h[v]; for t = 0 .. 254: w0 = sum_{v <= t} h[v], m0 = sum_{v <= t} v h[v], w1 = N - w0; t is skipped when
+ *             w0 = 0 or w1 = 0; d = mT w0 - m0 N exactly (|d| < 2^53); score = (double(d) * double(d)) / (double(w0) * double(w1)) in IEEE
+ *             double, in this order, no fused multiply-add; the smallest t of maximal score.  A single non-empty bin: no threshold (t = -1),
+ *             the mask is all zero.
+ *   polarity  B = S > t.  OCRVI_DOC_AUTO: when more than half of the ring's pixels (the outermost rows and columns, each once) are set,
+ *             B is inverted -- the frame is background; a tie keeps B.  OCRVI_DOC_BRIGHT keeps B, OCRVI_DOC_DARK inverts it.
+ *   opening   5 x 5 square erosion, then 5 x 5 dilation; pixels outside the image are background in both
+ *   output    one bit per working pixel, bit x & 31 of word y * ((ww + 31) / 32) + (x >> 5); padding bits are zero
+ * All entries below are enqueue-only on `stream` (no allocation, no synchronisation); every pointer is DEVICE memory unless stated. */
+#define OCRVI_DOC_AUTO 0
+#define OCRVI_DOC_BRIGHT 1
+#define OCRVI_DOC_DARK 2
+/* Host only: *ww and *ratio of an h x w page by the size rule; OCRVI_EINVAL outside the bounds above. */
+int ocrvi_doc_working_size(int h, int w, int work_h, int32_t* ww, double* ratio);
+/* Host only: the workspace of ocrvi_doc_mask_pages for n pages (1 .. 65535) whose working widths are at most ww_cap, and the uint32 words
+ * of one page's slot in `masks`, work_h * ((ww_cap + 31) / 32). */
+int ocrvi_doc_mask_sizes(int n, int work_h, int ww_cap, size_t* workspace_bytes, size_t* mask_words);
+/* The whole of (B) for n pages of their own sizes: `pages` is a page table (OCRVI_PAGE_ENTRY), read when the kernels run.  Page i's mask
+ * starts at masks + i * mask_words and is laid out by ITS OWN ww.  An invalid entry, a side above 16384 or a working width outside
+ * [8, ww_cap] leaves the page's slot all zero and touches nothing else.  workspace: 16-byte aligned. */
+int ocrvi_doc_mask_pages(int device, const int64_t* pages, int n, int work_h, int ww_cap, int polarity, uint32_t* masks, void* workspace,
+                         size_t workspace_bytes, void* stream);
+/* The stages one by one.  src uint8 HWC [h,w,3] -> dst uint8 [work_h][ww] (grey); uint8 [work_h][ww] -> the same (smooth, dst != src); ->
+ * hist int32 [256] (zeroed by the call); smooth + hist -> thr int32 [4] = (t, inverted 0 / 1, 0, 0); smooth + thr -> bits. */
+int ocrvi_doc_grey_u8(int device, const uint8_t* src, int h, int w, int work_h, uint8_t* dst, void* stream);
+int ocrvi_doc_smooth_u8(int device, const uint8_t* src, int work_h, int ww, uint8_t* dst, void* stream);
+int ocrvi_doc_histogram(int device, const uint8_t* src, int work_h, int ww, int32_t* hist, void* stream);
+int ocrvi_doc_otsu(int device, const uint8_t* smooth, const int32_t* hist, int work_h, int ww, int polarity, int32_t* thr, void* stream);
+int ocrvi_doc_mask_bits(int device, const uint8_t* smooth, int work_h, int ww, const int32_t* thr, uint32_t* bits, void* stream);
 
 /* Per-launch HIP-event profiler (process-global, off by default).  While enabled every MFMA / bandwidth kernel launch
  * of the graphs above is bracketed by two events recorded on its launch stream.  ocrvi_prof_report synchronises those

@@ -3,7 +3,8 @@
 Importing the package is cheap and CPU-safe; ``DBNetPP`` / ``SVTRv2`` / ``Engine`` (batched OCR over pages of mixed sizes) load ``lib/libocrvi.so`` on first use and
 raise if it is missing (there is no CPU fallback).  ``DBLoss`` / ``SVTRv2Loss`` / ``compute_metrics`` / ``compute_cer`` / ``compute_acc`` /
 ``validate_detection`` / ``validate_recognition`` (``val.py``) mirror the reference's validation loops on the device; ``DetectionDataset``
-(``data.py``) builds the detection batches they consume from polygon annotations."""
+(``data.py``) builds the detection batches they consume from polygon annotations.  ``find_document_contour`` / ``document_mask`` /
+``find_document_quad`` / ``find_document_quads`` (``pipeline.py``) find the document's corners for the rectification stage."""
 from .vocab import VOCAB, Tokenizer  # noqa: F401
 
 
@@ -23,7 +24,11 @@ def __getattr__(name):
     if name in _VAL_NAMES:      # validation: the reference's loss values, pixel metrics, CER and accuracy (val.py)
         from . import val
         return getattr(val, name)
+    if name in _DOCFIND_NAMES:  # the document finder: mask -> corners on the host, the library's own mask on the device (pipeline.py)
+        from . import pipeline
+        return getattr(pipeline, name)
     raise AttributeError(name)
 
 
 _VAL_NAMES = ("DBLoss", "compute_metrics", "SVTRv2Loss", "compute_cer", "compute_acc", "validate_detection", "validate_recognition")
+_DOCFIND_NAMES = ("find_document_contour", "document_mask", "find_document_quad", "find_document_quads")

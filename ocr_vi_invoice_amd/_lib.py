@@ -47,6 +47,8 @@ EXPORTS = [
     "ocrvi_test_conv_raw", "ocrvi_test_gconv_plan",
     "ocrvi_png_info", "ocrvi_png_parse", "ocrvi_png_table_entry", "ocrvi_png_plan", "ocrvi_png_decode_pages",
     "ocrvi_png_encode_sizes", "ocrvi_png_encode_table_entry", "ocrvi_png_encode_pages", "ocrvi_test_png_code_lengths",
+    "ocrvi_document_contour", "ocrvi_document_contour_bits", "ocrvi_doc_working_size", "ocrvi_doc_mask_sizes", "ocrvi_doc_mask_pages",
+    "ocrvi_doc_grey_u8", "ocrvi_doc_smooth_u8", "ocrvi_doc_histogram", "ocrvi_doc_otsu", "ocrvi_doc_mask_bits",
 ]
 PAGE_ENTRY = 4          # int64 fields of one page-table entry: (device address, height, width, 0) -- OCRVI_PAGE_ENTRY
 # ocrvi_det_eval's record: 13 slots of 8 bytes (OCRVI_DET_EVAL_*), the first six int64, the rest float64
@@ -69,6 +71,8 @@ PNG_ENC_BLOCK = 16384           # bytes of one deflate block -- OCRVI_PNG_ENC_BL
 OVERLAY_SEG = 8                 # int32 fields of one overlay segment -- OCRVI_OVERLAY_SEG
 OVERLAY_PRIM = 8                # int32 fields of one overlay primitive -- OCRVI_OVERLAY_PRIM
 OVERLAY_MAX_COORD = 16384       # OCRVI_OVERLAY_MAX_COORD: page sides 1..16384, endpoints within +-16384
+DOC_POLARITIES = {"auto": 0, "bright": 1, "dark": 2}   # OCRVI_DOC_AUTO / _BRIGHT / _DARK
+DOC_WORK_H = 500                # the reference's working height (scanner.py:85)
 
 
 class DetCfg(C.Structure):
@@ -213,6 +217,16 @@ def load() -> C.CDLL:
     lib.ocrvi_png_encode_table_entry.argtypes = [i32, i32, i32, i32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp]
     lib.ocrvi_png_encode_pages.argtypes = [i32, vp, vp, i32, vp, vp, vp, sz, vp]
     lib.ocrvi_test_png_code_lengths.argtypes = [i32, vp, i32, i32, i32, vp, vp]
+    lib.ocrvi_document_contour.argtypes = [vp, i32, i32, C.c_int64, vp, C.POINTER(C.c_int32)]
+    lib.ocrvi_document_contour_bits.argtypes = [vp, i32, i32, vp, C.POINTER(C.c_int32)]
+    lib.ocrvi_doc_working_size.argtypes = [i32, i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_double)]
+    lib.ocrvi_doc_mask_sizes.argtypes = [i32, i32, i32, C.POINTER(sz), C.POINTER(sz)]
+    lib.ocrvi_doc_mask_pages.argtypes = [i32, vp, i32, i32, i32, i32, vp, vp, sz, vp]
+    lib.ocrvi_doc_grey_u8.argtypes = [i32, vp, i32, i32, i32, vp, vp]
+    lib.ocrvi_doc_smooth_u8.argtypes = [i32, vp, i32, i32, vp, vp]
+    lib.ocrvi_doc_histogram.argtypes = [i32, vp, i32, i32, vp, vp]
+    lib.ocrvi_doc_otsu.argtypes = [i32, vp, vp, i32, i32, i32, vp, vp]
+    lib.ocrvi_doc_mask_bits.argtypes = [i32, vp, i32, i32, vp, vp, vp]
     lib.ocrvi_overlay_segments.argtypes = [vp, vp, vp, vp, vp, i32, C.c_uint32, C.c_uint32, i32, vp, C.c_int64, vp, C.c_int64, vp,
                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.ocrvi_overlay_pages.argtypes = [i32, vp, i32, vp, vp, vp, i32, i32, vp]

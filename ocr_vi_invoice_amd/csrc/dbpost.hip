@@ -114,6 +114,61 @@ void find_contours(const float* prob, float thresh, int H, int W, std::vector<st
     }
 }
 
+// cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) on a label image the caller has filled (H x W inside a one-pixel frame of
+// zeros, 1 = foreground): the scan and the border following of find_contours above, every border followed in the same order, but only
+// the outer borders of components that no other component encloses are kept, in discovery order.  Suzuki-Abe's parent of such a border
+// is the frame; here that is decided on the background instead: the pixel west of the border's start is background, and the border is
+// external exactly when that pixel is 4-connected to the frame through background (the complement of 8-connected foreground).
+void find_external_contours(signed char* f, int H, int W, std::vector<std::vector<Pt>>& contours) {
+    const int stride = W + 2;
+    static thread_local std::vector<unsigned char> outside;   // kept across calls, as the label images are
+    static thread_local std::vector<int> todo;
+    outside.assign((size_t)(H + 2) * stride, 0);
+    todo.clear();
+    // background reachable from the frame, before any label is written.  The frame itself is marked first and the image's own border
+    // pixels seed the fill, so every pixel taken off the stack has its four neighbours inside the padded image.
+    memset(outside.data(), 1, stride);
+    memset(outside.data() + (size_t)(H + 1) * stride, 1, stride);
+    auto seed = [&](int q) {
+        if (f[q] == 0 && !outside[q]) { outside[q] = 1; todo.push_back(q); }
+    };
+    for (int y = 1; y <= H; ++y) {
+        outside[(size_t)y * stride] = outside[(size_t)y * stride + W + 1] = 1;
+        seed(y * stride + 1);
+        seed(y * stride + W);
+    }
+    for (int x = 1; x <= W; ++x) {
+        seed(stride + x);
+        seed(H * stride + x);
+    }
+    while (!todo.empty()) {
+        const int p = todo.back();
+        todo.pop_back();
+        seed(p - 1);
+        seed(p + 1);
+        seed(p - stride);
+        seed(p + stride);
+    }
+    const int nbd = 2;
+    std::vector<Pt> border;
+    for (int y = 1; y <= H; ++y) {
+        signed char* row = f + (size_t)y * stride;
+        for (int x = 1; x <= W; ++x) {
+            const int v = row[x];
+            if (v == 0) continue;
+            bool is_hole;
+            if (v == 1 && row[x - 1] == 0) is_hole = false;
+            else if (v >= 1 && row[x + 1] == 0) is_hole = true;
+            else continue;
+            border.clear();
+            follow_border(f, stride, x, y, is_hole, nbd, border);
+            if (is_hole || !outside[(size_t)y * stride + x - 1]) continue;
+            for (Pt& p : border) { p.x -= 1; p.y -= 1; }
+            contours.push_back(border);
+        }
+    }
+}
+
 double arc_length_closed(const std::vector<Pt>& c) {  // cv2.arcLength(closed=True): float32 segment lengths, double sum
     double sum = 0;
     const size_t n = c.size();
@@ -304,6 +359,73 @@ extern "C" int ocrvi_unclip_polygon(const int32_t* pts, int n_pts, double distan
     for (size_t i = 0; i < res.size(); ++i) { out[2 * i] = res[i].x; out[2 * i + 1] = res[i].y; }
     *n_out = (int)res.size();
     return OCRVI_OK;
+}
+
+// ---------------------------------------------------------------- document finder, host half (include/ocrvi.h "Document finder")
+// find_document_contour_dl after its network (src/preprocess/scanner.py:104-132): external contours -> the five largest by area -> the
+// first whose polygon has four points, else the minimum-area rectangle of the largest.  `f` is the filled label image.
+static int document_contour_core(signed char* f, int h, int w, int32_t* quad, int32_t* found) {
+    std::vector<std::vector<Pt>> found_order, contours;
+    find_external_contours(f, h, w, found_order);
+    *found = 0;
+    for (int i = 0; i < 8; ++i) quad[i] = 0;
+    if (found_order.empty()) return OCRVI_OK;
+    std::vector<std::pair<double, int>> by_area;            // cv2 returns the last-found contour first; sorted(..., reverse=True) is stable
+    for (int i = (int)found_order.size() - 1; i >= 0; --i) by_area.push_back({shoelace_abs_half(found_order[i]), i});
+    std::stable_sort(by_area.begin(), by_area.end(), [](const std::pair<double, int>& a, const std::pair<double, int>& b) { return a.first > b.first; });
+    std::vector<Pt> approx;
+    for (size_t k = 0; k < by_area.size() && k < 5; ++k) {
+        const std::vector<Pt>& c = found_order[by_area[k].second];
+        approx_poly_closed(c, 0.02 * arc_length_closed(c), approx);
+        if (approx.size() != 4) continue;
+        for (int i = 0; i < 4; ++i) { quad[2 * i] = approx[i].x; quad[2 * i + 1] = approx[i].y; }
+        *found = 1;
+        return OCRVI_OK;
+    }
+    const std::vector<Pt>& c = found_order[by_area[0].second];
+    std::vector<int32_t> pts(2 * c.size());
+    for (size_t i = 0; i < c.size(); ++i) { pts[2 * i] = c[i].x; pts[2 * i + 1] = c[i].y; }
+    const int32_t offs[2] = {0, (int32_t)c.size()};
+    double q[8];
+    int32_t flag;
+    OCRVI_TRY(ocrvi_min_area_quads(pts.data(), offs, 1, q, &flag));
+    for (int i = 0; i < 8; ++i) quad[i] = (int32_t)q[i];    // np.int32(cv2.boxPoints(...)): truncation toward zero
+    *found = 2;
+    return OCRVI_OK;
+}
+
+static signed char* document_labels(int h, int w) {
+    static thread_local std::vector<signed char> buf;
+    buf.assign((size_t)(h + 2) * (w + 2), 0);
+    return buf.data();
+}
+
+extern "C" int ocrvi_document_contour(const uint8_t* mask, int h, int w, int64_t stride, int32_t* quad, int32_t* found) {
+    using namespace ocrvi;
+    OCRVI_CHECK(mask && quad && found, OCRVI_EINVAL, "document_contour: null pointer");
+    OCRVI_CHECK(h >= 1 && w >= 1 && h <= 16384 && w <= 16384 && stride >= w, OCRVI_EINVAL, "document_contour: a %d x %d mask with a row stride of %lld (sides 1 .. 16384, stride >= w)",
+                h, w, (long long)stride);
+    signed char* f = document_labels(h, w);
+    for (int y = 0; y < h; ++y) {
+        const uint8_t* src = mask + (size_t)y * (size_t)stride;
+        signed char* row = f + (size_t)(y + 1) * (w + 2) + 1;
+        for (int x = 0; x < w; ++x) row[x] = src[x] != 0;
+    }
+    return document_contour_core(f, h, w, quad, found);
+}
+
+extern "C" int ocrvi_document_contour_bits(const uint32_t* bits, int h, int w, int32_t* quad, int32_t* found) {
+    using namespace ocrvi;
+    OCRVI_CHECK(bits && quad && found, OCRVI_EINVAL, "document_contour_bits: null pointer");
+    OCRVI_CHECK(h >= 1 && w >= 1 && h <= 16384 && w <= 16384, OCRVI_EINVAL, "document_contour_bits: a %d x %d mask (sides 1 .. 16384)", h, w);
+    signed char* f = document_labels(h, w);
+    const int wpr = (w + 31) / 32;
+    for (int y = 0; y < h; ++y) {
+        const uint32_t* src = bits + (size_t)y * wpr;
+        signed char* row = f + (size_t)(y + 1) * (w + 2) + 1;
+        for (int x = 0; x < w; ++x) row[x] = (src[x >> 5] >> (x & 31)) & 1;
+    }
+    return document_contour_core(f, h, w, quad, found);
 }
 
 static int db_postprocess_core(const float* prob, const uint32_t* bits, int H, int W, float thresh, float box_thresh, int max_candidates,

@@ -29,9 +29,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .pipeline import (IMAGE_BYTES, DBPostProcessor, _check_crop, db_boxes_pages, enhance_init, enhance_workspace_bytes, four_point_geometry,
-                       is_png, jpeg_info_struct, jpeg_parse_into, jpeg_table_entry, overlay_paint_, overlay_segments, png_info_struct,
-                       png_parse_into, png_table_entry, quad_crops)
+from .pipeline import (IMAGE_BYTES, DBPostProcessor, _check_crop, db_boxes_pages, enhance_init, enhance_workspace_bytes, find_document_quads,
+                       four_point_geometry, imdecode, is_png, jpeg_info_struct, jpeg_parse_into, jpeg_table_entry, overlay_paint_,
+                       overlay_segments, png_info_struct, png_parse_into, png_table_entry, quad_crops)
 
 _ARENA_ALIGN = 256
 _STREAMS: Dict[int, Tuple[torch.cuda.Stream, torch.cuda.Stream]] = {}
@@ -104,6 +104,10 @@ class Engine:
     ``run(pages, quads)``: ``quads[i]`` is ``None`` or the four corners of page i's document; such a page is rectified on the device
     (``ocrvi_warp_perspective_pages`` into its arena slot, ahead of its chunk's detector launch) and everything downstream sees the
     rectified page, as ``detect_and_recognize(page, ..., quad=quads[i])`` does: boxes are in its coordinates.
+    ``run(pages, quads="auto")``: the corners are found first, by ``pipeline.find_document_quads`` (one page table and one launch per stage
+    for all pages, on the current stream), then exactly the path above runs: the result equals ``run(pages, find_document_quads(pages),
+    enhance)``.  Encoded pages are decoded once, up front (``pipeline.imdecode``), and host arrays uploaded once; they go on as device
+    tensors, so ``stats`` counts no ``jpeg`` / ``png`` page in that mode.
     ``run(pages, quads, enhance)``: ``enhance`` is a bool for all pages or one bool per page; such a page goes through
     ``ocrvi_enhance_u8`` (``pipeline.enhance_document``, src/preprocess/scanner.py:55-76) in its arena slot, after its rectification and
     ahead of its chunk's detector launch, eagerly on the detector stream, as ``detect_and_recognize(page, ..., enhance=True)`` does.
@@ -612,6 +616,17 @@ class Engine:
         pages = list(pages)
         self._annotate, self._annotated = bool(self.annotate), [None] * len(pages)
         t_start = time.perf_counter()              # (total_s includes the host entropy decode of JPEG pages and the inflate of PNG pages)
+        if isinstance(quads, str):
+            if quads != "auto":
+                raise ValueError(f"quads: expected None, a list of quads or \"auto\", got {quads!r}")
+            for i, p in enumerate(pages):
+                self._check_page(i, p)
+            enc = [i for i, p in enumerate(pages) if isinstance(p, IMAGE_BYTES)]
+            for i, page in zip(enc, imdecode([pages[i] for i in enc], self.dev) if enc else []):
+                pages[i] = page
+            pages = [p if isinstance(p, torch.Tensor) and p.is_cuda else
+                     torch.as_tensor(np.ascontiguousarray(p) if isinstance(p, np.ndarray) else p).to(self.dev) for p in pages]
+            quads = find_document_quads(pages, device=self.dev)
         infos = {i: (png_info_struct if is_png(p) else jpeg_info_struct)(p, f"page {i}") for i, p in enumerate(pages) if isinstance(p, IMAGE_BYTES)}
         raw_sizes = [self._check_page(i, p, infos.get(i)) for i, p in enumerate(pages)]
         # (every ValueError -- pages, quads, sizes that round to 0 -- is raised here, before any GPU work)

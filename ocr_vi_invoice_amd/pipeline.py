@@ -792,6 +792,148 @@ def imread(path: str, device: str = "cuda:0") -> torch.Tensor:
         return imdecode(f.read(), device)
 
 
+# ---------------------------------------------------------------------------------------------------- document finder
+DOC_KINDS = (None, "polygon", "rectangle")        # ocrvi_document_contour's `found`
+
+
+def find_document_contour(mask, return_kind: bool = False):
+    """scanner.py:104-132, the half of ``find_document_contour_dl`` after its network (``ocrvi_document_contour``, host only, needs no GPU):
+    ``mask`` is any 2-D uint8 / bool segmentation (non-zero = document; rembg's alpha channel is one) -> the reference's ``screen_cnt`` as
+    an int32 [4, 2] array of (x, y) in mask coordinates, or ``None`` when the mask is empty.  External contours, the five largest by area, the
+    first whose ``approxPolyDP(0.02 * arcLength)`` has four points, else the minimum-area rectangle of the largest.  ``return_kind=True``
+    returns (quad, "polygon" / "rectangle" / None).  The definition is in include/ocrvi.h; parity with cv2 is unpinned."""
+    if isinstance(mask, torch.Tensor):
+        mask = mask.detach().cpu().numpy()
+    m = np.asarray(mask)
+    if m.dtype == np.bool_:
+        m = m.view(np.uint8)
+    if m.dtype != np.uint8 or m.ndim != 2 or m.shape[0] < 1 or m.shape[1] < 1:
+        raise ValueError(f"find_document_contour: expected a 2-D uint8 mask, got dtype {m.dtype} shape {m.shape}")
+    if m.strides[1] != 1 or m.strides[0] < m.shape[1]:
+        m = np.ascontiguousarray(m)
+    quad, found = np.zeros((4, 2), np.int32), ctypes.c_int32(0)
+    rc = _lib.load().ocrvi_document_contour(m.ctypes.data, m.shape[0], m.shape[1], m.strides[0], quad.ctypes.data, ctypes.byref(found))
+    if rc == -1:
+        raise ValueError(f"find_document_contour: {_lib.last_error()}")
+    _lib.check(rc)
+    q = quad if found.value else None
+    return (q, DOC_KINDS[found.value]) if return_kind else q
+
+
+def doc_working_size(h: int, w: int, work_h: int = _lib.DOC_WORK_H) -> Tuple[int, float]:
+    """``ocrvi_doc_working_size``: (ww, ratio) of an h x w page at ``work_h`` working rows (scanner.py:85-86); ValueError outside the bounds
+    the header states (8 <= ww <= 8192, sides <= 16384, 8 <= work_h <= 512)."""
+    ww, ratio = ctypes.c_int32(0), ctypes.c_double(0)
+    rc = _lib.load().ocrvi_doc_working_size(int(h), int(w), int(work_h), ctypes.byref(ww), ctypes.byref(ratio))
+    if rc == -1:
+        raise ValueError(f"document finder: {_lib.last_error()}")
+    _lib.check(rc)
+    return ww.value, ratio.value
+
+
+def _doc_polarity(polarity) -> int:
+    try:
+        return _lib.DOC_POLARITIES[polarity]
+    except (KeyError, TypeError):
+        raise ValueError(f"polarity: expected one of {sorted(_lib.DOC_POLARITIES)}, got {polarity!r}") from None
+
+
+def doc_mask_bits(pages: Sequence[torch.Tensor], work_h: int = _lib.DOC_WORK_H, polarity="auto"):
+    """``ocrvi_doc_mask_pages`` on the current stream for device pages (uint8 HxWx3, one device) of any sizes: one page table, one launch
+    per stage.  Returns (bits, sizes): ``bits`` an int32 device tensor [n, work_h * ((ww_cap + 31) // 32)] whose row i holds page i's mask
+    in the layout of ITS OWN ww (bit x & 31 of word y * ((ww + 31) // 32) + (x >> 5)), ``sizes`` a list of (ww, ratio), ``None`` for a page
+    outside the bounds of ``doc_working_size`` (its row is all zero)."""
+    pol = _doc_polarity(polarity)
+    pages = [p.contiguous() for p in pages]
+    sizes = []
+    for p in pages:
+        try:
+            sizes.append(doc_working_size(p.shape[0], p.shape[1], work_h))
+        except ValueError:
+            sizes.append(None)
+    lib, device, n = _lib.load(), pages[0].device, len(pages)
+    ww_cap = max([s[0] for s in sizes if s is not None] + [8])
+    ws_bytes, words = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _lib.check(lib.ocrvi_doc_mask_sizes(n, int(work_h), ww_cap, ctypes.byref(ws_bytes), ctypes.byref(words)))
+    with torch.cuda.device(device):
+        table = torch.tensor([(p.data_ptr(), p.shape[0], p.shape[1], 0) for p in pages], dtype=torch.int64).pin_memory().to(device, non_blocking=True)
+        ws = torch.empty(ws_bytes.value, dtype=torch.uint8, device=device)
+        bits = torch.empty((n, words.value), dtype=torch.int32, device=device)
+        _lib.check(lib.ocrvi_doc_mask_pages(_dev_index(device), table.data_ptr(), n, int(work_h), ww_cap, pol, bits.data_ptr(), ws.data_ptr(),
+                                            ws.numel(), torch.cuda.current_stream(device).cuda_stream))
+    return bits, sizes                            # (table and workspace go back to the allocator of the stream the launches are on)
+
+
+def _check_rgb(image, what: str):
+    if not isinstance(image, (np.ndarray, torch.Tensor)):
+        raise ValueError(f"{what}: expected an RGB uint8 HxWx3 numpy array or tensor, got {type(image).__name__}")
+    if image.dtype != (np.uint8 if isinstance(image, np.ndarray) else torch.uint8) or image.ndim != 3 or image.shape[2] != 3:
+        raise ValueError(f"{what}: expected a uint8 HxWx3 image, got dtype {image.dtype} shape {tuple(image.shape)}")
+
+
+def document_mask(image, work_h: int = _lib.DOC_WORK_H, polarity="auto", device: str = "cuda:0"):
+    """The library's own document mask (include/ocrvi.h, "Document finder", part B): area-average luminance at ``work_h`` rows (500, the
+    reference's working height, scanner.py:85-86) -> binomial smooth -> Otsu -> polarity (``"auto"``: the frame is background; ``"bright"``
+    / ``"dark"``: the document is) -> 5 x 5 opening, all on the device.  Returns (mask uint8 [work_h, ww] of 0 / 255, ratio): a numpy array
+    for a host image, a device tensor for a device tensor.  It tells a document from its background by brightness alone; feed the mask to
+    ``find_document_contour``.  ValueError for a page outside the bounds of ``doc_working_size``."""
+    _check_rgb(image, "document_mask")
+    on_device = isinstance(image, torch.Tensor) and image.is_cuda
+    ww, ratio = doc_working_size(image.shape[0], image.shape[1], work_h)
+    img = image if on_device else torch.as_tensor(np.ascontiguousarray(image) if isinstance(image, np.ndarray) else image).to(device)
+    bits, _ = doc_mask_bits([img], work_h, polarity)
+    wpr = (ww + 31) // 32
+    b = bits[0, :work_h * wpr].view(work_h, wpr, 1) >> torch.arange(32, dtype=torch.int32, device=bits.device)
+    mask = ((b & 1).to(torch.uint8) * 255).view(work_h, wpr * 32)[:, :ww].contiguous()
+    if on_device:
+        return mask, ratio
+    mask = mask.cpu()
+    return (mask.numpy() if isinstance(image, np.ndarray) else mask), ratio
+
+
+def find_document_quads(images, polarity="auto", device: str = "cuda:0"):
+    """``find_document_contour_dl`` (scanner.py:78-132) with the library's own mask in the network's place, for a list of pages of any
+    sizes: host arrays, device tensors, JPEG bytes or PNG bytes.  Encoded pages are decoded in one batch per format, host pages are
+    uploaded, all pages go through one page table and one launch per stage (``ocrvi_doc_mask_pages``); only the bit masks, about 23 KB
+    a page, come back, and the host traces them (``ocrvi_document_contour_bits``).  Returns per page the corners as float64 [4, 2] in the
+    page's coordinates -- the contour scaled by the ratio, ``screen_cnt.reshape(4, 2) * ratio`` (scanner.py:187), what ``preprocess_image``
+    and ``Engine.run`` take as ``quad`` -- or ``None`` when nothing is found (an empty or constant page, a page outside the bounds of
+    ``doc_working_size``).  The quad is returned as found: a degenerate one is refused by ``four_point_geometry`` as before."""
+    images = list(images)
+    if not images:
+        return []
+    dev = torch.device(device)
+    enc = [i for i, p in enumerate(images) if isinstance(p, IMAGE_BYTES)]
+    pages = list(images)
+    for i, page in zip(enc, imdecode([images[i] for i in enc], dev) if enc else []):
+        pages[i] = page
+    for i, p in enumerate(pages):
+        _check_rgb(p, f"find_document_quads: page {i}")
+        if not (isinstance(p, torch.Tensor) and p.is_cuda):
+            pages[i] = torch.as_tensor(np.ascontiguousarray(p) if isinstance(p, np.ndarray) else p).to(dev)
+    work_h = _lib.DOC_WORK_H
+    bits, sizes = doc_mask_bits(pages, work_h, polarity)
+    host = bits.cpu().numpy()
+    lib = _lib.load()
+
+    def finish(i):                                # the host half of page i: ctypes drops the interpreter lock, pages trace in parallel
+        if sizes[i] is None:
+            return None
+        quad, found = np.zeros((4, 2), np.int32), ctypes.c_int32(0)
+        _lib.check(lib.ocrvi_document_contour_bits(host[i].ctypes.data, work_h, sizes[i][0], quad.ctypes.data, ctypes.byref(found)))
+        return quad.astype(np.float64) * sizes[i][1] if found.value else None
+
+    if len(pages) > 1:
+        return list(jpeg_pool().map(finish, range(len(pages))))
+    return [finish(0)]
+
+
+def find_document_quad(image, polarity="auto", device: str = "cuda:0"):
+    """``find_document_quads`` for one page: float64 [4, 2] or ``None``.  ``preprocess_image(image, find_document_quad(image))`` is the
+    reference's ``preprocess_image`` (scanner.py:168-196) with the library's mask in the network's place."""
+    return find_document_quads([image], polarity, device)[0]
+
+
 JPEG_SUBSAMPLINGS = {"4:2:0": 2, "4:4:4": 1}      # name -> luma sampling factor
 
 
