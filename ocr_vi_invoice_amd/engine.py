@@ -29,9 +29,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .pipeline import (IMAGE_BYTES, DBPostProcessor, _check_crop, db_boxes_pages, enhance_init, enhance_workspace_bytes, find_document_quads,
-                       four_point_geometry, imdecode, is_png, jpeg_info_struct, jpeg_parse_into, jpeg_table_entry, overlay_paint_,
-                       overlay_segments, png_info_struct, png_parse_into, png_table_entry, quad_crops)
+from .codec import IMAGE_BYTES, JPEG, PNG, format_of_info, imdecode, info_struct, parse_into, stream_buffer, table_entry
+from .pipeline import (DBPostProcessor, _check_crop, db_boxes_pages, enhance_init, enhance_workspace_bytes, find_document_quads,
+                       four_point_geometry, overlay_paint_, overlay_segments, quad_crops)
 
 _ARENA_ALIGN = 256
 _STREAMS: Dict[int, Tuple[torch.cuda.Stream, torch.cuda.Stream]] = {}
@@ -106,7 +106,7 @@ class Engine:
     rectified page, as ``detect_and_recognize(page, ..., quad=quads[i])`` does: boxes are in its coordinates.
     ``run(pages, quads="auto")``: the corners are found first, by ``pipeline.find_document_quads`` (one page table and one launch per stage
     for all pages, on the current stream), then exactly the path above runs: the result equals ``run(pages, find_document_quads(pages),
-    enhance)``.  Encoded pages are decoded once, up front (``pipeline.imdecode``), and host arrays uploaded once; they go on as device
+    enhance)``.  Encoded pages are decoded once, up front (``codec.imdecode``), and host arrays uploaded once; they go on as device
     tensors, so ``stats`` counts no ``jpeg`` / ``png`` page in that mode.
     ``run(pages, quads, enhance)``: ``enhance`` is a bool for all pages or one bool per page; such a page goes through
     ``ocrvi_enhance_u8`` (``pipeline.enhance_document``, src/preprocess/scanner.py:55-76) in its arena slot, after its rectification and
@@ -205,16 +205,14 @@ class Engine:
         #      refuses to work in place), grown per run
         self.d_enh_ws = torch.empty(0, dtype=torch.uint8, **d)
         self.d_enh_out = torch.empty(0, dtype=torch.uint8, **d)
-        # ---- JPEG pages: per detector chunk, the coefficient streams (device region + two pinned slots, grown on demand), the component
-        #      planes of the chunk's files and the decode table
-        self.d_jrec = torch.empty(0, dtype=torch.uint8, **d)
-        self.h_jrec = [torch.empty(0, dtype=torch.uint8), torch.empty(0, dtype=torch.uint8)]
-        self.d_jws = torch.empty(0, dtype=torch.uint8, **d)
-        self.d_jtab = torch.zeros((self.det_chunk, _lib.JPEG_ENTRY), dtype=torch.int64, **d)
-        self.h_jtab = [torch.zeros((self.det_chunk, _lib.JPEG_ENTRY), dtype=torch.int64).pin_memory() for _ in range(2)]
-        # ---- PNG pages share the stream region, its pinned slots and the workspace (there: the lines between bands); their table
-        self.d_ptab = torch.zeros((self.det_chunk, _lib.PNG_ENTRY), dtype=torch.int64, **d)
-        self.h_ptab = [torch.zeros((self.det_chunk, _lib.PNG_ENTRY), dtype=torch.int64).pin_memory() for _ in range(2)]
+        # ---- encoded pages: per detector chunk, the streams of its files (device region + two pinned slots, grown on demand) and the
+        #      decoders' workspace (JPEG: the component planes of the chunk's files; PNG: the lines between bands), shared by the two
+        #      formats; one decode table per format, their entries differ in width
+        self.d_streams = torch.empty(0, dtype=torch.uint8, **d)
+        self.h_streams = [torch.empty(0, dtype=torch.uint8), torch.empty(0, dtype=torch.uint8)]
+        self.d_dec_ws = torch.empty(0, dtype=torch.uint8, **d)
+        self.d_dec_tab = {f: torch.zeros((self.det_chunk, f.entry_width), dtype=torch.int64, **d) for f in (JPEG, PNG)}
+        self.h_dec_tab = {f: [torch.zeros((self.det_chunk, f.entry_width), dtype=torch.int64).pin_memory() for _ in range(2)] for f in (JPEG, PNG)}
         # one stream pair per device for every engine of the process: each new HIP stream takes the next hardware queue round-robin
         if self.devi not in _STREAMS:
             _STREAMS[self.devi] = (torch.cuda.Stream(self.dev), torch.cuda.Stream(self.dev))
@@ -289,7 +287,7 @@ class Engine:
     def _check_page(i, p, info=None):
         if isinstance(p, IMAGE_BYTES):            # a JPEG file: its size after orientation; a PNG file: its size (ValueError naming the page)
             if info is None:
-                info = (png_info_struct if is_png(p) else jpeg_info_struct)(p, f"page {i}")
+                info = info_struct(p, f"page {i}")
             return int(info.out_height), int(info.out_width)
         if isinstance(p, np.ndarray):
             ok = p.dtype == np.uint8
@@ -301,39 +299,36 @@ class Engine:
             raise ValueError(f"page {i}: expected an RGB uint8 HxWx3 array, got dtype {p.dtype} shape {tuple(p.shape)}")
         return int(p.shape[0]), int(p.shape[1])
 
-    def _parse_jpegs(self, pages, infos):
+    def _parse_files(self, pages, infos):
         """Entropy-decodes every JPEG page and inflates every PNG page of the call on the engine's host pool (``post_threads`` threads,
-        the budget of the box stage, which never runs at the same time): {page index: (info, uint32 stream, bytes used)}; the info is a
+        the budget of the box stage, which never runs at the same time): {page index: (info, uint8 stream, bytes used)}; the info is a
         ``JpegInfo`` or a ``PngInfo``.  ValueError naming the first bad page; nothing has touched the device by then.  ``jpeg_parse_s``
         and ``png_parse_s`` are the wall time from the start of this stage until the last file of that format was done (the two
         overlap when a call holds both).
         A stream waits in pageable memory until its chunk is staged and is dropped there.  It cannot be decoded into the pinned slot it
         is uploaded from: the two slots belong to the chunks in flight, while a corrupt scan must be found, for every file of the call,
         before the first chunk is launched; pinned room for a whole call would be hundreds of megabytes for a folder of pages.  The
-        buffer is sized by the bound ``ocrvi_jpeg_info`` gives; only the pages the stream's words touch ever become resident."""
+        buffer is sized by the bound ``ocrvi_jpeg_info`` / ``ocrvi_png_info`` gives (``codec.stream_buffer``); only the pages the stream
+        touches ever become resident."""
         if not infos:
             return {}
         t0 = time.perf_counter()
 
         def one(i):
-            if isinstance(infos[i], _lib.PngInfo):
-                buf = np.empty((infos[i].stream_bytes + 3) // 4, np.uint32)
-                used = png_parse_into(pages[i], buf.ctypes.data, buf.nbytes, f"page {i}")
-            else:
-                buf = np.empty(infos[i].stream_bytes // 4, np.uint32)
-                used = jpeg_parse_into(pages[i], buf.ctypes.data, buf.nbytes, f"page {i}")
+            buf = stream_buffer(infos[i])
+            used = parse_into(infos[i], pages[i], buf.ctypes.data, buf.nbytes, f"page {i}")
             return infos[i], buf, used, time.perf_counter()
 
         if self._pool is None:
             import concurrent.futures
-            self._pool = concurrent.futures.ThreadPoolExecutor(self.post_threads, thread_name_prefix="ocrvi-jpeg")
+            self._pool = concurrent.futures.ThreadPoolExecutor(self.post_threads, thread_name_prefix="ocrvi-codec")
         futs = [(i, self._pool.submit(one, i)) for i in sorted(infos)]
         out, err = {}, None
         for i, f in futs:                         # every job is waited for, the first failure in page order is raised
             try:
                 info, buf, used, done = f.result()
                 out[i] = (info, buf, used)
-                key = "png_parse_s" if isinstance(infos[i], _lib.PngInfo) else "jpeg_parse_s"
+                key = f"{format_of_info(info).name}_parse_s"
                 self.stats[key] = max(self.stats[key], done - t0)
             except Exception as e:               # noqa: BLE001
                 err = err or e
@@ -341,40 +336,34 @@ class Engine:
             raise err
         return out
 
-    def _decode_jpegs(self, wave, lo, hi, s, targets):
-        """The JPEG and PNG pages of chunk wave[lo:hi] -> ``targets`` [(page index, destination address)], one ``ocrvi_jpeg_decode_pages``
-        and one ``ocrvi_png_decode_pages`` launch (whichever format the chunk holds) on the detector stream: streams and tables through
-        pinned slot ``s``; the two formats share the stream region and the workspace."""
-        jtab, ptab = self.h_jtab[s].numpy(), self.h_ptab[s].numpy()
-        stage = self.h_jrec[s].numpy()
+    def _decode_files(self, s, targets):
+        """The JPEG and PNG pages of a chunk -> ``targets`` [(page index, destination address)], one ``decode_pages`` launch per format
+        the chunk holds (JPEG first) on the detector stream: streams and tables through pinned slot ``s``; the two formats share the
+        stream region and the workspace."""
+        stage = self.h_streams[s].numpy()
         base = self.arena.data_ptr()
-        soff = woff = nj = npng = 0
+        count = {JPEG: 0, PNG: 0}
+        tabs = {fmt: self.h_dec_tab[fmt][s].numpy() for fmt in count}
+        soff = woff = 0
         for i, dst_ptr in targets:
-            info, buf, used = self._jpeg[i]
-            stage[soff:soff + used] = buf.view(np.uint8)[:used]
-            self._jpeg[i] = (info, None, used)     # the host copy has served: only its sizes are still read
-            if isinstance(info, _lib.PngInfo):
-                png_table_entry(info, used, soff, dst_ptr - base, 3 * info.out_width, woff, ptab[npng])
-                npng += 1
-                self.stats["png_stream_bytes"] += used
-            else:
-                jpeg_table_entry(info, used, soff, dst_ptr - base, 3 * info.out_width, woff, jtab[nj])
-                nj += 1
-                self.stats["jpeg_stream_bytes"] += used
+            info, buf, used = self._encoded[i]
+            fmt = format_of_info(info)
+            stage[soff:soff + used] = buf[:used]
+            self._encoded[i] = (info, None, used)  # the host copy has served: only its sizes are still read
+            table_entry(info, used, soff, dst_ptr - base, 3 * info.out_width, woff, tabs[fmt][count[fmt]])
+            count[fmt] += 1
+            self.stats[f"{fmt.name}_stream_bytes"] += used
             soff += (used + _ARENA_ALIGN - 1) // _ARENA_ALIGN * _ARENA_ALIGN
             woff += info.workspace_bytes
-        self.d_jrec[:soff].copy_(self.h_jrec[s][:soff], non_blocking=True)
-        if nj:
-            self.d_jtab[:nj].copy_(self.h_jtab[s][:nj], non_blocking=True)
-            _lib.check(self.lib.ocrvi_jpeg_decode_pages(self.devi, self.d_jrec.data_ptr(), self.d_jtab.data_ptr(), nj, base, self.d_jws.data_ptr(),
-                                                        self.d_jws.numel(), self.s_det.cuda_stream))
-        if npng:
-            self.d_ptab[:npng].copy_(self.h_ptab[s][:npng], non_blocking=True)
-            _lib.check(self.lib.ocrvi_png_decode_pages(self.devi, self.d_jrec.data_ptr(), self.d_ptab.data_ptr(), npng, base,
-                                                       self.d_jws.data_ptr() if self.d_jws.numel() else None, self.d_jws.numel(),
-                                                       self.s_det.cuda_stream))
-        self.stats["jpeg"] += nj
-        self.stats["png"] += npng
+        self.d_streams[:soff].copy_(self.h_streams[s][:soff], non_blocking=True)
+        ws = self.d_dec_ws
+        for fmt, n in count.items():
+            if n:
+                self.d_dec_tab[fmt][:n].copy_(self.h_dec_tab[fmt][s][:n], non_blocking=True)
+                # (a chunk of PNG pages alone may need no workspace: a null pointer then)
+                fmt.decode_pages(self.devi, self.d_streams.data_ptr(), self.d_dec_tab[fmt].data_ptr(), n, base,
+                                 ws.data_ptr() if ws.numel() else None, ws.numel(), self.s_det.cuda_stream)
+            self.stats[fmt.name] += n
 
     def _stage(self, pages, wave, lo, hi, s=0):
         """Pages wave[lo:hi] (consecutive arena slots) -> the arena, on the detector stream.  A page with a quad is warped into its slot
@@ -382,7 +371,7 @@ class Engine:
         pinned slot ``s`` and the raw region (chunk c - 2, the previous user of slot ``s``, has been waited for by now)."""
         PE, dc = _lib.PAGE_ENTRY, self.det_chunk
         tabs, roff, n_warp = None, 0, 0
-        jpegs = []                                 # (page, destination address): the arena slot, or the raw region for a page with a quad
+        encoded = []                              # (page, destination address): the arena slot, or the raw region for a page with a quad
         for slot in range(lo, hi):
             i = wave[slot]
             p, off, nb = pages[i], self._offs[slot], self._nbytes[slot]
@@ -396,9 +385,9 @@ class Engine:
                     src = p if p.is_contiguous() else p.contiguous()
                     self._keep.append(src)         # alive until the wave has drained
                     src_ptr = src.data_ptr()
-                elif i in self._jpeg:
+                elif i in self._encoded:
                     src_ptr = self.d_raw.data_ptr() + roff
-                    jpegs.append((i, src_ptr))
+                    encoded.append((i, src_ptr))
                     roff += (rh * rw * 3 + _ARENA_ALIGN - 1) // _ARENA_ALIGN * _ARENA_ALIGN
                 else:
                     src = p.numpy() if isinstance(p, torch.Tensor) else p
@@ -414,15 +403,15 @@ class Engine:
                 n_warp += 1
             elif isinstance(p, torch.Tensor) and p.is_cuda:
                 dst.copy_(p.contiguous().view(-1), non_blocking=True)
-            elif i in self._jpeg:
-                jpegs.append((i, dst.data_ptr()))
+            elif i in self._encoded:
+                encoded.append((i, dst.data_ptr()))
             else:
                 src = p.numpy() if isinstance(p, torch.Tensor) else p
                 stage = self.h_stage[off:off + nb].numpy()
                 np.copyto(stage.reshape(src.shape), src)
                 dst.copy_(self.h_stage[off:off + nb], non_blocking=True)
-        if jpegs:                                  # ahead of the warp and the enhancement that read these pages
-            self._decode_jpegs(wave, lo, hi, s, jpegs)
+        if encoded:                                # ahead of the warp and the enhancement that read these pages
+            self._decode_files(s, encoded)
         if n_warp:
             self.d_warp.copy_(self.h_warp[s], non_blocking=True)
             base = self.d_warp.data_ptr()
@@ -542,7 +531,7 @@ class Engine:
         if self.arena.numel() < off:               # (the previous wave has drained: nothing reads the old arena any more)
             self.arena = torch.empty(off, dtype=torch.uint8, device=self.dev)
         on_host = [not (isinstance(pages[i], torch.Tensor) and pages[i].is_cuda) for i in wave]
-        if any(h and self._mats[i] is None and i not in self._jpeg for h, i in zip(on_host, wave)) and self.h_stage.numel() < off:
+        if any(h and self._mats[i] is None and i not in self._encoded for h, i in zip(on_host, wave)) and self.h_stage.numel() < off:
             self.h_stage = torch.empty(off, dtype=torch.uint8).pin_memory()
         tab = self.h_table.numpy()
         tab[:] = 0
@@ -568,17 +557,17 @@ class Engine:
         if self.d_raw.numel() < raw:               # (the previous wave has drained)
             self.d_raw = torch.empty(raw, dtype=torch.uint8, device=self.dev)
             self.h_raw = [torch.empty(raw, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        # the JPEG regions: the largest chunk's streams and component planes
-        jrec = jws = 0
+        # the regions of the encoded pages: the largest chunk's streams and decoder workspaces
+        streams = dec_ws = 0
         for lo, hi, _ in chunks:
-            js = [self._jpeg[wave[k]] for k in range(lo, hi) if wave[k] in self._jpeg]
-            jrec = max(jrec, sum((u + _ARENA_ALIGN - 1) // _ARENA_ALIGN * _ARENA_ALIGN for _, _, u in js))
-            jws = max(jws, sum(info.workspace_bytes for info, _, _ in js))
-        if self.d_jrec.numel() < jrec:             # (the previous wave has drained)
-            self.d_jrec = torch.empty(jrec, dtype=torch.uint8, device=self.dev)
-            self.h_jrec = [torch.empty(jrec, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        if self.d_jws.numel() < jws:
-            self.d_jws = torch.empty(jws, dtype=torch.uint8, device=self.dev)
+            files = [self._encoded[wave[k]] for k in range(lo, hi) if wave[k] in self._encoded]
+            streams = max(streams, sum((u + _ARENA_ALIGN - 1) // _ARENA_ALIGN * _ARENA_ALIGN for _, _, u in files))
+            dec_ws = max(dec_ws, sum(info.workspace_bytes for info, _, _ in files))
+        if self.d_streams.numel() < streams:       # (the previous wave has drained)
+            self.d_streams = torch.empty(streams, dtype=torch.uint8, device=self.dev)
+            self.h_streams = [torch.empty(streams, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        if self.d_dec_ws.numel() < dec_ws:
+            self.d_dec_ws = torch.empty(dec_ws, dtype=torch.uint8, device=self.dev)
         pending = collections.deque()
         for c, (lo, hi, shape) in enumerate(chunks):
             if len(pending) == 2:                  # its pinned map slot is the one chunk c reuses
@@ -627,7 +616,7 @@ class Engine:
             pages = [p if isinstance(p, torch.Tensor) and p.is_cuda else
                      torch.as_tensor(np.ascontiguousarray(p) if isinstance(p, np.ndarray) else p).to(self.dev) for p in pages]
             quads = find_document_quads(pages, device=self.dev)
-        infos = {i: (png_info_struct if is_png(p) else jpeg_info_struct)(p, f"page {i}") for i, p in enumerate(pages) if isinstance(p, IMAGE_BYTES)}
+        infos = {i: info_struct(p, f"page {i}") for i, p in enumerate(pages) if isinstance(p, IMAGE_BYTES)}
         raw_sizes = [self._check_page(i, p, infos.get(i)) for i, p in enumerate(pages)]
         # (every ValueError -- pages, quads, sizes that round to 0 -- is raised here, before any GPU work)
         sizes, mats, shapes, scales, buckets = plan_rectified(raw_sizes, quads, self.det_size)
@@ -652,8 +641,9 @@ class Engine:
             self.stats["quad_s"] = 0.0             # host time of ocrvi_min_area_quads + ocrvi_quad_crops (not part of post_s)
         if not pages:
             return []
-        self.stats.update(jpeg=0, jpeg_stream_bytes=0, jpeg_parse_s=0.0, png=0, png_stream_bytes=0, png_parse_s=0.0)
-        self._jpeg = self._parse_jpegs(pages, infos)      # (a corrupt scan raises here: still before any GPU work)
+        for fmt in (JPEG, PNG):
+            self.stats.update({fmt.name: 0, f"{fmt.name}_stream_bytes": 0, f"{fmt.name}_parse_s": 0.0})
+        self._encoded = self._parse_files(pages, infos)      # (a corrupt scan raises here: still before any GPU work)
         self._sizes, self._shapes, self._scales = sizes, shapes, scales
         self._raw_sizes, self._mats, self._keep = raw_sizes, mats, []
         self._enhance = flags

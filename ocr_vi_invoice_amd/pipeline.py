@@ -8,6 +8,8 @@ inline code at :312-314), ``rescale_boxes`` (:324-328) and ``detect_and_recogniz
 its enhancement half (``enhance_document``, scanner.py:55-76); ``draw_boxes_with_text`` (:173) and, for the ``--save_result`` branch
 (:358-360 + :397-400), ``save_result``.
 Image resizing and crop pre-processing run on the GPU (ocrvi_crop_resize_normalize / ocrvi_normalize_u8).
+File I/O -- ``imdecode`` / ``imread``, ``imencode*`` / ``imwrite``, the JPEG and PNG wrappers and the encode jobs -- lives in ``codec`` and
+is re-exported here under the same names.
 
 ``DBPostProcessor`` (src/det/test.py:46-106) is the host C++ implementation behind ``ocrvi_db_postprocess``; like the reference's, it works on
 the probability map after the device->host copy.  cv2 / pyclipper / shapely are absent from the build container, so its agreement with
@@ -23,6 +25,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from .codec import (IMAGE_BYTES, IMWRITE_FORMATS, JPEG_BYTES, JPEG_SUBSAMPLINGS, PNG_ENC_REGIONS, PNG_FILTERS, PNG_SIGNATURE, JpegEncodeJob,
+                    PngEncodeJob, _check_format, _dev_index, host_pool, imdecode, imencode, imencode_pages, imencode_png, imencode_png_pages,
+                    imread, imwrite, is_png, jpeg_encode_header, jpeg_encode_sizes, jpeg_info, jpeg_info_struct, jpeg_parse, jpeg_parse_into,
+                    jpeg_quant_tables, jpeg_table_entry, png_encode_sizes, png_info, png_info_struct, png_parse, png_parse_into, png_plan,
+                    png_table_entry)
 from .det import DBNetPP
 from .rec import SVTRv2
 
@@ -59,11 +66,6 @@ def load_detection_model(model_path: str, device: str = "cuda:0", dtype: str = "
 def load_recognition_model(model_path: str, device: str = "cuda:0", variant: str = "base", dtype: str = "f32") -> SVTRv2:
     """pipeline2.py:72-89."""
     return SVTRv2(variant=variant, in_channels=3, state_dict=load_checkpoint(model_path), device=device, dtype=dtype)
-
-
-def _dev_index(device) -> int:
-    d = torch.device(device)
-    return d.index if d.index is not None else torch.cuda.current_device()
 
 
 def resize_image_for_det(image, image_size: int = 640):
@@ -582,216 +584,6 @@ def preprocess_image(image, quad, enhance: bool = False, device: str = "cuda:0")
     return four_point_transform(image, quad, device)
 
 
-JPEG_BYTES = (bytes, bytearray, memoryview)
-_JPEG_POOL = None
-
-
-def jpeg_pool():
-    """The host thread pool of the entropy decoder (``ocrvi_jpeg_parse`` holds no lock and ctypes releases the interpreter lock)."""
-    global _JPEG_POOL
-    if _JPEG_POOL is None:
-        import concurrent.futures
-        import os
-        try:
-            n = len(os.sched_getaffinity(0))
-        except AttributeError:
-            n = os.cpu_count() or 1
-        _JPEG_POOL = concurrent.futures.ThreadPoolExecutor(max(1, min(n, 16)), thread_name_prefix="ocrvi-jpeg")
-    return _JPEG_POOL
-
-
-def _jpeg_view(data) -> np.ndarray:
-    """The file's bytes as a uint8 array, without a copy."""
-    if not isinstance(data, JPEG_BYTES):
-        raise ValueError(f"expected JPEG bytes (bytes, bytearray or memoryview), got {type(data).__name__}")
-    return np.frombuffer(data, dtype=np.uint8)
-
-
-def jpeg_info_struct(data, what: str = "jpeg") -> "_lib.JpegInfo":
-    """``ocrvi_jpeg_info`` (host only); ValueError ``what: message`` for a file the library refuses or cannot read."""
-    a = _jpeg_view(data)
-    info = _lib.JpegInfo()
-    rc = _lib.load().ocrvi_jpeg_info(a.ctypes.data if a.size else None, a.size, ctypes.byref(info))
-    if rc == -1:
-        raise ValueError(f"{what}: {info.reason.decode('utf-8', 'replace')}")
-    _lib.check(rc)
-    return info
-
-
-def jpeg_info(data) -> dict:
-    """What ``ocrvi_jpeg_info`` reports about a JPEG file (host only, needs no GPU): the coded width, height, components, sampling factors,
-    restart interval, EXIF orientation, the decoded page's ``out_height`` / ``out_width`` (after orientation), the number of blocks and the
-    two sizes ``stream_bytes`` / ``workspace_bytes``.  ValueError naming the feature for an unsupported file, or the fault of a corrupt one."""
-    info = jpeg_info_struct(data)
-    n = info.components
-    return {"width": info.width, "height": info.height, "components": n, "h_samp": list(info.h_samp)[:n], "v_samp": list(info.v_samp)[:n],
-            "restart_interval": info.restart_interval, "orientation": info.orientation, "out_height": info.out_height,
-            "out_width": info.out_width, "blocks": info.blocks, "stream_bytes": info.stream_bytes, "workspace_bytes": info.workspace_bytes,
-            "quant": np.ctypeslib.as_array(info.quant).copy()[:n]}
-
-
-def jpeg_parse_into(data, out_ptr: int, cap: int, what: str = "jpeg") -> int:
-    """``ocrvi_jpeg_parse`` into ``cap`` bytes at ``out_ptr``; returns the bytes used.  The error is read on the calling thread (it is
-    thread-local): ValueError for a corrupt file, MemoryError for a short buffer."""
-    a = _jpeg_view(data)
-    used = ctypes.c_size_t()
-    rc = _lib.load().ocrvi_jpeg_parse(a.ctypes.data if a.size else None, a.size, out_ptr, cap, ctypes.byref(used))
-    if rc == -1:
-        raise ValueError(f"{what}: {_lib.last_error()}")
-    _lib.check(rc)
-    return used.value
-
-
-def jpeg_parse(data) -> np.ndarray:
-    """The sparse coefficient stream of a file as uint32 words (host only; include/ocrvi.h states the format)."""
-    info = jpeg_info_struct(data)
-    buf = np.empty(info.stream_bytes // 4, np.uint32)
-    return buf[:jpeg_parse_into(data, buf.ctypes.data, buf.nbytes) // 4].copy()
-
-
-def jpeg_table_entry(info, used: int, stream_offset: int, dst_offset: int, dst_stride: int, workspace_offset: int, entry: np.ndarray) -> None:
-    """``ocrvi_jpeg_table_entry`` into ``entry`` (int64 [JPEG_ENTRY], contiguous)."""
-    assert entry.dtype == np.int64 and entry.size == _lib.JPEG_ENTRY and entry.flags.c_contiguous
-    _lib.check(_lib.load().ocrvi_jpeg_table_entry(ctypes.byref(info), used, stream_offset, dst_offset, dst_stride, workspace_offset,
-                                                  entry.ctypes.data))
-
-
-def _align(v: int, a: int = 256) -> int:
-    return (v + a - 1) // a * a
-
-
-PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
-IMAGE_BYTES = JPEG_BYTES                          # what an encoded page may be: the bytes of a baseline JPEG file or of a PNG file
-
-
-def is_png(data) -> bool:
-    """Whether ``data`` (``IMAGE_BYTES``) starts with the PNG signature; everything else is handed to the JPEG decoder, whose messages
-    name what is wrong with it."""
-    return isinstance(data, IMAGE_BYTES) and _jpeg_view(data)[:8].tobytes() == PNG_SIGNATURE
-
-
-def png_info_struct(data, what: str = "png") -> "_lib.PngInfo":
-    """``ocrvi_png_info`` (host only); ValueError ``what: message`` for a file the library refuses or cannot read."""
-    a = _jpeg_view(data)
-    info = _lib.PngInfo()
-    rc = _lib.load().ocrvi_png_info(a.ctypes.data if a.size else None, a.size, ctypes.byref(info))
-    if rc == -1:
-        raise ValueError(f"{what}: {info.reason.decode('utf-8', 'replace')}")
-    _lib.check(rc)
-    return info
-
-
-def png_info(data) -> dict:
-    """What ``ocrvi_png_info`` reports about a PNG file (host only, needs no GPU).  ValueError naming the feature for an unsupported
-    file, or the fault of a corrupt one."""
-    info = png_info_struct(data)
-    return {k: getattr(info, k) for k in ("width", "height", "bit_depth", "colour_type", "channels", "row_bytes", "out_height", "out_width",
-                                          "palette_entries", "idat_bytes", "stream_bytes", "workspace_bytes")}
-
-
-def png_parse_into(data, out_ptr: int, cap: int, what: str = "png") -> int:
-    """``ocrvi_png_parse`` into ``cap`` bytes at ``out_ptr``; returns the bytes used.  The error is read on the calling thread (it is
-    thread-local): ValueError for a corrupt file, MemoryError for a short buffer."""
-    a = _jpeg_view(data)
-    used = ctypes.c_size_t()
-    rc = _lib.load().ocrvi_png_parse(a.ctypes.data if a.size else None, a.size, out_ptr, cap, ctypes.byref(used))
-    if rc == -1:
-        raise ValueError(f"{what}: {_lib.last_error()}")
-    _lib.check(rc)
-    return used.value
-
-
-def png_parse(data) -> np.ndarray:
-    """The stream of a file as uint8 (host only; include/ocrvi.h states the format)."""
-    info = png_info_struct(data)
-    buf = np.empty(info.stream_bytes, np.uint8)
-    return buf[:png_parse_into(data, buf.ctypes.data, buf.nbytes)]
-
-
-def png_table_entry(info, used: int, stream_offset: int, dst_offset: int, dst_stride: int, workspace_offset: int, entry: np.ndarray) -> None:
-    """``ocrvi_png_table_entry`` into ``entry`` (int64 [PNG_ENTRY], contiguous)."""
-    assert entry.dtype == np.int64 and entry.size == _lib.PNG_ENTRY and entry.flags.c_contiguous
-    _lib.check(_lib.load().ocrvi_png_table_entry(ctypes.byref(info), used, stream_offset, dst_offset, dst_stride, workspace_offset,
-                                                 entry.ctypes.data))
-
-
-def png_plan(info) -> dict:
-    """``ocrvi_png_plan`` (host only): ``band_rows``, ``chunk_bytes``, ``bands`` and ``steps`` of the kernel's walk over the page."""
-    v = [ctypes.c_int() for _ in range(4)]
-    _lib.check(_lib.load().ocrvi_png_plan(ctypes.byref(info), *[ctypes.byref(x) for x in v]))
-    return dict(zip(("band_rows", "chunk_bytes", "bands", "steps"), (x.value for x in v)))
-
-
-def _imdecode_group(files, names, dev, png: bool):
-    """The files of one format -> pages, in one batched launch (``ocrvi_png_decode_pages`` / ``ocrvi_jpeg_decode_pages``)."""
-    lib = _lib.load()
-    info_of, parse_into, entry_of, width = ((png_info_struct, png_parse_into, png_table_entry, _lib.PNG_ENTRY) if png else
-                                            (jpeg_info_struct, jpeg_parse_into, jpeg_table_entry, _lib.JPEG_ENTRY))
-    infos = [info_of(f, w) for f, w in zip(files, names)]
-    devi = _dev_index(dev)
-    s_off, w_off, d_off = [0], [0], [0]
-    for info in infos:
-        s_off.append(s_off[-1] + _align(info.stream_bytes))
-        w_off.append(w_off[-1] + info.workspace_bytes)
-        d_off.append(d_off[-1] + _align(info.out_height * info.out_width * 3))
-    h_rec = torch.empty(s_off[-1], dtype=torch.uint8).pin_memory()
-    base = h_rec.data_ptr()
-    jobs = [(f, base + s_off[i], infos[i].stream_bytes, names[i]) for i, f in enumerate(files)]
-    if len(files) > 1:
-        used = list(jpeg_pool().map(lambda j: parse_into(*j), jobs))
-    else:
-        used = [parse_into(*jobs[0])]
-    table = np.zeros((len(files), width), np.int64)
-    for i, info in enumerate(infos):
-        entry_of(info, used[i], s_off[i], d_off[i], 3 * info.out_width, w_off[i], table[i])
-    with torch.cuda.device(dev):
-        d_rec = torch.empty(s_off[-1], dtype=torch.uint8, device=dev)
-        for i in range(len(files)):            # only the bytes each stream uses cross the bus
-            d_rec[s_off[i]:s_off[i] + used[i]].copy_(h_rec[s_off[i]:s_off[i] + used[i]], non_blocking=True)
-        d_tab = torch.from_numpy(table).pin_memory().to(dev, non_blocking=True)
-        ws = torch.empty(max(w_off[-1], 8), dtype=torch.uint8, device=dev)
-        out = torch.empty(d_off[-1], dtype=torch.uint8, device=dev)
-        decode = lib.ocrvi_png_decode_pages if png else lib.ocrvi_jpeg_decode_pages
-        _lib.check(decode(devi, d_rec.data_ptr(), d_tab.data_ptr(), len(files), out.data_ptr(), ws.data_ptr(), ws.numel(),
-                          torch.cuda.current_stream(dev).cuda_stream))
-    return [out[d_off[i]:d_off[i] + info.out_height * info.out_width * 3].view(info.out_height, info.out_width, 3)
-            for i, info in enumerate(infos)]
-
-
-def imdecode(data, device: str = "cuda:0"):
-    """cv2.imdecode / cv2.imread + cvtColor(BGR2RGB) (src/pipeline/pipeline2.py:284-288) for baseline JPEG and PNG: ``data`` is the bytes
-    of one file (-> one uint8 [h, w, 3] RGB tensor on ``device``) or a list of them (-> a list of tensors in the caller's order).  The
-    decoder is chosen per file by its signature (the PNG signature against FF D8); a list may mix the two formats and costs one batched
-    launch per format.  What is serial per file runs on the host, a thread per file (JPEG: entropy decoding; PNG: inflate), everything else
-    in ``ocrvi_jpeg_decode_pages`` / ``ocrvi_png_decode_pages`` on the current stream; a JPEG's EXIF orientation is applied.  ValueError for
-    an unsupported or corrupt file (naming its index in a list); there is no host decoder behind these.  The arithmetic is stated in
-    include/ocrvi.h: PIL's output for encoder-produced JPEG files and for PNG (16-bit grey aside), cv2 parity unpinned."""
-    single = isinstance(data, IMAGE_BYTES)
-    files = [data] if single else list(data)
-    if not files:
-        return []
-    names = ["imdecode" if single else f"imdecode: file {i}" for i in range(len(files))]
-    dev = torch.device(device)
-    png = [is_png(f) for f in files]
-    for i, f in enumerate(files):              # every header is read (a bad one named, in the caller's order) before anything is decoded
-        (png_info_struct if png[i] else jpeg_info_struct)(f, names[i])
-    pngs, jpegs = [i for i, p in enumerate(png) if p], [i for i, p in enumerate(png) if not p]
-    pages = [None] * len(files)
-    for group, as_png in ((jpegs, False), (pngs, True)):
-        if group:
-            for i, page in zip(group, _imdecode_group([files[i] for i in group], [names[i] for i in group], dev, as_png)):
-                pages[i] = page
-    return pages[0] if single else pages
-
-
-def imread(path: str, device: str = "cuda:0") -> torch.Tensor:
-    """``cv2.imread(path)`` + ``cvtColor(BGR2RGB)`` of the reference's loop (pipeline2.py:284-288) for a baseline JPEG or a PNG file: the file's
-    bytes through ``imdecode``.  OSError for an unreadable file (the reference gets ``None`` and skips the image), ValueError for one that
-    is neither a supported JPEG nor a supported PNG."""
-    with open(path, "rb") as f:
-        return imdecode(f.read(), device)
-
-
 # ---------------------------------------------------------------------------------------------------- document finder
 DOC_KINDS = (None, "polygon", "rectangle")        # ocrvi_document_contour's `found`
 
@@ -924,7 +716,7 @@ def find_document_quads(images, polarity="auto", device: str = "cuda:0"):
         return quad.astype(np.float64) * sizes[i][1] if found.value else None
 
     if len(pages) > 1:
-        return list(jpeg_pool().map(finish, range(len(pages))))
+        return list(host_pool().map(finish, range(len(pages))))
     return [finish(0)]
 
 
@@ -932,326 +724,6 @@ def find_document_quad(image, polarity="auto", device: str = "cuda:0"):
     """``find_document_quads`` for one page: float64 [4, 2] or ``None``.  ``preprocess_image(image, find_document_quad(image))`` is the
     reference's ``preprocess_image`` (scanner.py:168-196) with the library's mask in the network's place."""
     return find_document_quads([image], polarity, device)[0]
-
-
-JPEG_SUBSAMPLINGS = {"4:2:0": 2, "4:4:4": 1}      # name -> luma sampling factor
-
-
-def jpeg_quant_tables(quality: int) -> Tuple[np.ndarray, np.ndarray]:
-    """``ocrvi_jpeg_quant_tables`` (host only): the luminance and chrominance tables of ``quality``, uint16 [64] in natural order."""
-    luma, chroma = np.zeros(64, np.uint16), np.zeros(64, np.uint16)
-    _lib.check(_lib.load().ocrvi_jpeg_quant_tables(int(quality), luma.ctypes.data, chroma.ctypes.data))
-    return luma, chroma
-
-
-def jpeg_encode_header(height: int, width: int, components: int, subsampling: str = "4:2:0", quality: int = 95) -> bytes:
-    """``ocrvi_jpeg_encode_header`` (host only): the bytes SOI .. SOS of the file ``imencode`` writes for such a page."""
-    if subsampling not in JPEG_SUBSAMPLINGS:
-        raise ValueError(f"subsampling {subsampling!r}: expected one of {sorted(JPEG_SUBSAMPLINGS)}")
-    buf = np.zeros(_lib.JPEG_HEADER_MAX, np.uint8)
-    used = ctypes.c_size_t()
-    _lib.check(_lib.load().ocrvi_jpeg_encode_header(int(width), int(height), int(components), JPEG_SUBSAMPLINGS[subsampling], int(quality),
-                                                    buf.ctypes.data, buf.size, ctypes.byref(used)))
-    return buf[:used.value].tobytes()
-
-
-def jpeg_encode_sizes(height: int, width: int, components: int, subsampling: str = "4:2:0") -> dict:
-    """``ocrvi_jpeg_encode_sizes`` (host only): ``blocks``, ``workspace_bytes``, ``scan_capacity`` and the workspace ``offsets`` of a page."""
-    if subsampling not in JPEG_SUBSAMPLINGS:
-        raise ValueError(f"subsampling {subsampling!r}: expected one of {sorted(JPEG_SUBSAMPLINGS)}")
-    blocks, wsb, cap = ctypes.c_int64(), ctypes.c_uint64(), ctypes.c_uint64()
-    offs = np.zeros(8, np.uint64)
-    _lib.check(_lib.load().ocrvi_jpeg_encode_sizes(int(width), int(height), int(components), JPEG_SUBSAMPLINGS[subsampling], ctypes.byref(blocks),
-                                                   ctypes.byref(wsb), ctypes.byref(cap), offs.ctypes.data))
-    return {"blocks": blocks.value, "workspace_bytes": wsb.value, "scan_capacity": cap.value, "offsets": [int(v) for v in offs]}
-
-
-class JpegEncodeJob:
-    """The pages of one ``ocrvi_jpeg_encode_pages`` call: validated and laid out by the constructor (ValueError before anything touches
-    the device), uploaded and enqueued by ``launch`` (one page table, one set of launches, no synchronisation), read back by ``collect``
-    (the lengths, then only the compressed bytes).  ``imencode_pages`` is ``JpegEncodeJob(...).launch().collect()``."""
-
-    def __init__(self, images, quality=95, subsampling: str = "4:2:0", device="cuda:0", what: str = "imencode"):
-        if subsampling not in JPEG_SUBSAMPLINGS:
-            raise ValueError(f"{what}: subsampling {subsampling!r}: expected one of {sorted(JPEG_SUBSAMPLINGS)}")
-        self.images = list(images)
-        n = len(self.images)
-        if isinstance(quality, (list, tuple, np.ndarray)):
-            if len(quality) != n:
-                raise ValueError(f"{what}: {len(quality)} qualities for {n} pages")
-            qualities = list(quality)
-        else:
-            qualities = [quality] * n
-        self.qualities = []
-        for i, q in enumerate(qualities):
-            if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or not 1 <= int(q) <= 100:
-                raise ValueError(f"{what}: page {i}: quality {q!r} outside 1..100")
-            self.qualities.append(int(q))
-        self.subsampling = subsampling
-        self.dev = torch.device(device)
-        self.geom = []                          # (h, w, components, luma sampling factor)
-        for i, im in enumerate(self.images):
-            if not isinstance(im, (np.ndarray, torch.Tensor)):
-                raise ValueError(f"{what}: page {i}: expected a numpy array or a tensor, got {type(im).__name__}")
-            if im.dtype not in (np.uint8, torch.uint8):
-                raise ValueError(f"{what}: page {i}: dtype {im.dtype} (uint8 expected)")
-            shape = tuple(im.shape)
-            if not (len(shape) == 2 or (len(shape) == 3 and shape[2] == 3)):
-                raise ValueError(f"{what}: page {i}: shape {shape} (H x W x 3 RGB or H x W grey expected)")
-            if not (1 <= shape[0] <= 65500 and 1 <= shape[1] <= 65500):
-                raise ValueError(f"{what}: page {i}: sides {shape[0]} x {shape[1]} outside 1..65500")
-            nc = 1 if len(shape) == 2 else 3
-            self.geom.append((shape[0], shape[1], nc, 1 if nc == 1 else JPEG_SUBSAMPLINGS[subsampling]))
-        lib = _lib.load()
-        self.w_off, self.o_off, self.caps = [0], [0], []
-        for h, w, nc, hs in self.geom:
-            wsb, cap = ctypes.c_uint64(), ctypes.c_uint64()
-            rc = lib.ocrvi_jpeg_encode_sizes(w, h, nc, hs, None, ctypes.byref(wsb), ctypes.byref(cap), None)
-            if rc == -1:
-                raise ValueError(f"{what}: {_lib.last_error()}")
-            _lib.check(rc)
-            self.caps.append(_align(cap.value))
-            self.w_off.append(self.w_off[-1] + wsb.value)
-            self.o_off.append(self.o_off[-1] + self.caps[-1])
-        self.lengths = self.out = None
-
-    def launch(self) -> "JpegEncodeJob":
-        n = len(self.images)
-        if n == 0:
-            return self
-        dev, lib = self.dev, _lib.load()
-        with torch.cuda.device(dev):
-            # host pages travel in one pinned buffer and one copy; device pages are read where they lie
-            host = [i for i, im in enumerate(self.images) if isinstance(im, np.ndarray) or not im.is_cuda]
-            h_off = [0]
-            for i in host:
-                h, w, nc, _ = self.geom[i]
-                h_off.append(h_off[-1] + _align(h * w * nc))
-            src = [None] * n
-            if host:
-                stage = torch.empty(h_off[-1], dtype=torch.uint8).pin_memory()
-                for k, i in enumerate(host):
-                    im = self.images[i]
-                    flat = torch.from_numpy(np.ascontiguousarray(im)) if isinstance(im, np.ndarray) else im.contiguous()
-                    stage[h_off[k]:h_off[k] + flat.numel()].copy_(flat.reshape(-1))
-                d_stage = stage.to(dev, non_blocking=True)
-                for k, i in enumerate(host):
-                    src[i] = d_stage[h_off[k]:]
-            for i, im in enumerate(self.images):
-                if src[i] is None:
-                    src[i] = im.to(dev).contiguous()
-            base = src[0].data_ptr()
-            table = np.zeros((n, _lib.JPEG_ENC_ENTRY), np.int64)
-            for i, (h, w, nc, hs) in enumerate(self.geom):
-                _lib.check(lib.ocrvi_jpeg_encode_table_entry(w, h, nc, hs, self.qualities[i], src[i].data_ptr() - base, w * nc, self.o_off[i],
-                                                             self.caps[i], self.w_off[i], table[i].ctypes.data))
-            self._src = src                     # kept alive until collect
-            d_tab = torch.from_numpy(table).pin_memory().to(dev, non_blocking=True)
-            self._ws = torch.empty(self.w_off[-1], dtype=torch.uint8, device=dev)
-            self.out = torch.empty(self.o_off[-1], dtype=torch.uint8, device=dev)
-            self.lengths = torch.empty(n, dtype=torch.int64, device=dev)
-            self._tab, self._base = d_tab, base
-            self.enqueue()
-        return self
-
-    def enqueue(self) -> None:
-        """The six launches alone, on the current stream (what tools/jpeg_encode_bench.py times as "kernels")."""
-        _lib.check(_lib.load().ocrvi_jpeg_encode_pages(_dev_index(self.dev), self._base, self._tab.data_ptr(), len(self.images), self.out.data_ptr(),
-                                                       self.lengths.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
-                                                       torch.cuda.current_stream(self.dev).cuda_stream))
-
-    def collect_scans(self) -> List[bytes]:
-        """Waits for the lengths, then copies the compressed bytes alone to the host."""
-        n = len(self.images)
-        if n == 0:
-            return []
-        lens = [int(v) for v in self.lengths.cpu()]
-        for i, ln in enumerate(lens):
-            if not 0 < ln <= self.caps[i]:
-                raise RuntimeError(f"jpeg encode: page {i} was skipped by the device (length {ln})")
-        packed = torch.cat([self.out[self.o_off[i]:self.o_off[i] + lens[i]] for i in range(n)]) if n > 1 else self.out[:lens[0]]
-        host = packed.cpu().numpy()
-        ends = np.cumsum([0] + lens)
-        return [host[ends[i]:ends[i + 1]].tobytes() for i in range(n)]
-
-    def collect(self) -> List[bytes]:
-        scans = self.collect_scans()
-        return [jpeg_encode_header(h, w, nc, self.subsampling, self.qualities[i]) + scans[i] + b"\xff\xd9"
-                for i, (h, w, nc, _) in enumerate(self.geom)]
-
-
-def imencode_pages(images, quality=95, subsampling: str = "4:2:0", device: str = "cuda:0") -> List[bytes]:
-    """``imencode`` for a list of pages of any sizes, grey and colour mixed, ``quality`` a scalar or one value per page: one upload of a
-    page table and one set of launches (``ocrvi_jpeg_encode_pages``) serve the whole list; only the compressed bytes come back."""
-    return JpegEncodeJob(images, quality, subsampling, device, "imencode_pages").launch().collect()
-
-
-def imencode(image, quality: int = 95, subsampling: str = "4:2:0", device: str = "cuda:0") -> bytes:
-    """``cv2.imencode(".jpg", image, [IMWRITE_JPEG_QUALITY, quality])`` for an RGB page: the bytes of a baseline JPEG file.  ``image`` is
-    uint8 [h, w, 3] RGB or uint8 [h, w] grey (a one-component file), a numpy array or a tensor on the host or the device; ``subsampling`` is
-    "4:2:0" (what cv2.imwrite and PIL write by default) or "4:4:4".  The host writes the header; everything else runs on the device.  The
-    arithmetic is stated in include/ocrvi.h: libjpeg-turbo's default encoder byte for byte (PIL's ``save(..., "JPEG", quality=q)``), cv2
-    parity unpinned.  ValueError for sides outside 1..65500, other dtypes, shapes or subsamplings, or a quality outside 1..100."""
-    return JpegEncodeJob([image], quality, subsampling, device, "imencode").launch().collect()[0]
-
-
-PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}      # name -> filter mode (OCRVI_PNG_FILTER_*)
-PNG_ENC_REGIONS = ("filters", "stream", "hist", "lens", "cl_tokens", "records", "bit_offsets", "crc_partials", "info")
-
-
-def png_encode_sizes(height: int, width: int, components: int) -> dict:
-    """``ocrvi_png_encode_sizes`` (host only): ``stream_bytes``, ``blocks``, ``workspace_bytes``, ``out_capacity`` and the workspace
-    ``offsets`` of a page."""
-    stream, blocks, wsb, cap = ctypes.c_uint64(), ctypes.c_int64(), ctypes.c_uint64(), ctypes.c_uint64()
-    offs = np.zeros(9, np.uint64)
-    _lib.check(_lib.load().ocrvi_png_encode_sizes(int(width), int(height), int(components), ctypes.byref(stream), ctypes.byref(blocks),
-                                                  ctypes.byref(wsb), ctypes.byref(cap), offs.ctypes.data))
-    return {"stream_bytes": stream.value, "blocks": blocks.value, "workspace_bytes": wsb.value, "out_capacity": cap.value,
-            "offsets": [int(v) for v in offs]}
-
-
-class PngEncodeJob:
-    """The pages of one ``ocrvi_png_encode_pages`` call, shaped like ``JpegEncodeJob``: validated and laid out by the constructor
-    (ValueError before anything touches the device), uploaded and enqueued by ``launch`` (one page table, one set of launches, no
-    synchronisation), read back by ``collect`` (the lengths, then only the files' bytes).  ``stage(i)`` reads page i's workspace regions
-    for the tests.  ``imencode_png_pages`` is ``PngEncodeJob(...).launch().collect()``."""
-
-    def __init__(self, images, filters: str = "adaptive", device="cuda:0", what: str = "imencode_png"):
-        if filters not in PNG_FILTERS:
-            raise ValueError(f"{what}: filters {filters!r}: expected one of {sorted(PNG_FILTERS)}")
-        self.images = list(images)
-        self.filters = filters
-        self.dev = torch.device(device)
-        self.geom = []                          # (h, w, components)
-        for i, im in enumerate(self.images):
-            if not isinstance(im, (np.ndarray, torch.Tensor)):
-                raise ValueError(f"{what}: page {i}: expected a numpy array or a tensor, got {type(im).__name__}")
-            if im.dtype not in (np.uint8, torch.uint8):
-                raise ValueError(f"{what}: page {i}: dtype {im.dtype} (uint8 expected)")
-            shape = tuple(im.shape)
-            if not (len(shape) == 2 or (len(shape) == 3 and shape[2] == 3)):
-                raise ValueError(f"{what}: page {i}: shape {shape} (H x W x 3 RGB or H x W grey expected)")
-            if not (1 <= shape[0] <= 65500 and 1 <= shape[1] <= 65500):
-                raise ValueError(f"{what}: page {i}: sides {shape[0]} x {shape[1]} outside 1..65500")
-            self.geom.append((shape[0], shape[1], 1 if len(shape) == 2 else 3))
-        lib = _lib.load()
-        self.w_off, self.o_off, self.caps, self.offsets = [0], [0], [], []
-        for i, (h, w, nc) in enumerate(self.geom):
-            wsb, cap = ctypes.c_uint64(), ctypes.c_uint64()
-            offs = np.zeros(9, np.uint64)
-            rc = lib.ocrvi_png_encode_sizes(w, h, nc, None, None, ctypes.byref(wsb), ctypes.byref(cap), offs.ctypes.data)
-            if rc == -1:
-                raise ValueError(f"{what}: page {i}: {_lib.last_error()}")
-            _lib.check(rc)
-            self.caps.append(_align(cap.value))
-            self.offsets.append([int(v) for v in offs] + [wsb.value])
-            self.w_off.append(self.w_off[-1] + wsb.value)
-            self.o_off.append(self.o_off[-1] + self.caps[-1])
-        self.lengths = self.out = None
-
-    def launch(self) -> "PngEncodeJob":
-        n = len(self.images)
-        if n == 0:
-            return self
-        dev, lib = self.dev, _lib.load()
-        with torch.cuda.device(dev):
-            # host pages travel in one pinned buffer and one copy; device pages are read where they lie
-            host = [i for i, im in enumerate(self.images) if isinstance(im, np.ndarray) or not im.is_cuda]
-            h_off = [0]
-            for i in host:
-                h, w, nc = self.geom[i]
-                h_off.append(h_off[-1] + _align(h * w * nc))
-            src = [None] * n
-            if host:
-                stage = torch.empty(h_off[-1], dtype=torch.uint8).pin_memory()
-                for k, i in enumerate(host):
-                    im = self.images[i]
-                    flat = torch.from_numpy(np.ascontiguousarray(im)) if isinstance(im, np.ndarray) else im.contiguous()
-                    stage[h_off[k]:h_off[k] + flat.numel()].copy_(flat.reshape(-1))
-                d_stage = stage.to(dev, non_blocking=True)
-                for k, i in enumerate(host):
-                    src[i] = d_stage[h_off[k]:]
-            for i, im in enumerate(self.images):
-                if src[i] is None:
-                    src[i] = im.to(dev).contiguous()
-            base = src[0].data_ptr()
-            table = np.zeros((n, _lib.PNG_ENC_ENTRY), np.int64)
-            for i, (h, w, nc) in enumerate(self.geom):
-                _lib.check(lib.ocrvi_png_encode_table_entry(w, h, nc, PNG_FILTERS[self.filters], src[i].data_ptr() - base, w * nc, self.o_off[i],
-                                                            self.caps[i], self.w_off[i], table[i].ctypes.data))
-            self._src = src                     # kept alive until collect
-            d_tab = torch.from_numpy(table).pin_memory().to(dev, non_blocking=True)
-            self._ws = torch.empty(self.w_off[-1], dtype=torch.uint8, device=dev)
-            self.out = torch.empty(self.o_off[-1], dtype=torch.uint8, device=dev)
-            self.lengths = torch.empty(n, dtype=torch.int64, device=dev)
-            self._tab, self._base = d_tab, base
-            self.enqueue()
-        return self
-
-    def enqueue(self) -> None:
-        """The six launches alone, on the current stream (what tools/png_encode_bench.py times as "kernels")."""
-        _lib.check(_lib.load().ocrvi_png_encode_pages(_dev_index(self.dev), self._base, self._tab.data_ptr(), len(self.images), self.out.data_ptr(),
-                                                      self.lengths.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
-                                                      torch.cuda.current_stream(self.dev).cuda_stream))
-
-    def stage(self, i: int) -> dict:
-        """Page i's workspace regions as uint8 arrays on the host, by the names of ``PNG_ENC_REGIONS`` (include/ocrvi.h states what each
-        holds); for the tests."""
-        o = self.offsets[i]
-        ws = self._ws[self.w_off[i]:self.w_off[i] + o[9]].cpu().numpy()
-        return {name: ws[o[k]:o[k + 1]] for k, name in enumerate(PNG_ENC_REGIONS)}
-
-    def collect(self) -> List[bytes]:
-        """Waits for the lengths, then copies the files' bytes alone to the host."""
-        n = len(self.images)
-        if n == 0:
-            return []
-        lens = [int(v) for v in self.lengths.cpu()]
-        for i, ln in enumerate(lens):
-            if not 0 < ln <= self.caps[i]:
-                raise RuntimeError(f"png encode: page {i} was skipped by the device (length {ln})")
-        packed = torch.cat([self.out[self.o_off[i]:self.o_off[i] + lens[i]] for i in range(n)]) if n > 1 else self.out[:lens[0]]
-        host = packed.cpu().numpy()
-        ends = np.cumsum([0] + lens)
-        return [host[ends[i]:ends[i + 1]].tobytes() for i in range(n)]
-
-
-def imencode_png_pages(images, filters: str = "adaptive", device: str = "cuda:0") -> List[bytes]:
-    """``imencode_png`` for a list of pages of any sizes, grey and colour mixed: one upload of a page table and one set of launches
-    (``ocrvi_png_encode_pages``) serve the whole list; only the files' bytes come back."""
-    return PngEncodeJob(images, filters, device, "imencode_png_pages").launch().collect()
-
-
-def imencode_png(image, filters: str = "adaptive", device: str = "cuda:0") -> bytes:
-    """``cv2.imencode(".png", image)`` for an RGB page: the bytes of a PNG file (bit depth 8, colour type 2, or 0 for a grey page, no
-    interlace, the chunks IHDR, one IDAT, IEND).  ``image`` is uint8 [h, w, 3] RGB or uint8 [h, w] grey, a numpy array or a tensor on the
-    host or the device.  ``filters``: "adaptive" (libpng's heuristic per row) or one of "none", "sub", "up", "average", "paeth" for every
-    row.  Filtering, deflate (distance-1 matches, the cheapest of stored, fixed and dynamic codes per 16 KiB block), both checksums and the
-    file's assembly run on the device; the arithmetic is stated in include/ocrvi.h.  Lossless: ``imdecode`` (and zlib, PIL) read the pixels
-    back exactly.  ValueError for other dtypes, shapes or filters, sides outside 1..65500, or a page whose IDAT could exceed 2^31 - 1 bytes."""
-    return PngEncodeJob([image], filters, device, "imencode_png").launch().collect()[0]
-
-
-IMWRITE_FORMATS = (None, "png")
-
-
-def _check_format(format, what: str) -> None:
-    if format not in IMWRITE_FORMATS:
-        raise ValueError(f"{what}: format {format!r}: expected None (JPEG) or 'png'")
-
-
-def imwrite(path: str, image, quality: int = 95, subsampling: str = "4:2:0", device: str = "cuda:0", format=None, filters: str = "adaptive") -> bool:
-    """``cv2.imwrite(path, image)`` of the reference's loop (pipeline2.py:397-400) for an RGB page: ``imencode`` into the file -- JPEG
-    whatever the suffix of ``path`` says -- or, with ``format="png"``, ``imencode_png`` (``quality`` and ``subsampling`` are then ignored).
-    True when the file was written, False when it could not be (cv2's convention); ValueError as ``imencode`` / ``imencode_png``."""
-    _check_format(format, "imwrite")
-    data = imencode_png(image, filters, device) if format == "png" else imencode(image, quality, subsampling, device)
-    try:
-        with open(path, "wb") as f:
-            f.write(data)
-    except OSError:
-        return False
-    return True
 
 
 # ---------------------------------------------------------------------------------------------------- result overlay
