@@ -296,24 +296,43 @@ int k_frm_vertical(int dtype, const void* kv, const float* vq, void* out, int B,
 // their NATIVE resolution (1/4 + 1/16 + 1/64 of the pixels).  (2) asf_blend_kernel at p2 resolution: 16 lanes share a pixel
 // (16 channels = two 16-byte chunks per lane, 4 pixels per wave): own-level score by a 16-lane butterfly, coarse scores by
 // bilinear taps of the tiny maps, softmax over 4, then out = a0*p2 + sum_{l,tap} (a_l*w_tap) * p_l[tap].
+// asf_scores_kernel: one launch covers the three levels: the work items are chunks of four consecutive pixels of one level (level 3's chunks first, the
+// largest), a wave takes chunks with a grid stride and has a chunk's four 1 KB pixel loads in flight before it reduces the first (with
+// one pixel per pass a wave waited out a full memory round trip per pixel).  Per pixel the arithmetic is unchanged.
 template <typename T>
-__global__ __launch_bounds__(256) void asf_scores_kernel(const T* __restrict__ p, const float* __restrict__ w, float* __restrict__ sc, int level,
-                                                         size_t npix) {
-    const int lane = threadIdx.x & 63;
-    float wr[4][4];
+__device__ __forceinline__ void asf_score_chunk(const T* __restrict__ p, const float (&wr)[4][4], float* __restrict__ sc, size_t pix0, size_t npix,
+                                                int lane) {
+    float f[4][4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float4 t = *(const float4*)(w + i * 1024 + level * 256 + lane * 4);
-        wr[i][0] = t.x; wr[i][1] = t.y; wr[i][2] = t.z; wr[i][3] = t.w;
-    }
-    const size_t wave = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (size_t)gridDim.x * 4;
-    for (size_t pix = wave; pix < npix; pix += nwaves) {
-        float f[4];
-        load4<T>(p + pix * 256 + lane * 4, f);
+    for (int u = 0; u < 4; ++u) load4<T>(p + min(pix0 + u, npix - 1) * 256 + lane * 4, f[u]);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
         float a[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) a[i] = wave_sum(f[0] * wr[i][0] + f[1] * wr[i][1] + f[2] * wr[i][2] + f[3] * wr[i][3]);
-        if (lane == 0) *(float4*)(sc + pix * 4) = make_float4(a[0], a[1], a[2], a[3]);
+        for (int i = 0; i < 4; ++i) a[i] = wave_sum(f[u][0] * wr[i][0] + f[u][1] * wr[i][1] + f[u][2] * wr[i][2] + f[u][3] * wr[i][3]);
+        if (lane == 0 && pix0 + u < npix) *(float4*)(sc + (pix0 + u) * 4) = make_float4(a[0], a[1], a[2], a[3]);
+    }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void asf_scores_kernel(const T* __restrict__ p3, const T* __restrict__ p4, const T* __restrict__ p5,
+                                                         const float* __restrict__ w, float* __restrict__ s3, float* __restrict__ s4,
+                                                         float* __restrict__ s5, size_t n3, size_t n4, size_t n5) {
+    const int lane = threadIdx.x & 63;
+    float w3[4][4], w4[4][4], w5[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float4 a = *(const float4*)(w + i * 1024 + 256 + lane * 4), b = *(const float4*)(w + i * 1024 + 512 + lane * 4),
+                     c = *(const float4*)(w + i * 1024 + 768 + lane * 4);
+        w3[i][0] = a.x; w3[i][1] = a.y; w3[i][2] = a.z; w3[i][3] = a.w;
+        w4[i][0] = b.x; w4[i][1] = b.y; w4[i][2] = b.z; w4[i][3] = b.w;
+        w5[i][0] = c.x; w5[i][1] = c.y; w5[i][2] = c.z; w5[i][3] = c.w;
+    }
+    const size_t c3 = (n3 + 3) / 4, c4 = (n4 + 3) / 4, c5 = (n5 + 3) / 4;
+    const size_t wave = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (size_t)gridDim.x * 4;
+    for (size_t c = wave; c < c3 + c4 + c5; c += nwaves) {      // wave-uniform
+        if (c < c3) asf_score_chunk<T>(p3, w3, s3, c * 4, n3, lane);
+        else if (c < c3 + c4) asf_score_chunk<T>(p4, w4, s4, (c - c3) * 4, n4, lane);
+        else asf_score_chunk<T>(p5, w5, s5, (c - c3 - c4) * 4, n5, lane);
     }
 }
 
@@ -426,7 +445,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // registers -- (top, bottom) in use and the row after them already requested -- and p2 runs four pixels ahead; in the steady state no
 // load is waited for.  The four waves of a workgroup take four adjacent columns (their coarse taps overlap in L1).  The arithmetic is
 // asf_blend_kernel's except for the order of the 64-lane score sums (DPP row sums + four row totals instead of a butterfly).
+//
+// What belongs to a PIXEL and not to a channel is computed with one pixel per lane instead of 64 times over.  Per task, lane r takes row
+// ya + r of the column: the three levels' y0, their four tap weights and the sum of the twelve coarse score terms (ordinary vector
+// loads, summed in level and tap order: the walk has no scalar loads).  The walk then goes in groups of ASF_G pixels: (1) per pixel the
+// own-level partial sums, reduced as before (wave_sum_uniform) and kept in lane (row) of four registers; (2) once per group, all lanes
+// at once: score = (own + bias) + coarse sum, the softmax and the thirteen blend coefficients a0, a_l * tw[l][q]; (3) the group's
+// pixels are blended, each reading its coefficients from its lane (v_readlane) and the "did y0 advance" decision from lane r's y0.
+// Tap coordinates, fractions, tap weights and own-level sums have the per-pixel form's bits: x fractions as fma(scale, x, -x0), y
+// fractions from the ROUNDED product (tap_frac_rounded), which is what the compiler made of the wave-uniform form.  The 13-term score
+// sum is ordered differently -- the per-pixel form adds the twelve coarse fmas onto own + bias one by one, which would keep 48 score
+// registers per lane alive through the walk -- so a score, and with it `fused`, can differ by an fp32 rounding of the score.
+// Segment heights are multiples of 8 (k_asf), hence of ASF_G.
 constexpr int ASF_TALL = 48;
+constexpr int ASF_G = 4;
+static_assert(ASF_TALL <= 64 && ASF_TALL % 8 == 0 && 8 % ASF_G == 0, "one row per lane, whole groups");
+// f = scale * c rounded, i0 = (int)f, frac = f - i0: never contracted into fma(scale, c, -i0)
+__device__ __forceinline__ void tap_frac_rounded(float scale, float c, int& i0, float& frac) {
+#pragma clang fp contract(off)
+    const float f = scale * c;
+    i0 = (int)f;
+    frac = f - (float)i0;
+}
+__device__ __forceinline__ float lane_value(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
 template <typename T>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void asf_blend_col_kernel(const T* __restrict__ p2, const T* __restrict__ p3, const T* __restrict__ p4,
                                                         const T* __restrict__ p5, const float* __restrict__ s3, const float* __restrict__ s4,
@@ -455,9 +496,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const int sx = task % strips, tt = task / strips, sg = tt % segs, n = tt / segs;
         const int x = sx * 4 + wv;
         const int ya = sg * ASF_TALL, yb = min(ya + ASF_TALL, H);      // rows [ya, yb) of column x
-        // ---- per level: the taps' column pair and its weights, and three tap rows: slots 0,1 = (top, x0 / x1), 2,3 = bottom, 4,5 = next
-        int cx0[3], cx1[3], cy0[3], base[3];
-        float clx[3];
+        const int rows = yb - ya;
+        // ---- per level: the taps' column pair and its weights (wave-uniform); in lanes, row min(ya + lane, H - 1): y0, the four tap
+        // weights and the four coarse score vectors; three tap rows: slots 0,1 = (top, x0 / x1), 2,3 = bottom, 4,5 = next
+        const int yl = min(ya + lane, H - 1);
+        int cx0[3], cx1[3], cy0[3], base[3], ly0[3];
+        float tw[3][4];
+        float cs[4] = {0.f, 0.f, 0.f, 0.f};       // lane r: the twelve coarse score terms of row ya + r, summed in level and tap order
         uint4 tap[3][6];
 #pragma unroll
         for (int l = 0; l < 3; ++l) {
@@ -466,9 +511,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             const int x0 = (int)fx;
             cx0[l] = x0;
             cx1[l] = x0 + (x0 < Wl - 1 ? 1 : 0);
-            clx[l] = fx - (float)x0;
+            const float lx = fmaf(swl[l], (float)x, -(float)x0), hx = 1.f - lx;
             base[l] = n * Hl * Wl;
-            const int y0 = __builtin_amdgcn_readfirstlane((int)(shl[l] * (float)ya));
+            float ly;
+            tap_frac_rounded(shl[l], (float)yl, ly0[l], ly);
+            const float hy = 1.f - ly;
+            tw[l][0] = hy * hx; tw[l][1] = hy * lx; tw[l][2] = ly * hx; tw[l][3] = ly * lx;
+            const int y1 = ly0[l] + (ly0[l] < Hl - 1 ? 1 : 0);
+            const int r0 = base[l] + ly0[l] * Wl, r1 = base[l] + y1 * Wl;
+            const float4 sv[4] = {*(const float4*)(slev[l] + (size_t)(r0 + cx0[l]) * 4), *(const float4*)(slev[l] + (size_t)(r0 + cx1[l]) * 4),
+                                  *(const float4*)(slev[l] + (size_t)(r1 + cx0[l]) * 4), *(const float4*)(slev[l] + (size_t)(r1 + cx1[l]) * 4)};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (l == 0 && q == 0) {
+                    cs[0] = tw[l][q] * sv[q].x; cs[1] = tw[l][q] * sv[q].y; cs[2] = tw[l][q] * sv[q].z; cs[3] = tw[l][q] * sv[q].w;
+                } else {
+                    cs[0] = fmaf(tw[l][q], sv[q].x, cs[0]); cs[1] = fmaf(tw[l][q], sv[q].y, cs[1]);
+                    cs[2] = fmaf(tw[l][q], sv[q].z, cs[2]); cs[3] = fmaf(tw[l][q], sv[q].w, cs[3]);
+                }
+            }
+            const int y0 = __builtin_amdgcn_readlane(ly0[l], 0);
             cy0[l] = y0;
 #pragma unroll
             for (int r = 0; r < 3; ++r) {
@@ -480,87 +542,80 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const T* const pcol = p2 + (((size_t)n * H + ya) * W + x) * 256 + lane * 4;
         T* const ocol = out + (((size_t)n * H + ya) * W + x) * 256 + lane * 4;
         const size_t rowstep = (size_t)W * 256;
-        const int rows = yb - ya;
-        uint4 ring[4];
+        uint4 ring[ASF_G];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) ring[k] = *(const uint4*)(pcol + (size_t)min(k, rows - 1) * rowstep);
-        auto pixel = [&](int yy, uint4& slot) {
-            const int y = ya + yy;
-            float f0[4];
-            Chunk<T>::unpack(slot, f0);
-            slot = *(const uint4*)(pcol + (size_t)min(yy + 4, rows - 1) * rowstep);     // four pixels ahead
-            // tap rows of this pixel; the coarse score vectors are wave-uniform loads (scalar), requested before the reductions below
-            float tw[3][4];
-            float4 sv[3][4];
+        for (int k = 0; k < ASF_G; ++k) ring[k] = *(const uint4*)(pcol + (size_t)min(k, rows - 1) * rowstep);
+        float own[4] = {0.f, 0.f, 0.f, 0.f};      // lane r: the own-level score sums of row ya + r
+#pragma unroll 1
+        for (int g0 = 0; g0 < rows; g0 += ASF_G) {      // rows is a multiple of ASF_G; the p2 ring has static slots
+            float f0[ASF_G][4];
+            // (1) own-level scores of the group's pixels, each into its lane
 #pragma unroll
-            for (int l = 0; l < 3; ++l) {
-                const int Hl = H >> (l + 1), Wl = W >> (l + 1);
-                const float fy = shl[l] * (float)y;
-                const int y0 = __builtin_amdgcn_readfirstlane((int)fy);
-                if (y0 != cy0[l]) {      // wave-uniform: the rows advance by one; request the row after the new bottom row
-                    tap[l][0] = tap[l][2]; tap[l][1] = tap[l][3];
-                    tap[l][2] = tap[l][4]; tap[l][3] = tap[l][5];
-                    const int row = min(y0 + 2, Hl - 1);
-                    tap[l][4] = *(const uint4*)(lev[l] + (size_t)(base[l] + row * Wl + cx0[l]) * 256 + lane * 4);
-                    tap[l][5] = *(const uint4*)(lev[l] + (size_t)(base[l] + row * Wl + cx1[l]) * 256 + lane * 4);
-                    cy0[l] = y0;
+            for (int k = 0; k < ASF_G; ++k) {
+                Chunk<T>::unpack(ring[k], f0[k]);
+                ring[k] = *(const uint4*)(pcol + (size_t)min(g0 + k + ASF_G, rows - 1) * rowstep);     // ASF_G pixels ahead
+                const bool mine = lane == g0 + k;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    float a = 0.f;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) a = fmaf(w0[i][e], f0[k][e], a);
+                    const float t = wave_sum_uniform(a);
+                    own[i] = mine ? t : own[i];
                 }
-                const int y1 = y0 + (y0 < Hl - 1 ? 1 : 0);
-                const float ly = fy - (float)y0, lx = clx[l], hy = 1.f - ly, hx = 1.f - lx;
-                tw[l][0] = hy * hx; tw[l][1] = hy * lx; tw[l][2] = ly * hx; tw[l][3] = ly * lx;
-                const int o00 = __builtin_amdgcn_readfirstlane(base[l] + y0 * Wl + cx0[l]), o01 = __builtin_amdgcn_readfirstlane(base[l] + y0 * Wl + cx1[l]);
-                const int o10 = __builtin_amdgcn_readfirstlane(base[l] + y1 * Wl + cx0[l]), o11 = __builtin_amdgcn_readfirstlane(base[l] + y1 * Wl + cx1[l]);
-                sv[l][0] = *(const float4*)(slev[l] + (size_t)o00 * 4); sv[l][1] = *(const float4*)(slev[l] + (size_t)o01 * 4);
-                sv[l][2] = *(const float4*)(slev[l] + (size_t)o10 * 4); sv[l][3] = *(const float4*)(slev[l] + (size_t)o11 * 4);
             }
-            float sc[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float a = 0.f;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) a = fmaf(w0[i][e], f0[e], a);
-                sc[i] = wave_sum_uniform(a);
-            }
-            sc[0] += bv.x; sc[1] += bv.y; sc[2] += bv.z; sc[3] += bv.w;
-#pragma unroll
-            for (int l = 0; l < 3; ++l)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    sc[0] = fmaf(tw[l][q], sv[l][q].x, sc[0]); sc[1] = fmaf(tw[l][q], sv[l][q].y, sc[1]);
-                    sc[2] = fmaf(tw[l][q], sv[l][q].z, sc[2]); sc[3] = fmaf(tw[l][q], sv[l][q].w, sc[3]);
-                }
+            // (2) all lanes: scores, softmax, blend coefficients (the lanes of the group hold this group's; the others' are not read)
+            float sc[4] = {(own[0] + bv.x) + cs[0], (own[1] + bv.y) + cs[1], (own[2] + bv.z) + cs[2], (own[3] + bv.w) + cs[3]};
             const float mx = fmaxf(fmaxf(sc[0], sc[1]), fmaxf(sc[2], sc[3]));
             float den = 0.f;
 #pragma unroll
             for (int i = 0; i < 4; ++i) { sc[i] = __expf(sc[i] - mx); den += sc[i]; }
             const float inv = 1.f / den;
-            float o[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = f0[e] * (sc[0] * inv);
+            float cf[13];
+            cf[0] = sc[0] * inv;
 #pragma unroll
             for (int l = 0; l < 3; ++l) {
                 const float al = sc[l + 1] * inv;
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float cf = al * tw[l][q];
-                    if constexpr (IsSplit<T>::value) {
-                        Chunk<T>::fma(tap[l][q], cf, o);      // both halves of every channel in mixed-precision fmas, no conversions
-                    } else {
-                        float f[4];
-                        Chunk<T>::unpack(tap[l][q], f);
+                for (int q = 0; q < 4; ++q) cf[1 + l * 4 + q] = al * tw[l][q];
+            }
+            // (3) blend the group's pixels
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) o[e] = fmaf(cf, f[e], o[e]);
+            for (int k = 0; k < ASF_G; ++k) {
+                const int yy = g0 + k;
+#pragma unroll
+                for (int l = 0; l < 3; ++l) {
+                    const int Hl = H >> (l + 1), Wl = W >> (l + 1);
+                    const int y0 = __builtin_amdgcn_readlane(ly0[l], yy);
+                    if (y0 != cy0[l]) {      // wave-uniform: the rows advance by one; request the row after the new bottom row
+                        tap[l][0] = tap[l][2]; tap[l][1] = tap[l][3];
+                        tap[l][2] = tap[l][4]; tap[l][3] = tap[l][5];
+                        const int row = min(y0 + 2, Hl - 1);
+                        tap[l][4] = *(const uint4*)(lev[l] + (size_t)(base[l] + row * Wl + cx0[l]) * 256 + lane * 4);
+                        tap[l][5] = *(const uint4*)(lev[l] + (size_t)(base[l] + row * Wl + cx1[l]) * 256 + lane * 4);
+                        cy0[l] = y0;
                     }
                 }
+                const float a0 = lane_value(cf[0], yy);
+                float o[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = f0[k][e] * a0;
+#pragma unroll
+                for (int l = 0; l < 3; ++l)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const float c = lane_value(cf[1 + l * 4 + q], yy);
+                        if constexpr (IsSplit<T>::value) {
+                            Chunk<T>::fma(tap[l][q], c, o);      // both halves of every channel in mixed-precision fmas, no conversions
+                        } else {
+                            float f[4];
+                            Chunk<T>::unpack(tap[l][q], f);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) o[e] = fmaf(c, f[e], o[e]);
+                        }
+                    }
+                *(uint4*)(ocol + (size_t)yy * rowstep) = Chunk<T>::pack(o);
             }
-            *(uint4*)(ocol + (size_t)yy * rowstep) = Chunk<T>::pack(o);
-        };
-#pragma unroll 1
-        for (int yy = 0; yy < rows; yy += 4) {      // unrolled by four so that the p2 ring has static slots
-            pixel(yy, ring[0]);
-            if (yy + 1 < rows) pixel(yy + 1, ring[1]);
-            if (yy + 2 < rows) pixel(yy + 2, ring[2]);
-            if (yy + 3 < rows) pixel(yy + 3, ring[3]);
         }
     }
 }
@@ -568,12 +623,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 template <typename T>
 static void asf_launch(const void* p2, const void* p3, const void* p4, const void* p5, const float* w, const float* b, float* s3, float* s4,
                        float* s5, void* out, int N, int H, int W, hipStream_t s) {
-    const void* lv[3] = {p3, p4, p5};
-    float* sv[3] = {s3, s4, s5};
-    for (int l = 0; l < 3; ++l) {
-        const size_t np = (size_t)N * (H >> (l + 1)) * (W >> (l + 1));
-        const int grid = (int)std::min<size_t>((np + 3) / 4, 2048);
-        hipLaunchKernelGGL(asf_scores_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)lv[l], w, sv[l], l + 1, np);
+    {
+        const size_t n3 = (size_t)N * (H >> 1) * (W >> 1), n4 = (size_t)N * (H >> 2) * (W >> 2), n5 = (size_t)N * (H >> 3) * (W >> 3);
+        const size_t chunks = (n3 + 3) / 4 + (n4 + 3) / 4 + (n5 + 3) / 4;
+        const int grid = (int)std::min<size_t>((chunks + 3) / 4, 2048);
+        hipLaunchKernelGGL(asf_scores_kernel<T>, dim3(grid), dim3(256), 0, s, (const T*)p3, (const T*)p4, (const T*)p5, w, s3, s4, s5, n3, n4, n5);
     }
     const size_t total = (size_t)N * H * W;
     const int grid = (int)std::min<size_t>(total / 64, 256 * 8);
