@@ -1030,7 +1030,7 @@ int ocrvi_test_stem_pool(int device, int dtype, const float* x, const float* wei
 int ocrvi_test_attention(int device, int dtype, const float* qkv, int B, int N, int heads, float* out, int iters,
                          float* avg_ms);
 
-/* The fused MixingBlock MLP of the 16-bit modes (svtrv2.py:28-39,100): x [M][D] float32 DEVICE, updated in place to
+/* The fused MixingBlock MLP of the 16-bit modes and of OCRVI_F16X2 (svtrv2.py:28-39,100): x [M][D] float32 DEVICE, updated in place to
  * x + fc2(gelu(fc1(LayerNorm(x; ln_g, ln_b)))); with want_xn also xn_out [M][D] float32 DEVICE = LayerNorm(x_new; next_g, next_b) rounded to
  * `dtype` (next_g == NULL: x_new rounded to `dtype`).  Weights and vectors are HOST float32 (fc1 [4D][D], fc2 [D][4D]).  D in {128, 256, 384}. */
 int ocrvi_test_mlp(int device, int dtype, float* x, const float* ln_g_host, const float* ln_b_host, const float* w1_host, const float* b1_host,
@@ -1042,6 +1042,13 @@ int ocrvi_test_mlp(int device, int dtype, float* x, const float* ln_g_host, cons
 int ocrvi_test_mlp_raw(int device, int dtype, float* x, const float* ln_g_host, const float* ln_b_host, const float* w1_host, const float* b1_host,
                        const float* w2_host, const float* b2_host, const float* next_g_host, const float* next_b_host, int M, int D, void* xn_raw,
                        float* xn_out, int iters, float* avg_ms);
+/* lin_x2_kernel (the token-stationary f16x2 Linear of the recogniser's qkv-type layers) on its own: out = a W^T + b in OCRVI_F16X2.
+ * a [M][K] float32 DEVICE (cast on the device), weight_host [N][K], bias_host [N] or NULL; K is 256 or 384, N % 32 == 0.  out [M][N] float32
+ * DEVICE: the f16x2 result decoded.  out_raw: NULL, or the caller's own DEVICE buffer of at least M rows of N * 4 bytes that the kernel
+ * writes directly (rows past M must come back untouched).  max_workgroups > 0 caps the grid, so that a workgroup walks several row tiles
+ * at small M.  iters > 0: avg_ms = mean time of `iters` launches. */
+int ocrvi_test_lin_x2(int device, const float* a, const float* weight_host, const float* bias_host, int M, int K, int N, int max_workgroups,
+                      void* out_raw, float* out, int iters, float* avg_ms);
 /* Host-only (no GPU): the OCRVI_F16X2 weight format.  src: n fp32 values of one layer (n % 4 == 0) -> dst: n 4-byte elements, per chunk of
  * 4 consecutive elements [hi0 hi1 hi2 hi3 | lo0 lo1 lo2 lo3] (fp16), hi + lo = src * 2^s with one power of two s per layer that puts the
  * largest magnitude into [2^13, 2^14); *wscale = 2^-s.  (What ocrvi_*_create does to every GEMM weight in that mode.) */

@@ -640,6 +640,31 @@ extern "C" int ocrvi_test_mlp_raw(int device, int dtype, float* x, const float* 
                          iters, avg_ms);
 }
 
+// lin_x2_kernel alone (lin_x2.hip), the pattern of test_gemm_impl: fp32 in, cast on the device; out_raw: the caller's own output buffer or null
+extern "C" int ocrvi_test_lin_x2(int device, const float* a, const float* weight_host, const float* bias_host, int M, int K, int N, int max_workgroups,
+                                 void* out_raw, float* out, int iters, float* avg_ms) {
+    OCRVI_CHECK(a && weight_host && out && M > 0, OCRVI_EINVAL, "test_lin_x2: bad argument");
+    OCRVI_CHECK(lin_x2_eligible(OCRVI_F16X2, K, N), OCRVI_EINVAL, "test_lin_x2: needs K in {256, 384} and N %% 32 == 0, N <= 2048 (got K %d, N %d)", K, N);
+    OCRVI_HIP(hipSetDevice(device));
+    Scratch sc;
+    OCRVI_TRY(sc.init());
+    DeviceStore st;
+    std::vector<char> packed;
+    pack_lin_x2_stream(weight_host, N, K, packed);
+    void* ws = nullptr;
+    float* b = nullptr;
+    OCRVI_TRY(st.upload(packed.data(), packed.size(), &ws));
+    if (bias_host) OCRVI_TRY(st.upload(bias_host, (size_t)N * 4, (void**)&b));
+    void *an = nullptr, *yn = out_raw;
+    OCRVI_TRY(sc.alloc((size_t)M * K * 4, &an));
+    if (!yn) OCRVI_TRY(sc.alloc((size_t)M * N * 4, &yn));
+    OCRVI_TRY(k_cast_from_f32(OCRVI_F16X2, a, an, (size_t)M * K, sc.s));
+    OCRVI_TRY(timed(sc, iters, avg_ms, [&]() { return k_lin_x2(an, ws, b, yn, M, K, N, sc.s, max_workgroups); }));
+    OCRVI_TRY(k_nhwc_to_nchw_f32(OCRVI_F16X2, yn, out, 1, 1, M * N, 1, 1, 0, sc.s));
+    OCRVI_HIP(hipStreamSynchronize(sc.s));
+    return OCRVI_OK;
+}
+
 // ---- the memory-bound kernels of kernels.hip, one hook each (no timing arguments: nothing benchmarks these)
 namespace {
 // [n] T -> float32 (same order): a C = 1 "NHWC -> NCHW" copy is a plain cast

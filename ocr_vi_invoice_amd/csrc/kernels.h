@@ -21,12 +21,19 @@ int k_layernorm(int dtype, const void* x, int x_f32, void* out, int out_f32, con
 // residual stream x [M][D]; when xn != null also writes xn [M][D] T = LN(x_new; next_g, next_b), or T(x_new) when next_g == null.
 // wstream = pack_mlp_stream(fc1.weight [4D][D], fc2.weight [D][4D]) uploaded to the device; b1 [4D], b2 [D] device fp32.
 bool mlp_fused_eligible(int dtype, int D);
-// f16x2, D = 128 / 256 (mlp_x2.hip): same contract; the stream carries its two weight scales behind the units
+// f16x2, D = 128 / 256 / 384 (mlp_x2.hip): same contract; the stream carries its two weight scales behind the units
 bool mlp_x2_eligible(int dtype, int D);
 void pack_mlp_x2_stream(const float* w1, const float* w2, int D, std::vector<char>& out);
 int k_mlp_x2(float* x, void* xn, const float* ln_g, const float* ln_b, const float* next_g, const float* next_b, const void* wstream, const float* b1,
              const float* b2, int M, int D, hipStream_t s);
 void pack_mlp_stream(const float* w1, const float* w2, int D, int dtype, std::vector<char>& out);
+// Token-stationary f16x2 Linear, K = 256 / 384, N % 32 == 0 (lin_x2.hip): out [M][N] f16x2 = a [M][K] f16x2 . W^T + bias, bit for bit what the
+// ring GEMM computes.  wstream = pack_lin_x2_stream(weight [N][K]) uploaded to the device (its weight scale rides behind the units); bias
+// [N] device fp32 or null.  lin_x2_eligible: by (dtype, K, N) only, and off together with mlp_x2 (OCRVI_MLP_X2=0).  max_workgroups > 0 caps
+// the grid (tests: a workgroup then walks several tiles at small M).
+bool lin_x2_eligible(int dtype, int K, int N);
+void pack_lin_x2_stream(const float* w, int N, int K, std::vector<char>& out);
+int k_lin_x2(const void* a, const void* wstream, const float* bias, void* out, int M, int K, int N, hipStream_t s, int max_workgroups = 0);
 int k_mlp_fused(int dtype, float* x, void* xn, const float* ln_g, const float* ln_b, const float* next_g, const float* next_b, const void* wstream,
                 const float* b1, const float* b2, int M, int D, hipStream_t s);
 // f32 -> T cast (n elements).

@@ -1,4 +1,4 @@
-// Fused MixingBlock MLP for the f16x2 mode, D = 128 / 256 (svtrv2.py:28-39,100):   x <- x + fc2(gelu(fc1(LayerNorm(x))))   [+ the NEXT LayerNorm]
+// Fused MixingBlock MLP for the f16x2 mode, D = 128 / 256 / 384 (svtrv2.py:28-39,100):   x <- x + fc2(gelu(fc1(LayerNorm(x))))   [+ the NEXT LayerNorm]
 //
 // The f16x2 counterpart of mlp_fused.hip, re-cut for operands that are twice as wide: unfused, the block is a LayerNorm launch and two
 // ring GEMMs whose 4 D hidden tensor makes a round trip through HBM (M x 4 D x 4 B written and read: 503 MB per 256 crops at D = 256).
@@ -14,7 +14,8 @@
 //     units runs ahead across chunk and tile boundaries, counted vmcnt, one barrier per unit;
 //   * epilogue: + bias + fp32 residual -> x; optionally LayerNorm of the result with the next block's norm1 (or a plain cast) -> xn (f16x2,
 //     range-checked), which removes that LayerNorm / cast kernel too.
-// D = 384 does not fit: the normalised rows and the output accumulators alone are 192 of a wave's 256 registers there.
+// D = 384 does not fit that cut -- the normalised rows and the output accumulators alone are 192 of a wave's 256 registers -- and runs as a
+// 4-wave build, 32 tokens per wave, one wave per SIMD with the whole register file (TB = 2, SPLIT: below).
 #include <stdlib.h>
 #include <string.h>
 

@@ -22,6 +22,7 @@ struct BlockW {
     LNw n1, n2;
     ConvLayer conv1, conv2;  // local
     ConvLayer qkv, proj;     // global
+    void* qkv_lin = nullptr; // f16x2, K = 256 / 384: qkv packed for the token-stationary Linear (lin_x2.hip)
     MlpW mlp;
 };
 }  // namespace
@@ -36,6 +37,7 @@ struct ocrvi_rec {
     LNw backbone_norm;
     LNw h_norm, h_norm2, v_norm_kv, v_norm2;
     ConvLayer h_qkv, h_proj, v_kv, v_proj, head;
+    void *h_qkv_lin = nullptr, *v_kv_lin = nullptr;   // as BlockW::qkv_lin
     MlpW h_mlp, v_mlp;
     float* vq = nullptr;
     // pointers into the last forward's workspace (debug taps)
@@ -49,6 +51,17 @@ static int load_ln(DeviceStore& st, const Blob& b, const std::string& name, int 
 }
 static int load_lin(DeviceStore& st, const Blob& b, const std::string& name, int cout, int cin, int dt, ConvLayer* L, const float* extra = nullptr) {
     return load_conv(st, b, name, cout, cin, 0, 1, AM_CONV1, dt, true, L, extra);
+}
+// A Linear without activation or residual whose output is T: also packed for lin_x2 where that kernel takes it (by dtype, K and N only; off
+// together with mlp_x2: OCRVI_MLP_X2=0 restores the ring launches).  *lin stays null otherwise.
+static int load_lin_x2(DeviceStore& st, const Blob& b, const std::string& name, int cout, int cin, int dt, ConvLayer* L, void** lin) {
+    OCRVI_TRY(load_lin(st, b, name, cout, cin, dt, L));
+    if (!lin_x2_eligible(dt, cin, cout)) return OCRVI_OK;
+    const BlobTensor* w = nullptr;
+    OCRVI_TRY(b.get(name + ".w", cout, cin, 0, 0, &w));
+    std::vector<char> packed;
+    pack_lin_x2_stream(w->data, cout, cin, packed);
+    return st.upload(packed.data(), packed.size(), lin);
 }
 static int load_mlp(DeviceStore& st, const Blob& b, const std::string& name, int d, int dt, MlpW* m) {
     OCRVI_TRY(load_lin(st, b, name + ".fc1", 4 * d, d, dt, &m->fc1));
@@ -104,7 +117,7 @@ extern "C" int ocrvi_rec_create(int device, const void* blob_p, size_t blob_byte
                 OCRVI_TRY(load_conv(st, blob, p + ".mixer.conv1", d, 32, 3, groups, AM_CONV3, dt, true, &bw.conv1));
                 OCRVI_TRY(load_conv(st, blob, p + ".mixer.conv2", d, 32, 3, groups, AM_CONV3, dt, true, &bw.conv2));
             } else {
-                OCRVI_TRY(load_lin(st, blob, p + ".mixer.qkv", 3 * d, d, dt, &bw.qkv));
+                OCRVI_TRY(load_lin_x2(st, blob, p + ".mixer.qkv", 3 * d, d, dt, &bw.qkv, &bw.qkv_lin));
                 OCRVI_TRY(load_lin(st, blob, p + ".mixer.proj", d, d, dt, &bw.proj));
             }
             OCRVI_TRY(load_mlp(st, blob, p + ".mlp", d, dt, &bw.mlp));
@@ -117,9 +130,9 @@ extern "C" int ocrvi_rec_create(int device, const void* blob_p, size_t blob_byte
     OCRVI_TRY(load_ln(st, blob, "frm.h_norm2", d, &h->h_norm2));
     OCRVI_TRY(load_ln(st, blob, "frm.v_norm_kv", d, &h->v_norm_kv));
     OCRVI_TRY(load_ln(st, blob, "frm.v_norm2", d, &h->v_norm2));
-    OCRVI_TRY(load_lin(st, blob, "frm.h_qkv", 3 * d, d, dt, &h->h_qkv));
+    OCRVI_TRY(load_lin_x2(st, blob, "frm.h_qkv", 3 * d, d, dt, &h->h_qkv, &h->h_qkv_lin));
     OCRVI_TRY(load_lin(st, blob, "frm.h_proj", d, d, dt, &h->h_proj));
-    OCRVI_TRY(load_lin(st, blob, "frm.v_kv", 2 * d, d, dt, &h->v_kv));
+    OCRVI_TRY(load_lin_x2(st, blob, "frm.v_kv", 2 * d, d, dt, &h->v_kv, &h->v_kv_lin));
     // t_q + v_proj(out): the residual t_q is the (input-independent) select token -> fold it into the bias (svtrv2.py:226,244)
     const BlobTensor* tok = nullptr;
     OCRVI_TRY(blob.get("frm.select_token", d, 0, 0, 0, &tok));
@@ -158,6 +171,12 @@ static int ln(Runner& r, const Tensor& x, const Tensor& y, const LNw& w) {
     return k_layernorm(r.dtype, x.p, x.f32, y.p, y.f32, w.g, w.b, (int)x.pixels(), x.c, r.stream);
 }
 static Tensor view(const Tensor& t, int n, int h, int w, int c) { return wrap(t.p, n, h, w, c, t.f32); }
+// y = x W^T + b, both T: lin_x2 where the loader packed the layer for it, the conv family otherwise
+static int linear(Runner& r, const ConvLayer& L, void* lin, const Tensor& x, const Tensor& y) {
+    if (!lin) return conv(r, L, x, y, ConvOpts());
+    if (r.dry()) return OCRVI_OK;
+    return k_lin_x2(x.p, lin, L.bias, y.p, (int)x.pixels(), x.c, y.c, r.stream);
+}
 // Multi-head self-attention over `seqs` sequences of `len` tokens, qkv -> out.  Sequences beyond 512 keys in the 4-byte modes go through
 // per-chunk partial rows that are merged: their scratch comes from the arena for the duration of the call.
 static int attention(Runner& r, const Tensor& qkv, const Tensor& out, int seqs, int len, int heads) {
@@ -250,7 +269,7 @@ static int rec_run(ocrvi_rec* h, Runner& r, const float* x, int B, int H, int W,
                 OCRVI_TRY(conv(r, bw.conv2, t1, xs, o));
             } else {  // x + proj(MHSA(qkv(LN x)))  (svtrv2.py:77-86,98)
                 ConvOpts o;
-                OCRVI_TRY(conv(r, bw.qkv, view(xn, rows, 1, 1, d), view(big, rows, 1, 1, 3 * d), o));
+                OCRVI_TRY(linear(r, bw.qkv, bw.qkv_lin, view(xn, rows, 1, 1, d), view(big, rows, 1, 1, 3 * d)));
                 OCRVI_TRY(attention(r, big, t1, B, Hs * Ws, d / 32));
                 o.res = &xs; o.res_mode = RES_SAME;
                 OCRVI_TRY(conv(r, bw.proj, view(t1, rows, 1, 1, d), view(xs, rows, 1, 1, d), o));
@@ -284,7 +303,7 @@ static int rec_run(ocrvi_rec* h, Runner& r, const float* x, int B, int H, int W,
     OCRVI_TRY(ln(r, bn, xn, h->h_norm));
     {
         ConvOpts o;
-        OCRVI_TRY(conv(r, h->h_qkv, xn, view(big, rows, 1, 1, 3 * d2), o));
+        OCRVI_TRY(linear(r, h->h_qkv, h->h_qkv_lin, xn, view(big, rows, 1, 1, 3 * d2)));
         OCRVI_TRY(attention(r, big, t1, B * Hs, Ws, d2 / 32));  // one sequence per image row
         o.res = &bn; o.res_mode = RES_SAME;
         OCRVI_TRY(conv(r, h->h_proj, t1, xr, o));
@@ -297,7 +316,7 @@ static int rec_run(ocrvi_rec* h, Runner& r, const float* x, int B, int H, int W,
     const Tensor tq = wrap(r.arena.alloc((size_t)cols * d2 * 4), cols, 1, 1, d2, true);
     {
         ConvOpts o;
-        OCRVI_TRY(conv(r, h->v_kv, xn, view(big, rows, 1, 1, 2 * d2), o));
+        OCRVI_TRY(linear(r, h->v_kv, h->v_kv_lin, xn, view(big, rows, 1, 1, 2 * d2)));
         if (!r.dry()) OCRVI_TRY(k_frm_vertical(dt, big.p, h->vq, t1.p, B, Hs, Ws, d2, r.stream));
         OCRVI_TRY(conv(r, h->v_proj, view(t1, cols, 1, 1, d2), tq, o));  // bias carries + select_token
     }

@@ -61,7 +61,7 @@ def touches_before_wait(body, start, dst):
     return hits
 
 
-ALL_SOURCES = ["conv_bf16.hip", "conv_f16.hip", "conv_f32.hip", "conv_f16x2.hip", "mlp_fused.hip", "attention.hip", "stem_pool.hip", "mlp_x2.hip", "bneck_tail.hip"]
+ALL_SOURCES = ["conv_bf16.hip", "conv_f16.hip", "conv_f32.hip", "conv_f16x2.hip", "mlp_fused.hip", "attention.hip", "stem_pool.hip", "mlp_x2.hip", "bneck_tail.hip", "lin_x2.hip"]
 _ASM = {}
 
 
@@ -218,6 +218,53 @@ def check_bneck_tail(src="bneck_tail.hip"):
         rep[name] = dict(scratch=sum("scratch_" in t for t, _ in ins), vgprs=int(v.group(1)) if v else -1, exposed_waits=exposed,
                          mfma_a=sum(t.startswith("v_mfma") for t in span_a), mfma_bc=sum(t.startswith("v_mfma") for t in span_bc),
                          asm_loads=len(loads), touches=touches, compiler_vmcnt_waits=cwaits)
+    return rep
+
+
+def check_lin_x2(src="lin_x2.hip"):
+    """The token-stationary f16x2 Linear (lin_x2.hip) counts the vmcnt of its weight ring and of its stores by hand and reads its weight
+    fragments two K-steps ahead.  name -> dict for every `lin_x2_kernel` build, the unit loop being the instructions at loop depth >= 2:
+      scratch, vgprs        spill instructions in the whole kernel (an uncounted VMEM operation inside the protocol); the register count;
+      mfma, stores, counted_waits   MFMA, buffer-store and inline-asm `s_waitcnt vmcnt` instructions of the unit loop;
+      exposed_waits         `s_waitcnt lgkmcnt(0)` directly behind a fragment `ds_read` in the unit loop;
+      compiler_vmcnt_waits  hipcc's own vmcnt waits in the unit loop (between the ring's counted waits they would drain it)."""
+    txt = asm_of(src)
+    lines = txt.split("\n")
+    rep = {}
+    for i, l in enumerate(lines):
+        m = re.match(r"(_ZN5ocrvi13lin_x2_kernel\w*):", l)
+        if not m:
+            continue
+        name, depth, inasm, loop, scratch = m.group(1), 0, False, [], 0
+        for t in lines[i + 1:]:
+            if t.strip().startswith(".Lfunc_end"):
+                break
+            d = re.search(r"Depth=(\d+)", t)
+            if re.match(r"\s*(\.LBB\w+:|; %bb\.\d+:)", t):
+                depth = int(d.group(1)) if d else 0
+                continue
+            if d and t.strip().startswith(";"):   # (a loop header's own depth can sit on the comment line after its label)
+                depth = int(d.group(1))
+                continue
+            if "#ASMSTART" in t:
+                inasm = True
+                continue
+            if "#ASMEND" in t:
+                inasm = False
+                continue
+            body = t.split(";")[0].strip()
+            if not body or body.startswith("."):
+                continue
+            scratch += "scratch_" in body
+            if depth >= 2:
+                loop.append((body, inasm))
+        ins = [t for t, _ in loop]
+        v = re.search(r"\.name:\s+" + re.escape(name) + r"\n(?:(?!\.name:).*\n)*?\s*\.vgpr_count:\s*(\d+)", txt)
+        rep[name] = dict(scratch=scratch, vgprs=int(v.group(1)) if v else -1, mfma=sum(t.startswith("v_mfma") for t in ins),
+                         stores=sum(t.startswith("buffer_store") for t in ins),
+                         counted_waits=sum(a and t.startswith("s_waitcnt vmcnt") for t, a in loop),
+                         exposed_waits=sum(1 for x, y in zip(ins, ins[1:]) if x.startswith("ds_read") and re.match(r"s_waitcnt lgkmcnt\(0\)\s*$", y)),
+                         compiler_vmcnt_waits=[t for t, a in loop if not a and t.startswith("s_waitcnt") and "vmcnt" in t])
     return rep
 
 
