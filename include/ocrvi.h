@@ -130,6 +130,14 @@ int ocrvi_rec_workspace_bytes(const ocrvi_rec* h, int B, int H, int W, size_t* b
 int ocrvi_rec_forward(ocrvi_rec* h, const float* x, int B, int H, int W,
                       float* log_probs, int32_t* argmax_ids, int32_t* ids, int32_t* lens,
                       void* workspace, size_t workspace_bytes, void* stream);
+/* ocrvi_rec_forward with the confidence outputs of ocrvi_ctc_greedy_conf (defined there): best_lp [B,T] float32, char_lp [B,T] float32,
+ * char_span [B,T,2] int32, computed from the log-probabilities this forward produces whether or not log_probs is stored.  Any output may be
+ * NULL; log_probs, argmax_ids, ids and lens are bit-equal to what ocrvi_rec_forward writes for the same input.  Same workspace as
+ * ocrvi_rec_forward (ocrvi_rec_workspace_bytes); enqueue-only, so it can be captured into a graph. */
+int ocrvi_rec_forward_conf(ocrvi_rec* h, const float* x, int B, int H, int W,
+                           float* log_probs, int32_t* argmax_ids, int32_t* ids, int32_t* lens,
+                           float* best_lp, float* char_lp, int32_t* char_span,
+                           void* workspace, size_t workspace_bytes, void* stream);
 /* Test hook: float32 copies of backbone_norm output [B, H/16*W/4, D] (svtrv2.py:500) and FRM output
  * [B, W/4, D] (svtrv2.py:247).  Either may be NULL.  Must follow a forward on the same workspace/stream. */
 int ocrvi_rec_status(const ocrvi_rec* h);   /* as ocrvi_det_status */
@@ -144,6 +152,19 @@ int ocrvi_range_flag(int device, int* raised);
  * (svtrv2.py:555-566).  log_probs [T,B,C] float32 on device. */
 int ocrvi_ctc_greedy(int device, const float* log_probs, int T, int B, int C, int blank_id,
                      int32_t* argmax_ids, int32_t* ids, int32_t* lens, void* stream);
+
+/* ocrvi_ctc_greedy with confidences: how sure the greedy path was of each character it kept, and which steps the character covers.
+ * argmax_ids, ids and lens are exactly what ocrvi_ctc_greedy writes.  argmax_ids and best_lp are required, the rest may be NULL.
+ *   best_lp [B,T] float32, laid out like argmax_ids: best_lp[b,t] is the float32 that log_probs[t,b,argmax_ids[b,t]] holds, bit for bit
+ *     (for a step whose log-probs are NaN the argmax is 0 and best_lp is that NaN).
+ *   Character k of row b, 0 <= k < lens[b], is emitted at step t0, the k-th step with am[t0] != blank_id && am[t0] != am[t0-1] (am =
+ *     argmax_ids[b]; step 0 has no predecessor).  Its run is [t0, t1], t1 the last step such that am[t0..t1] are all equal.
+ *   char_span [B,T,2] int32: (t0, t1) of character k; (-1, -1) for k >= lens[b].
+ *   char_lp [B,T] float32: the maximum of best_lp[b, t0..t1] under fmaxf, so a NaN step is ignored unless every step of the run is NaN;
+ *     -inf for k >= lens[b].
+ * One wave per row, 64 steps per pass; a run that crosses a pass boundary is carried in registers and stored once, when it closes. */
+int ocrvi_ctc_greedy_conf(int device, const float* log_probs, int T, int B, int C, int blank_id,
+                          int32_t* argmax_ids, int32_t* ids, int32_t* lens, float* best_lp, float* char_lp, int32_t* char_span, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Pre-processing on the device (the callers either side of the two models on the e2e path).
@@ -1078,6 +1099,10 @@ int ocrvi_test_db_maps(int device, const float* bin_logits, const float* thresh_
  * C classes into log_probs [T][B][C] and its per-step argmax into argmax_ids [B][T] (first index wins ties; 0 for a row whose log-probs
  * are NaN, as ocrvi_ctc_greedy gives).  Either output may be NULL.  C <= 1024, ld >= C. */
 int ocrvi_test_ctc_logsoftmax(int device, const float* logits, int ld, int B, int T, int C, float* log_probs, int32_t* argmax_ids);
+/* The same head as ocrvi_rec_forward_conf launches it: also best_lp [B][T], the float32 log_probs[t][b][argmax_ids[b][t]] bit for bit (the
+ * NaN of entry 0 for a NaN row).  Any output may be NULL. */
+int ocrvi_test_ctc_logsoftmax_conf(int device, const float* logits, int ld, int B, int T, int C, float* log_probs, int32_t* argmax_ids,
+                                   float* best_lp);
 
 /* ------------------------------------------------------------------------------------------------
  * Document finder: the corners that four-point rectification takes, found from the page (find_document_contour_dl,

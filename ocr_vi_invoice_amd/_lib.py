@@ -49,6 +49,7 @@ EXPORTS = [
     "ocrvi_png_encode_sizes", "ocrvi_png_encode_table_entry", "ocrvi_png_encode_pages", "ocrvi_test_png_code_lengths",
     "ocrvi_document_contour", "ocrvi_document_contour_bits", "ocrvi_doc_working_size", "ocrvi_doc_mask_sizes", "ocrvi_doc_mask_pages",
     "ocrvi_doc_grey_u8", "ocrvi_doc_smooth_u8", "ocrvi_doc_histogram", "ocrvi_doc_otsu", "ocrvi_doc_mask_bits",
+    "ocrvi_rec_forward_conf", "ocrvi_ctc_greedy_conf", "ocrvi_test_ctc_logsoftmax_conf",
 ]
 PAGE_ENTRY = 4          # int64 fields of one page-table entry: (device address, height, width, 0) -- OCRVI_PAGE_ENTRY
 # ocrvi_det_eval's record: 13 slots of 8 bytes (OCRVI_DET_EVAL_*), the first six int64, the rest float64
@@ -136,6 +137,9 @@ def load() -> C.CDLL:
     lib.ocrvi_rec_forward.argtypes = [vp, f32p, i32, i32, i32, f32p, i32p, i32p, i32p, vp, sz, vp]
     lib.ocrvi_rec_debug_features.argtypes = [vp, i32, i32, i32, f32p, f32p, vp, sz, vp]
     lib.ocrvi_ctc_greedy.argtypes = [i32, f32p, i32, i32, i32, i32, i32p, i32p, i32p, vp]
+    lib.ocrvi_rec_forward_conf.argtypes = [vp, f32p, i32, i32, i32, f32p, i32p, i32p, i32p, f32p, f32p, i32p, vp, sz, vp]
+    lib.ocrvi_ctc_greedy_conf.argtypes = [i32, f32p, i32, i32, i32, i32, i32p, i32p, i32p, f32p, f32p, i32p, vp]
+    lib.ocrvi_test_ctc_logsoftmax_conf.argtypes = [i32, f32p, i32, i32, i32, i32, f32p, i32p, f32p]
     lib.ocrvi_normalize_u8.argtypes = [i32, vp, i32, i32, i32, f32p, vp]
     lib.ocrvi_resize_u8.argtypes = [i32, vp, i32, i32, vp, i32, i32, vp]
     lib.ocrvi_crop_resize_normalize.argtypes = [i32, vp, i32, i32, i32, i32p, i32, i32, i32, f32p, vp]

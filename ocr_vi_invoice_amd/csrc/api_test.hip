@@ -781,3 +781,13 @@ extern "C" int ocrvi_test_ctc_logsoftmax(int device, const float* logits, int ld
     OCRVI_HIP(hipStreamSynchronize(sc.s));
     return OCRVI_OK;
 }
+
+extern "C" int ocrvi_test_ctc_logsoftmax_conf(int device, const float* logits, int ld, int B, int T, int C, float* log_probs,
+                                              int32_t* argmax_ids, float* best_lp) {
+    OCRVI_HIP(hipSetDevice(device));
+    Scratch sc;
+    OCRVI_TRY(sc.init());
+    OCRVI_TRY(k_ctc_logsoftmax_argmax_conf(logits, ld, log_probs, argmax_ids, best_lp, B, T, C, sc.s));
+    OCRVI_HIP(hipStreamSynchronize(sc.s));
+    return OCRVI_OK;
+}

@@ -65,5 +65,12 @@ int k_ctc_logsoftmax_argmax(const float* logits, int ld, float* log_probs, int32
 int k_ctc_argmax_tbc(const float* log_probs, int32_t* argmax_ids, int B, int T, int C, hipStream_t s);
 // argmax [B][T] -> collapsed ids [B][T] (-1 padded) + lens [B] (svtrv2.py:559-566)
 int k_ctc_collapse(const int32_t* argmax_ids, int32_t* ids, int32_t* lens, int B, int T, int blank, hipStream_t s);
+// The same three with confidences (include/ocrvi.h, ocrvi_ctc_greedy_conf): best_lp f32 [B][T] (nullable in the first two) is the winning
+// log-probability of each step; the collapse reads it and adds char_lp f32 [B][T] and char_span int32 [B][T][2] (every output nullable).
+int k_ctc_logsoftmax_argmax_conf(const float* logits, int ld, float* log_probs, int32_t* argmax_ids, float* best_lp, int B, int T, int C,
+                                 hipStream_t s);
+int k_ctc_argmax_tbc_conf(const float* log_probs, int32_t* argmax_ids, float* best_lp, int B, int T, int C, hipStream_t s);
+int k_ctc_collapse_conf(const int32_t* argmax_ids, const float* best_lp, int32_t* ids, int32_t* lens, float* char_lp, int32_t* char_span, int B,
+                        int T, int blank, hipStream_t s);
 
 }  // namespace ocrvi

@@ -692,8 +692,10 @@ __device__ __forceinline__ void wave_argmax(float& v, int& idx) {
     }
 }
 
-__global__ void ctc_logsoftmax_argmax_kernel(const float* __restrict__ logits, int ld, float* __restrict__ log_probs,
-                                             int32_t* __restrict__ argmax_ids, int B, int T, int C) {
+// kConf also writes best_lp[b][t], the log-probability the argmax won with: the float32 log_probs[t][b][argmax_ids[b][t]] holds, bit for bit
+template <bool kConf>
+__device__ __forceinline__ void ctc_logsoftmax_argmax_row(const float* __restrict__ logits, int ld, float* __restrict__ log_probs,
+                                                          int32_t* __restrict__ argmax_ids, float* __restrict__ best_lp, int B, int T, int C) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);  // b*T + t
     if (row >= B * T) return;
@@ -730,6 +732,16 @@ __global__ void ctc_logsoftmax_argmax_kernel(const float* __restrict__ logits, i
     // a row whose log-probs are NaN (a NaN or +inf logit, or nothing but -inf) leaves every lane without a candidate: index 0, the rule of
     // ctc_argmax_tbc_kernel below and what torch.log_softmax(..).argmax(-1) gives -- never an id outside [0, C)
     if (argmax_ids && lane == 0) argmax_ids[(size_t)b * T + t] = bi == 0x7fffffff ? 0 : bi;
+    // (best, bi) travel together, so best is the value at bi; a NaN row has no winner and reports its entry 0, which lane 0 holds in v[0]
+    if (kConf && best_lp && lane == 0) best_lp[(size_t)b * T + t] = bi == 0x7fffffff ? (v[0] - mx) - lse : best;
+}
+__global__ void ctc_logsoftmax_argmax_kernel(const float* __restrict__ logits, int ld, float* __restrict__ log_probs,
+                                             int32_t* __restrict__ argmax_ids, int B, int T, int C) {
+    ctc_logsoftmax_argmax_row<false>(logits, ld, log_probs, argmax_ids, nullptr, B, T, C);
+}
+__global__ void ctc_logsoftmax_argmax_conf_kernel(const float* __restrict__ logits, int ld, float* __restrict__ log_probs,
+                                                  int32_t* __restrict__ argmax_ids, float* __restrict__ best_lp, int B, int T, int C) {
+    ctc_logsoftmax_argmax_row<true>(logits, ld, log_probs, argmax_ids, best_lp, B, T, C);
 }
 int k_ctc_logsoftmax_argmax(const float* logits, int ld, float* log_probs, int32_t* argmax_ids, int B, int T, int C, hipStream_t s) {
     OCRVI_CHECK(logits && B > 0 && T > 0 && C > 0 && C <= 1024 && ld >= C, OCRVI_EINVAL, "ctc: bad shape B=%d T=%d C=%d", B, T, C);
@@ -738,8 +750,19 @@ int k_ctc_logsoftmax_argmax(const float* logits, int ld, float* log_probs, int32
     OCRVI_HIP(hipGetLastError());
     return OCRVI_OK;
 }
+int k_ctc_logsoftmax_argmax_conf(const float* logits, int ld, float* log_probs, int32_t* argmax_ids, float* best_lp, int B, int T, int C,
+                                 hipStream_t s) {
+    OCRVI_CHECK(logits && B > 0 && T > 0 && C > 0 && C <= 1024 && ld >= C, OCRVI_EINVAL, "ctc: bad shape B=%d T=%d C=%d", B, T, C);
+    ProfScope ps_("ctc_logsoftmax_argmax_conf", 0.0, (double)B*T*C*(log_probs?8.0:4.0), s);
+    hipLaunchKernelGGL(ctc_logsoftmax_argmax_conf_kernel, dim3(cdiv(B * T, 4)), dim3(256), 0, s, logits, ld, log_probs, argmax_ids, best_lp,
+                       B, T, C);
+    OCRVI_HIP(hipGetLastError());
+    return OCRVI_OK;
+}
 
-__global__ void ctc_argmax_tbc_kernel(const float* __restrict__ lp, int32_t* __restrict__ argmax_ids, int B, int T, int C) {
+template <bool kConf>
+__device__ __forceinline__ void ctc_argmax_tbc_row(const float* __restrict__ lp, int32_t* __restrict__ argmax_ids, float* __restrict__ best_lp,
+                                                   int B, int T, int C) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);  // t*B + b
     if (row >= B * T) return;
@@ -754,11 +777,28 @@ __global__ void ctc_argmax_tbc_kernel(const float* __restrict__ lp, int32_t* __r
     }
     if (bi == 0x7fffffff && !any_nan) bi = lane < C ? lane : 0x7fffffff;  // all -inf: first index
     wave_argmax(best, bi);
-    if (lane == 0) argmax_ids[(size_t)b * T + t] = bi == 0x7fffffff ? 0 : bi;
+    if (lane == 0) {
+        const int id = bi == 0x7fffffff ? 0 : bi;
+        argmax_ids[(size_t)b * T + t] = id;
+        if (kConf && best_lp) best_lp[(size_t)b * T + t] = lp[(size_t)row * C + id];  // the input itself, so a NaN row reports its own NaN
+    }
+}
+__global__ void ctc_argmax_tbc_kernel(const float* __restrict__ lp, int32_t* __restrict__ argmax_ids, int B, int T, int C) {
+    ctc_argmax_tbc_row<false>(lp, argmax_ids, nullptr, B, T, C);
+}
+__global__ void ctc_argmax_tbc_conf_kernel(const float* __restrict__ lp, int32_t* __restrict__ argmax_ids, float* __restrict__ best_lp, int B,
+                                           int T, int C) {
+    ctc_argmax_tbc_row<true>(lp, argmax_ids, best_lp, B, T, C);
 }
 int k_ctc_argmax_tbc(const float* log_probs, int32_t* argmax_ids, int B, int T, int C, hipStream_t s) {
     OCRVI_CHECK(log_probs && argmax_ids && B > 0 && T > 0 && C > 0, OCRVI_EINVAL, "ctc argmax: bad shape");
     hipLaunchKernelGGL(ctc_argmax_tbc_kernel, dim3(cdiv(B * T, 4)), dim3(256), 0, s, log_probs, argmax_ids, B, T, C);
+    OCRVI_HIP(hipGetLastError());
+    return OCRVI_OK;
+}
+int k_ctc_argmax_tbc_conf(const float* log_probs, int32_t* argmax_ids, float* best_lp, int B, int T, int C, hipStream_t s) {
+    OCRVI_CHECK(log_probs && argmax_ids && B > 0 && T > 0 && C > 0, OCRVI_EINVAL, "ctc argmax: bad shape");
+    hipLaunchKernelGGL(ctc_argmax_tbc_conf_kernel, dim3(cdiv(B * T, 4)), dim3(256), 0, s, log_probs, argmax_ids, best_lp, B, T, C);
     OCRVI_HIP(hipGetLastError());
     return OCRVI_OK;
 }
@@ -788,6 +828,92 @@ __global__ void ctc_collapse_kernel(const int32_t* __restrict__ am, int32_t* __r
 int k_ctc_collapse(const int32_t* argmax_ids, int32_t* ids, int32_t* lens, int B, int T, int blank, hipStream_t s) {
     OCRVI_CHECK(argmax_ids && B > 0 && T > 0, OCRVI_EINVAL, "ctc collapse: bad shape");
     hipLaunchKernelGGL(ctc_collapse_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, argmax_ids, ids, lens, B, T, blank);
+    OCRVI_HIP(hipGetLastError());
+    return OCRVI_OK;
+}
+
+// ctc_collapse_kernel plus one record per kept character k: its run [t0, t1] of equal argmax ids into char_span[b][k] and the fmaxf of best_lp
+// over the run into char_lp[b][k].  A run is a contiguous range of lanes: run index = inclusive count of run starts, maximum = segmented suffix
+// maximum by doubling.  A run still open at lane 63 is carried to the next pass in wave-uniform registers (character index, t0, running
+// maximum) and stored once, when it closes: no record is ever read back from memory.
+__global__ void ctc_collapse_conf_kernel(const int32_t* __restrict__ am, const float* __restrict__ best_lp, int32_t* __restrict__ ids,
+                                         int32_t* __restrict__ lens, float* __restrict__ char_lp, int32_t* __restrict__ char_span, int B, int T,
+                                         int blank) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int32_t* a = am + (size_t)b * T;
+    const float* lp = best_lp + (size_t)b * T;
+    int32_t* o = ids ? ids + (size_t)b * T : nullptr;
+    float* olp = char_lp ? char_lp + (size_t)b * T : nullptr;
+    int32_t* osp = char_span ? char_span + (size_t)b * T * 2 : nullptr;
+    int count = 0;
+    bool open = false;  // the carry: a kept character whose run reached the end of the last pass
+    int open_k = 0, open_t0 = 0;
+    float open_mx = 0.f;
+    for (int tb = 0; tb < T; tb += 64) {
+        const int t = tb + lane;
+        const int cur = t < T ? a[t] : blank;
+        const int prev = (t > 0 && t < T) ? a[t - 1] : -1;
+        const bool start = t >= T || cur != prev;  // a step past the end closes whatever runs into it
+        const bool keep = t < T && cur != blank && cur != prev;
+        const unsigned long long smask = __ballot(start), kmask = __ballot(keep);
+        const unsigned long long below = (1ull << lane) - 1ull, above = ~(below | (1ull << lane));
+        const int run = __popcll(smask & (below | (1ull << lane)));
+        float m = t < T ? lp[t] : -INFINITY;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const float om = __shfl_down(m, d);
+            const int orun = __shfl_down(run, d);
+            if (lane + d < 64 && orun == run) m = fmaxf(m, om);
+        }
+        const int first = smask ? __ffsll((long long)smask) - 1 : 64;  // lanes below `first` continue the carried run
+        if (open) {
+            if (first > 0) open_mx = fmaxf(open_mx, __shfl(m, 0));
+            if (first < 64) {
+                if (lane == 0) {
+                    if (olp) olp[open_k] = open_mx;
+                    if (osp) { osp[2 * open_k] = open_t0; osp[2 * open_k + 1] = tb + first - 1; }
+                }
+                open = false;
+            }
+        }
+        const int pos = count + __popcll(kmask & below);
+        const unsigned long long later = smask & above;
+        if (keep) {
+            if (o) o[pos] = cur;
+            if (later) {  // the run closes inside this pass, one step before the next start
+                if (olp) olp[pos] = m;
+                if (osp) { osp[2 * pos] = t; osp[2 * pos + 1] = tb + __ffsll((long long)later) - 2; }
+            }
+        }
+        if (smask) {
+            const int last = 63 - __clzll((long long)smask);
+            if ((kmask >> last) & 1ull) {  // the last run of this pass is a character and runs through lane 63
+                open = true;
+                open_k = __shfl(pos, last);
+                open_t0 = tb + last;
+                open_mx = __shfl(m, last);
+            }
+        }
+        count += __popcll(kmask);
+    }
+    if (open && lane == 0) {  // T is a multiple of 64 and the last run ends with the sequence
+        if (olp) olp[open_k] = open_mx;
+        if (osp) { osp[2 * open_k] = open_t0; osp[2 * open_k + 1] = T - 1; }
+    }
+    for (int k = count + lane; k < T; k += 64) {
+        if (o) o[k] = -1;
+        if (olp) olp[k] = -INFINITY;
+        if (osp) { osp[2 * k] = -1; osp[2 * k + 1] = -1; }
+    }
+    if (lens && lane == 0) lens[b] = count;
+}
+int k_ctc_collapse_conf(const int32_t* argmax_ids, const float* best_lp, int32_t* ids, int32_t* lens, float* char_lp, int32_t* char_span, int B,
+                        int T, int blank, hipStream_t s) {
+    OCRVI_CHECK(argmax_ids && best_lp && B > 0 && T > 0, OCRVI_EINVAL, "ctc collapse: bad shape");
+    hipLaunchKernelGGL(ctc_collapse_conf_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, argmax_ids, best_lp, ids, lens, char_lp, char_span, B, T,
+                       blank);
     OCRVI_HIP(hipGetLastError());
     return OCRVI_OK;
 }

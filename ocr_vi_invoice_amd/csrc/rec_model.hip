@@ -210,8 +210,16 @@ static int mlp_block(Runner& r, const Tensor& x, const Tensor& xn, const Tensor&
     return conv(r, m.fc2, view(hb, rows, 1, 1, 4 * d), view(x, rows, 1, 1, d), o2);
 }
 
+// The confidence outputs (ocrvi_rec_forward_conf): with all three null the decode head launches exactly what it always has.
+struct RecConf {
+    float* best_lp = nullptr;
+    float* char_lp = nullptr;
+    int32_t* char_span = nullptr;
+    bool any() const { return best_lp || char_lp || char_span; }
+};
+
 static int rec_run(ocrvi_rec* h, Runner& r, const float* x, int B, int H, int W, float* log_probs, int32_t* argmax_ids, int32_t* ids,
-                   int32_t* lens) {
+                   int32_t* lens, const RecConf& conf = RecConf()) {
     const ocrvi_rec_cfg& c = h->cfg;
     const int dt = c.dtype;
     const bool lowp = dt != OCRVI_F32;
@@ -333,10 +341,19 @@ static int rec_run(ocrvi_rec* h, Runner& r, const float* x, int B, int H, int W,
         ConvOpts o;
         OCRVI_TRY(conv(r, h->head, hin, logits, o));
     }
+    // (allocated last, so every other buffer keeps its offset; the size query plans it whether or not a caller asks for confidences)
+    float* blp_buf = (float*)r.arena.alloc((size_t)B * T * 4);
     if (!r.dry()) {
         int32_t* am = argmax_ids ? argmax_ids : am_buf;
-        OCRVI_TRY(k_ctc_logsoftmax_argmax((const float*)logits.p, c.num_classes, log_probs, am, B, T, c.num_classes, r.stream));
-        if (ids || lens) OCRVI_TRY(k_ctc_collapse(am, ids, lens, B, T, c.blank_id, r.stream));
+        if (conf.any()) {
+            float* blp = conf.best_lp ? conf.best_lp : blp_buf;
+            OCRVI_TRY(k_ctc_logsoftmax_argmax_conf((const float*)logits.p, c.num_classes, log_probs, am, blp, B, T, c.num_classes, r.stream));
+            if (ids || lens || conf.char_lp || conf.char_span)
+                OCRVI_TRY(k_ctc_collapse_conf(am, blp, ids, lens, conf.char_lp, conf.char_span, B, T, c.blank_id, r.stream));
+        } else {
+            OCRVI_TRY(k_ctc_logsoftmax_argmax((const float*)logits.p, c.num_classes, log_probs, am, B, T, c.num_classes, r.stream));
+            if (ids || lens) OCRVI_TRY(k_ctc_collapse(am, ids, lens, B, T, c.blank_id, r.stream));
+        }
     }
     return OCRVI_OK;
 }
@@ -352,6 +369,16 @@ extern "C" int ocrvi_rec_forward(ocrvi_rec* h, const float* x, int B, int H, int
     return run_forward("rec_forward", h, x && workspace, "null input/workspace", workspace, workspace_bytes, stream,
                        [&] { return check_rec_shape(h, B, H, W); },
                        [&](Runner& r) { return rec_run(h, r, x, B, H, W, log_probs, argmax_ids, ids, lens); });
+}
+
+extern "C" int ocrvi_rec_forward_conf(ocrvi_rec* h, const float* x, int B, int H, int W, float* log_probs, int32_t* argmax_ids, int32_t* ids,
+                                      int32_t* lens, float* best_lp, float* char_lp, int32_t* char_span, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+    RecConf conf;
+    conf.best_lp = best_lp; conf.char_lp = char_lp; conf.char_span = char_span;
+    return run_forward("rec_forward_conf", h, x && workspace, "null input/workspace", workspace, workspace_bytes, stream,
+                       [&] { return check_rec_shape(h, B, H, W); },
+                       [&](Runner& r) { return rec_run(h, r, x, B, H, W, log_probs, argmax_ids, ids, lens, conf); });
 }
 
 extern "C" int ocrvi_rec_status(const ocrvi_rec* h) {
@@ -380,5 +407,16 @@ extern "C" int ocrvi_ctc_greedy(int device, const float* log_probs, int T, int B
     OCRVI_HIP(dg.err);
     OCRVI_TRY(k_ctc_argmax_tbc(log_probs, argmax_ids, B, T, C, (hipStream_t)stream));
     if (ids || lens) OCRVI_TRY(k_ctc_collapse(argmax_ids, ids, lens, B, T, blank_id, (hipStream_t)stream));
+    return OCRVI_OK;
+}
+
+extern "C" int ocrvi_ctc_greedy_conf(int device, const float* log_probs, int T, int B, int C, int blank_id, int32_t* argmax_ids, int32_t* ids,
+                                     int32_t* lens, float* best_lp, float* char_lp, int32_t* char_span, void* stream) {
+    OCRVI_CHECK(log_probs && argmax_ids && best_lp, OCRVI_EINVAL, "ctc_greedy_conf: log_probs, argmax_ids and best_lp are required");
+    DeviceGuard dg(device);
+    OCRVI_HIP(dg.err);
+    OCRVI_TRY(k_ctc_argmax_tbc_conf(log_probs, argmax_ids, best_lp, B, T, C, (hipStream_t)stream));
+    if (ids || lens || char_lp || char_span)
+        OCRVI_TRY(k_ctc_collapse_conf(argmax_ids, best_lp, ids, lens, char_lp, char_span, B, T, blank_id, (hipStream_t)stream));
     return OCRVI_OK;
 }

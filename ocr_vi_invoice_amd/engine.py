@@ -32,6 +32,7 @@ from . import _lib
 from .codec import IMAGE_BYTES, JPEG, PNG, format_of_info, imdecode, info_struct, parse_into, stream_buffer, table_entry
 from .pipeline import (DBPostProcessor, _check_crop, db_boxes_pages, enhance_init, enhance_workspace_bytes, find_document_quads,
                        four_point_geometry, overlay_paint_, overlay_segments, quad_crops)
+from .rec import make_recognitions
 
 _ARENA_ALIGN = 256
 _STREAMS: Dict[int, Tuple[torch.cuda.Stream, torch.cuda.Stream]] = {}
@@ -129,11 +130,16 @@ class Engine:
     new device uint8 tensor: the page as the detector saw it (rectified and enhanced where asked for, as the reference draws on its
     preprocessed ``original_image``, pipeline2.py:358-360) with ``pipeline.draw_boxes_with_text(page, boxes, texts)`` painted on it -- per
     wave, one copy per page out of the arena and one ``ocrvi_overlay_pages`` launch.  The arena and the caller's tensors are never written.
+    ``confidence=True`` (the constructor's argument only: it decides what the recogniser graph holds): each page's result gains a last
+    element ``recs``, one ``rec.Recognition`` per box with ``recs[i].text == texts[i]`` (after ``annotated`` when both are on).  The
+    recogniser graph then calls ``enqueue_forward_conf`` (``ocrvi_rec_forward_conf``) and ``char_lp`` / ``char_span`` come back beside the
+    ids; no log-probabilities are stored, so ``log_prob`` is ``None``.  With ``False`` the engine enqueues exactly what it always has.
     The captured graphs hold the models' weights as they were: after reloading a model's weights, build a new Engine."""
 
     def __init__(self, det_model, rec_model, post_processor: DBPostProcessor, det_size: int = 960, rec_size: Tuple[int, int] = (32, 256),
                  det_chunk: int = 16, rec_batch: int = 256, max_pages: int = 256, graphs: bool = True, graph_cache: int = 16,
-                 post_threads: int = 0, prob_hook=None, binary_head: bool = False, crop: str = "rect", annotate: bool = False):
+                 post_threads: int = 0, prob_hook=None, binary_head: bool = False, crop: str = "rect", annotate: bool = False,
+                 confidence: bool = False):
         rh, rw = int(rec_size[0]), int(rec_size[1])
         if rh <= 0 or rw <= 0 or rh % 16 or rw % 4:
             raise ValueError(f"rec_size {rec_size}: the height must be a multiple of 16 and the width of 4")
@@ -185,6 +191,12 @@ class Engine:
         self.h_ids = [torch.empty((self.rec_batch, T), dtype=torch.int32).pin_memory() for _ in range(nslots)]
         self.h_lens = [torch.empty((self.rec_batch,), dtype=torch.int32).pin_memory() for _ in range(nslots)]
         self.ev_rec = [torch.cuda.Event() for _ in range(nslots)]
+        self.confidence = bool(confidence)
+        if self.confidence:                        # per-character records beside the ids: char_lp [B,T], char_span [B,T,2]
+            self.d_char_lp = torch.empty((self.rec_batch, T), dtype=torch.float32, **d)
+            self.d_char_span = torch.empty((self.rec_batch, T, 2), dtype=torch.int32, **d)
+            self.h_char_lp = [torch.empty((self.rec_batch, T), dtype=torch.float32).pin_memory() for _ in range(nslots)]
+            self.h_char_span = [torch.empty((self.rec_batch, T, 2), dtype=torch.int32).pin_memory() for _ in range(nslots)]
         if self.crop == "quad":                    # oriented crops: a descriptor row (page, w, h, 0) and a matrix per crop instead of a rectangle
             self.d_qcrops = torch.zeros((self.rec_batch, 4), dtype=torch.int32, **d)
             self.d_qmat = torch.zeros((self.rec_batch, 9), dtype=torch.float64, **d)
@@ -248,6 +260,11 @@ class Engine:
         else:
             _lib.check(self.lib.ocrvi_crop_resize_normalize_pages(self.devi, self.d_rec_table.data_ptr(), self.max_pages, self.d_rects.data_ptr(),
                                                                   self.rec_batch, rh, rw, self.d_crops.data_ptr(), st))
+        if self.confidence:
+            self.rec.enqueue_forward_conf(self.d_crops.data_ptr(), self.rec_batch, rh, rw, None, self.d_am.data_ptr(), self.d_ids.data_ptr(),
+                                          self.d_lens.data_ptr(), None, self.d_char_lp.data_ptr(), self.d_char_span.data_ptr(),
+                                          self.rec_ws.data_ptr(), self.rec_ws.numel(), st)
+            return
         self.rec.enqueue_forward(self.d_crops.data_ptr(), self.rec_batch, rh, rw, None, self.d_am.data_ptr(), self.d_ids.data_ptr(),
                                  self.d_lens.data_ptr(), self.rec_ws.data_ptr(), self.rec_ws.numel(), st)
 
@@ -453,6 +470,9 @@ class Engine:
             self._run_rec()
             self.h_ids[k].copy_(self.d_ids, non_blocking=True)
             self.h_lens[k].copy_(self.d_lens, non_blocking=True)
+            if self.confidence:
+                self.h_char_lp[k].copy_(self.d_char_lp, non_blocking=True)
+                self.h_char_span[k].copy_(self.d_char_span, non_blocking=True)
             self.ev_rec[k].record(self.s_rec)
         self._rec_inflight.append((k, tags))
         self.stats["rec_batches"] += 1
@@ -463,6 +483,13 @@ class Engine:
         self.ev_rec[k].synchronize()
         self.stats["rec_wait_s"] += time.perf_counter() - t0
         n = len(tags)
+        if self.confidence:
+            recs = make_recognitions(self.rec.tokenizer, self.h_ids[k][:n].numpy(), self.h_lens[k][:n].numpy(), self.h_char_lp[k][:n].numpy(),
+                                     self.h_char_span[k][:n].numpy())
+            for (pg, b), r in zip(tags, recs):
+                self._texts[pg][b] = r.text
+                self._recs[pg][b] = r
+            return
         ids, lens = self.h_ids[k][:n].tolist(), self.h_lens[k][:n].tolist()
         texts = self.rec.tokenizer.decode([row[:m] for row, m in zip(ids, lens)])
         for (pg, b), t in zip(tags, texts):
@@ -492,6 +519,7 @@ class Engine:
         for i, slot, (polys, r, sc) in zip(idx, slots, res):
             self._boxes[i], self._scores[i] = polys, [float(v) for v in sc]
             self._texts[i] = [None] * len(polys)
+            self._recs[i] = [None] * len(polys)
             if self.crop == "quad":                # the page's polygons -> quads -> descriptors, one batch call each
                 tq = time.perf_counter()
                 qc, qm = quad_crops(polys, self._sizes[i], page_id=slot)
@@ -654,6 +682,7 @@ class Engine:
             if self.d_enh_out.numel() < enh_out:
                 self.d_enh_out = torch.empty(enh_out, dtype=torch.uint8, device=self.dev)
         self._boxes, self._scores, self._texts = [None] * len(pages), [None] * len(pages), [None] * len(pages)
+        self._recs = [None] * len(pages)
         self._pend_rects, self._pend_tags = [], []
         self._rec_inflight, self._rec_slot = collections.deque(), 0
         order = [i for v in buckets.values() for i in v]
@@ -679,7 +708,10 @@ class Engine:
                 raise OverflowError(msg)
             _lib.check(rc)
         self.stats["total_s"] = time.perf_counter() - t_start
+        out = [(self._boxes[i], self._scores[i], self._texts[i]) for i in range(len(pages))]
         if self._annotate:
             annotated, self._annotated = self._annotated, []
-            return [(self._boxes[i], self._scores[i], self._texts[i], annotated[i]) for i in range(len(pages))]
-        return [(self._boxes[i], self._scores[i], self._texts[i]) for i in range(len(pages))]
+            out = [r + (annotated[i],) for i, r in enumerate(out)]
+        if self.confidence:
+            out = [r + (self._recs[i],) for i, r in enumerate(out)]
+        return out

@@ -31,7 +31,7 @@ from .codec import (IMAGE_BYTES, IMWRITE_FORMATS, JPEG_BYTES, JPEG_SUBSAMPLINGS,
                     jpeg_quant_tables, jpeg_table_entry, png_encode_sizes, png_info, png_info_struct, png_parse, png_parse_into, png_plan,
                     png_table_entry)
 from .det import DBNetPP
-from .rec import SVTRv2
+from .rec import Recognition, SVTRv2
 
 
 def _numpy_data_globals():
@@ -452,14 +452,40 @@ def recognize_text(model: SVTRv2, crop: np.ndarray, device: str = "cuda:0", img_
 
 
 def recognize_text_batch(model: SVTRv2, crops: List[np.ndarray], device: str = "cuda:0", img_size: Tuple[int, int] = (32, 256),
-                         batch_size: int = 32) -> List[str]:
+                         batch_size: int = 32, return_confidence: bool = False):
     """pipeline2.py:144-168: batches of ``batch_size`` crops -> forward -> greedy CTC strings.  Empty crops become the all-zero tensor
-    of :154-156."""
-    texts: List[str] = []
+    of :154-156.  ``return_confidence=True``: a list of ``rec.Recognition`` instead, whose ``text`` are those strings."""
+    texts = []
     for i in range(0, len(crops), batch_size):
         ts = [preprocess_for_recognition(c, img_size, device) for c in crops[i:i + batch_size]]
-        texts.extend(model.decode_greedy(torch.stack(ts)))
+        texts.extend(model.decode_greedy(torch.stack(ts), True) if return_confidence else model.decode_greedy(torch.stack(ts)))
     return texts
+
+
+def char_boxes(rect, rec: Recognition, rec_size: Tuple[int, int] = (32, 256)) -> np.ndarray:
+    """Where the characters of a recognised rectangle crop sit on the page: ``rect = (x, y, w, h)`` as ``crop_rect`` gives it, ``rec`` the
+    crop's ``Recognition`` -> int32 [len(rec.text), 4] rectangles (x, y, w, h).  Step t of the recogniser stands for columns [4t, 4t + 4) of
+    the resized crop, clipped to its resized width ``rw`` (the ``new_w`` of ``preprocess_for_recognition``: ``int(w * (rec_h / h))``, at
+    most ``rec_size[1]``, at least 1); a span (t0, t1) covers resized columns [c0, c1) = [4 t0, 4 t1 + 4) and maps back in integers:
+    ``x0 = x + (c0 * w) // rw``, ``x1 = x + ceil(c1 * w / rw)`` clipped to ``x + w``, the width at least 1 and inside the crop (a span that
+    lies in the padding right of ``rw`` gives the crop's last column).  ``y`` and ``h`` are the crop's.
+    Greedy CTC spans are peaky -- the network commits to a character on a step or two and emits blank around it -- so these boxes are
+    approximate: they say where the character was decided, not its full extent.  Oriented (quad) crops are not supported: ValueError."""
+    r = np.asarray(rect)
+    if r.shape != (4,) or r.dtype.kind not in "iu":
+        raise ValueError(f"char_boxes: expected an integer rectangle (x, y, w, h), got shape {r.shape} dtype {r.dtype} "
+                         "(oriented crops are not supported)")
+    x, y, w, h = (int(v) for v in r)
+    if w <= 0 or h <= 0:
+        raise ValueError(f"char_boxes: empty rectangle {w}x{h}")
+    rw = max(min(int(w * (rec_size[0] / h)), int(rec_size[1])), 1)
+    out = np.empty((len(rec.spans), 4), np.int32)
+    for i, (t0, t1) in enumerate(rec.spans):
+        c0, c1 = min(4 * t0, rw), min(4 * t1 + 4, rw)
+        x0 = min(x + (c0 * w) // rw, x + w - 1)
+        x1 = min(x + -((-c1 * w) // rw), x + w)
+        out[i] = (x0, y, max(x1 - x0, 1), h)
+    return out
 
 
 def as_quad(pts, what: str = "quad") -> np.ndarray:
@@ -877,7 +903,7 @@ def save_result(path: str, image, boxes, texts=None, quality: int = 95, device: 
 
 def detect_and_recognize(original_image, det_model, rec_model, post_processor: DBPostProcessor, device: str = "cuda:0", det_size: int = 640,
                          rec_size: Tuple[int, int] = (32, 256), rec_batch_size: int = 64, binary_head: bool = False, quad=None,
-                         enhance: bool = False, crop: str = "rect"):
+                         enhance: bool = False, crop: str = "rect", confidence: bool = False):
     """Steps 2 and 3 of the reference's per-image loop (pipeline2.py:306-352) with every stage on this library: resize + normalise on the
     device -> ``det_model`` -> ``post_processor`` on the host copy of the binary map -> boxes rescaled to the original image -> the
     bounding rectangle of each box cropped, resized and normalised on the device straight from the uploaded page -> ``rec_model`` greedy
@@ -890,6 +916,7 @@ def detect_and_recognize(original_image, det_model, rec_model, post_processor: D
     the enhanced page.
     ``crop``: ``"rect"`` (the reference's crop, the default) or ``"quad"``: each box's minimum-area rectangle is warped upright into the
     recogniser instead of its bounding rectangle (``quad_crops``, ``preprocess_crops_quad``); boxes and scores do not change.
+    ``confidence=True``: the result gains a last element ``recs``, one ``rec.Recognition`` per box with ``recs[i].text == texts[i]``.
     Returns (rescaled_boxes [int32 (n_i, 2)], scores, texts); empty crops decode the all-zero tensor as pipeline2.py:154-156 does."""
     _check_crop(crop)
     if isinstance(original_image, IMAGE_BYTES):              # a JPEG or PNG file's bytes: decoded on the device (``imdecode``)
@@ -909,11 +936,22 @@ def detect_and_recognize(original_image, det_model, rec_model, post_processor: D
         det_model.check_range()                           # f16x2 only: OverflowError if an activation left fp16's range
     rescaled = rescale_boxes(boxes, scale_w, scale_h)
     texts: List[str] = []
+    recs: List[Recognition] = []
+
+    def decode(batch):
+        if confidence:
+            recs.extend(rec_model.decode_greedy(batch, True))
+        else:
+            texts.extend(rec_model.decode_greedy(batch))
+
+    def result():
+        return (rescaled, scores, [r.text for r in recs], recs) if confidence else (rescaled, scores, texts)
+
     if crop == "quad":
         qc, qm = quad_crops(rescaled, (h, w))
         for i in range(0, len(qc), rec_batch_size):
-            texts.extend(rec_model.decode_greedy(preprocess_crops_quad(page[None], qc[i:i + rec_batch_size], qm[i:i + rec_batch_size], rec_size)))
-        return rescaled, scores, texts
+            decode(preprocess_crops_quad(page[None], qc[i:i + rec_batch_size], qm[i:i + rec_batch_size], rec_size))
+        return result()
     rects = [(0,) + crop_rect((h, w), b) for b in rescaled]
     for i in range(0, len(rects), rec_batch_size):
         chunk = rects[i:i + rec_batch_size]
@@ -922,19 +960,20 @@ def detect_and_recognize(original_image, det_model, rec_model, post_processor: D
         if live:
             idx = torch.as_tensor([j for j, r in enumerate(chunk) if r[3] > 0 and r[4] > 0], device=page.device)
             batch[idx] = preprocess_crops(page[None], live, rec_size)
-        texts.extend(rec_model.decode_greedy(batch))
-    return rescaled, scores, texts
+        decode(batch)
+    return result()
 
 
 def detect_and_recognize_pages(images, det_model, rec_model, post_processor: DBPostProcessor, device: str = "cuda:0", det_size: int = 640,
-                               rec_size: Tuple[int, int] = (32, 256), rec_batch_size: int = 64, binary_head: bool = False, crop: str = "rect"):
+                               rec_size: Tuple[int, int] = (32, 256), rec_batch_size: int = 64, binary_head: bool = False, crop: str = "rect",
+                               confidence: bool = False):
     """``detect_and_recognize`` for a list of pages of any sizes in one call: a one-shot ``engine.Engine`` (pages bucketed by detector
     shape, detector chunks and recogniser batches across pages).  ``det_model`` / ``rec_model`` are the library's DBNetPP / SVTRv2 on
     ``device``.  Returns [(rescaled_boxes, scores, texts) per page, in input order], each what ``detect_and_recognize`` returns for that
-    page alone (``binary_head`` and ``crop`` as there)."""
+    page alone (``binary_head``, ``crop`` and ``confidence`` as there; the engine keeps no log-probabilities, so ``log_prob`` is ``None``)."""
     from .engine import Engine
     _check_crop(crop)
     if torch.device(device).type != "cuda" or _dev_index(device) != det_model._dev_index():
         raise ValueError(f"models live on cuda:{det_model._dev_index()}, not {device}")
     return Engine(det_model, rec_model, post_processor, det_size=det_size, rec_size=rec_size, rec_batch=rec_batch_size, binary_head=binary_head,
-                  crop=crop).run(images)
+                  crop=crop, confidence=confidence).run(images)

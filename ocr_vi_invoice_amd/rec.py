@@ -3,13 +3,51 @@
 ``decode_greedy`` semantics and attributes (``tokenizer``, ``blank_id``, ``dims``)."""
 from __future__ import annotations
 
-from typing import List
+import math
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib, weights
 from ._model import HandleModel
 from .vocab import VOCAB, Tokenizer
+
+
+class Recognition(NamedTuple):
+    """One recognised line with the greedy CTC path's confidences (``return_confidence=True``).  ``char_scores[i]`` is exp of the largest
+    log-probability the path gave character i over the steps of its run, ``spans[i] = (t0, t1)`` that run (inclusive steps of T = W / 4;
+    include/ocrvi.h, ``ocrvi_ctc_greedy_conf``); both cover exactly the characters of ``text``.  ``score`` is their mean (0.0 for an empty
+    string): the path's own per-character maximum, not a calibrated probability.  ``log_prob`` is the log-probability of the collapsed id
+    sequence over all alignments (``-ocrvi_ctc_loss``), or ``None`` where no log-probabilities were kept."""
+    text: str
+    score: float
+    char_scores: Tuple[float, ...]
+    spans: Tuple[Tuple[int, int], ...]
+    log_prob: Optional[float]
+
+
+def make_recognitions(tokenizer: Tokenizer, ids, lens, char_lp, char_span, log_probs: Optional[Sequence[float]] = None) -> List[Recognition]:
+    """Host half of the confidences: the device's exact ``ids`` [n,T] / ``lens`` [n] / ``char_lp`` [n,T] / ``char_span`` [n,T,2] on the
+    host (numpy arrays or anything ``np.asarray`` takes) -> one ``Recognition`` per row, in float64.  An id outside
+    ``tokenizer.id_to_token`` (pad id 1) is dropped from text, scores and spans alike, as ``Tokenizer.decode`` drops it from the text.
+    Only the ``lens[b]`` valid entries of a row become Python objects."""
+    ids, lens, char_lp, char_span = np.asarray(ids), np.asarray(lens), np.asarray(char_lp), np.asarray(char_span)
+    tokens = tokenizer.id_to_token
+    out = []
+    for b in range(len(lens)):
+        n = int(lens[b])
+        row = ids[b, :n].tolist()
+        keep = [k for k, i in enumerate(row) if i in tokens]
+        if len(keep) == n:
+            lp, sp = char_lp[b, :n].tolist(), char_span[b, :n].tolist()
+        else:
+            lp, sp = char_lp[b, keep].tolist(), char_span[b, keep].tolist()
+            row = [row[k] for k in keep]
+        scores = tuple([math.exp(v) for v in lp])
+        out.append(Recognition("".join([tokens[i] for i in row]), math.fsum(scores) / len(scores) if scores else 0.0, scores,
+                               tuple([(t0, t1) for t0, t1 in sp]), None if log_probs is None else float(log_probs[b])))
+    return out
 
 
 class SVTRv2(HandleModel):
@@ -49,6 +87,12 @@ class SVTRv2(HandleModel):
         """``ocrvi_rec_forward``, enqueue-only: raw device pointers (any output may be None), sizes and a stream; nothing is allocated
         or synchronised."""
         _lib.check(_lib.load().ocrvi_rec_forward(self._handle, x, B, H, W, log_probs, argmax, ids, lens, ws, ws_bytes, stream))
+
+    def enqueue_forward_conf(self, x, B, H, W, log_probs, argmax, ids, lens, best_lp, char_lp, char_span, ws, ws_bytes, stream) -> None:
+        """``ocrvi_rec_forward_conf``, enqueue-only like ``enqueue_forward``: the same four outputs plus best_lp / char_lp [B,T] float32 and
+        char_span [B,T,2] int32 (any may be None)."""
+        _lib.check(_lib.load().ocrvi_rec_forward_conf(self._handle, x, B, H, W, log_probs, argmax, ids, lens, best_lp, char_lp, char_span, ws,
+                                                      ws_bytes, stream))
 
     def _run(self, x: torch.Tensor, want_log_probs: bool, want_ids: bool):
         if x.dim() != 4 or x.shape[1] != 3:
@@ -93,20 +137,59 @@ class SVTRv2(HandleModel):
         self.check_range()      # (the copies above synchronised the stream already)
         return self.tokenizer.decode([row[:n] for row, n in zip(ids_h, lens_h)])
 
-    def decode_probs(self, log_probs: torch.Tensor) -> List[str]:
+    def _conf_buffers(self, B: int, T: int):
+        d = dict(device=self.device)
+        return (torch.empty((B, T), dtype=torch.int32, **d), torch.empty((B, T), dtype=torch.int32, **d), torch.empty((B,), dtype=torch.int32, **d),
+                torch.empty((B, T), dtype=torch.float32, **d), torch.empty((B, T), dtype=torch.float32, **d),
+                torch.empty((B, T, 2), dtype=torch.int32, **d))
+
+    def _recognitions(self, lp: torch.Tensor, ids, lens, char_lp, char_span) -> List[Recognition]:
+        """Device outputs -> ``Recognition`` rows; ``log_prob = -ocrvi_ctc_loss`` of ``lp`` with the device ids / lens as targets."""
+        T, B, Cn = lp.shape
+        logp = None
+        if T <= _lib.CTC_LOSS_MAX_TARGET:
+            nll = torch.empty(B, dtype=torch.float64, device=self.device)
+            _lib.check(_lib.load().ocrvi_ctc_loss(self._dev_index(), lp.data_ptr(), T, B, Cn, ids.data_ptr(), T, lens.data_ptr(), None,
+                                                  self.blank_id, nll.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
+            logp = (-nll).cpu().tolist()
+        rows = [t.cpu().numpy() for t in (ids, lens, char_lp, char_span)]
+        self.check_range()      # (the copies above synchronised the stream already)
+        return make_recognitions(self.tokenizer, *rows, logp)
+
+    def decode_probs(self, log_probs: torch.Tensor, return_confidence: bool = False):
         """Greedy CTC decode of (T,B,C) log-probs (svtrv2.py:545-569): argmax, collapse repeats, drop blank on the
-        device; id -> text (dropping pad id 1, tokenizer.py:73) on the host."""
+        device; id -> text (dropping pad id 1, tokenizer.py:73) on the host.  ``return_confidence=True``: a list of ``Recognition``
+        (``ocrvi_ctc_greedy_conf``) whose ``text`` are the strings returned otherwise."""
         lp = log_probs.to(device=self.device, dtype=torch.float32).contiguous()
         T, B, Cn = lp.shape
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if return_confidence:
+            am, ids, lens, blp, clp, span = self._conf_buffers(B, T)
+            _lib.check(_lib.load().ocrvi_ctc_greedy_conf(self._dev_index(), lp.data_ptr(), T, B, Cn, self.blank_id, am.data_ptr(), ids.data_ptr(),
+                                                         lens.data_ptr(), blp.data_ptr(), clp.data_ptr(), span.data_ptr(), stream))
+            return self._recognitions(lp, ids, lens, clp, span)
         am = torch.empty((B, T), dtype=torch.int32, device=self.device)
         ids = torch.empty((B, T), dtype=torch.int32, device=self.device)
         lens = torch.empty((B,), dtype=torch.int32, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
         _lib.check(_lib.load().ocrvi_ctc_greedy(self._dev_index(), lp.data_ptr(), T, B, Cn, self.blank_id, am.data_ptr(), ids.data_ptr(),
                                                 lens.data_ptr(), stream))
         return self._ids_to_text(ids, lens)
 
-    def decode_greedy(self, images: torch.Tensor) -> List[str]:
-        """forward + decode in one device pass (svtrv2.py:538-543)."""
+    def decode_greedy(self, images: torch.Tensor, return_confidence: bool = False):
+        """forward + decode in one device pass (svtrv2.py:538-543).  ``return_confidence=True``: a list of ``Recognition``; the pass then
+        also stores the log-probabilities, which ``log_prob`` needs."""
+        if return_confidence:
+            if images.dim() != 4 or images.shape[1] != 3:
+                raise ValueError(f"expected (B,3,H,W) input, got {tuple(images.shape)}")
+            x = images.to(device=self.device, dtype=torch.float32).contiguous()
+            B, _, H, W = x.shape
+            T = W // 4
+            ws = self._workspace(B, H, W)
+            lp = torch.empty((T, B, self.tokenizer.num_classes), dtype=torch.float32, device=self.device)
+            am, ids, lens, blp, clp, span = self._conf_buffers(B, T)
+            self.enqueue_forward_conf(x.data_ptr(), B, H, W, lp.data_ptr(), am.data_ptr(), ids.data_ptr(), lens.data_ptr(), blp.data_ptr(),
+                                      clp.data_ptr(), span.data_ptr(), ws.data_ptr(), ws.numel(),
+                                      torch.cuda.current_stream(self.device).cuda_stream)
+            return self._recognitions(lp, ids, lens, clp, span)
         _, _, ids, lens = self._run(images, False, True)
         return self._ids_to_text(ids, lens)

@@ -11,6 +11,7 @@ bench.py's map blend through ``prob_hook``: every page's ground-truth line boxes
 at 0.75 + 0.25 binary (elsewhere 0.25 binary).  Each ``run`` drains at its end (bench.py's timed region carries the recogniser's last
 partial batch over into the next step instead).
 ``--binary-head`` repeats the uniform / mixed sets with ``Engine(binary_head=True)`` under the key ``runs_binary_head``.
+``--confidence`` repeats them with ``Engine(confidence=True)`` under the key ``runs_confidence``.
 ``--quads`` adds the four-point rectification: under ``warp`` the kernel time of one 4000x3000 page warped to about 3586x2567 and of a
 16-page chunk of them through ``ocrvi_warp_perspective_pages`` (HIP events around every launch, warm, median), and under ``runs_quads`` the
 uniform / mixed sets with a quad on every page (``Engine.run(pages, quads)``: the page's own corners pulled in by a few per cent)."""
@@ -195,6 +196,8 @@ def main():
     ap.add_argument("--sets", default="uniform,mixed,preproc")
     ap.add_argument("--binary-head", action="store_true",
                     help="run the uniform / mixed sets a second time with Engine(binary_head=True); results under 'runs_binary_head'")
+    ap.add_argument("--confidence", action="store_true",
+                    help="run the uniform / mixed sets a second time with Engine(confidence=True); results under 'runs_confidence'")
     ap.add_argument("--quads", action="store_true",
                     help="time the perspective warp ('warp') and run the uniform / mixed sets with a quad on every page ('runs_quads')")
     ap.add_argument("--backbone", default="resnet50", choices=["resnet50", "resnet18"], help="the detector's backbone (backbone.py:12-15)")
@@ -233,6 +236,14 @@ def main():
             if "mixed" in sets:
                 runs_b.append(run_set("mixed binary_head " + ",".join(f"{h}x{w}" for h, w in MIXED), kwb, sizes, 960, args, det, rec, pp))
             res["runs_binary_head"] = runs_b
+        if args.confidence:    # the same sets with per-character confidences (ocrvi_rec_forward_conf in the recogniser graph)
+            kwc = dict(kw, confidence=True)
+            runs_c = []
+            if "uniform" in sets:
+                runs_c.append(run_set("uniform 960x1280 confidence", kwc, [(960, 1280)] * args.pages, 1280, args, det, rec, pp))
+            if "mixed" in sets:
+                runs_c.append(run_set("mixed confidence " + ",".join(f"{h}x{w}" for h, w in MIXED), kwc, sizes, 960, args, det, rec, pp))
+            res["runs_confidence"] = runs_c
         if args.quads:         # the same sets photographed: every page carries a quad and is rectified on the device first
             runs_q = []
             if "uniform" in sets:
