@@ -1074,6 +1074,21 @@ int ocrvi_test_lin_x2(int device, const float* a, const float* weight_host, cons
  * 4 consecutive elements [hi0 hi1 hi2 hi3 | lo0 lo1 lo2 lo3] (fp16), hi + lo = src * 2^s with one power of two s per layer that puts the
  * largest magnitude into [2^13, 2^14); *wscale = 2^-s.  (What ocrvi_*_create does to every GEMM weight in that mode.) */
 int ocrvi_test_pack_f16x2(const float* src, size_t n, void* dst, float* wscale);
+/* Host-only (no GPU): the bytes a weight packer hands to its kernel, weights float32 HOST.  kind
+ *   0  pack_lin_x2_stream(w0 [N = d0][K = d1])                                          (the stream carries its scale behind the units)
+ *   1  pack_mlp_stream(fc1 = w0 [4D][D], fc2 = w1 [D][4D], D = d0, dtype = d1)          (f16x2: likewise)
+ *   2  pack_bneck_tail(w3 = w0 [256][64], w1 = the next conv1 [64][256] or NULL): the tail stream; scales = {ws3, ws1}
+ *   3  pack_conv of a 3x3 layer w0 [Co = d1][C = d0][3][3] for conv3_halo (f16x2, halo): the quartet form; scales[0] = wscale
+ *   4  pack_conv of the same for the deformable convolution's pipelined kernel (f16x2): the quartet form; scales[0] = wscale
+ * *size = the byte count; out NULL: nothing else is written, else out [cap >= *size] receives the bytes.  scales: what the kernel's
+ * epilogue multiplies by (1.0 where the kind has none). */
+int ocrvi_test_pack_stream(int kind, const float* w0, const float* w1, int d0, int d1, void* out, size_t cap, size_t* size, float scales[2]);
+/* Host-only (no GPU): the XOR swizzle of rows 0 .. 63 of a [rows][128 B] LDS image, as the packers above and the kernels compute it: the
+ * 16-byte position P of row r is kept at P ^ swizzle(r).  swz128: row bits 1 and 3 (bits 0 and 2 of the value); swz_halo: row bits 1 and 2. */
+int ocrvi_test_swizzles(int32_t swz128_rows[64], int32_t swz_halo_rows[64]);
+/* Host-only (no GPU): the grid of a persistent kernel that walks ntile > 0 tiles on `slots` workgroup slots: at most min(ntile, slots)
+ * workgroups, and no more than the longest walk needs. */
+int ocrvi_test_persistent_grid(int ntile, int slots, int32_t* grid);
 
 /* The memory-bound kernels of the hot path, one hook each.  Same conventions as above: float32 DEVICE tensors in and out (converted to and
  * from `dtype`, the element type the kernel runs in, around the call), weights and vectors float32 HOST; each hook allocates, binds the

@@ -38,7 +38,7 @@ EXPORTS = [
     "ocrvi_jpeg_info", "ocrvi_jpeg_parse", "ocrvi_jpeg_table_entry", "ocrvi_jpeg_decode_pages",
     "ocrvi_test_conv_res", "ocrvi_test_db_tail",
     "ocrvi_db_target_jobs", "ocrvi_db_target_maps", "ocrvi_resize_normalize_pad_pages",
-    "ocrvi_test_mlp_raw", "ocrvi_test_lin_x2",
+    "ocrvi_test_mlp_raw", "ocrvi_test_lin_x2", "ocrvi_test_pack_stream", "ocrvi_test_swizzles", "ocrvi_test_persistent_grid",
     "ocrvi_test_bneck_tail",
     "ocrvi_jpeg_quant_tables", "ocrvi_jpeg_encode_header", "ocrvi_jpeg_encode_sizes", "ocrvi_jpeg_encode_table_entry", "ocrvi_jpeg_encode_pages",
     "ocrvi_test_gemm_raw", "ocrvi_test_ring_plan",
@@ -183,6 +183,9 @@ def load() -> C.CDLL:
     lib.ocrvi_test_lin_x2.argtypes = [i32, f32p, vp, vp, i32, i32, i32, i32, vp, f32p, i32, C.POINTER(C.c_float)]
     lib.ocrvi_test_mlp_raw.argtypes = [i32, i32, f32p, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, f32p, i32, C.POINTER(C.c_float)]
     lib.ocrvi_test_pack_f16x2.argtypes = [f32p, sz, vp, C.POINTER(C.c_float)]
+    lib.ocrvi_test_pack_stream.argtypes = [i32, vp, vp, i32, i32, vp, sz, C.POINTER(sz), C.POINTER(C.c_float)]
+    lib.ocrvi_test_swizzles.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.ocrvi_test_persistent_grid.argtypes = [i32, i32, C.POINTER(C.c_int32)]
     lib.ocrvi_test_layernorm.argtypes = [i32, i32, f32p, i32, i32, vp, vp, i32, i32, f32p]
     lib.ocrvi_test_frm_vertical.argtypes = [i32, i32, f32p, vp, i32, i32, i32, i32, f32p]
     lib.ocrvi_test_asf.argtypes = [i32, i32, f32p, f32p, f32p, f32p, vp, vp, i32, i32, i32, f32p]

@@ -665,6 +665,55 @@ extern "C" int ocrvi_test_lin_x2(int device, const float* a, const float* weight
     return OCRVI_OK;
 }
 
+// Host only: the bytes a weight packer hands to its kernel (include/ocrvi.h lists the kinds).  No HIP call.
+extern "C" int ocrvi_test_pack_stream(int kind, const float* w0, const float* w1, int d0, int d1, void* out, size_t cap, size_t* size,
+                                      float scales[2]) {
+    OCRVI_CHECK(w0 && size && scales, OCRVI_EINVAL, "test_pack_stream: null argument");
+    std::vector<char> bytes;
+    scales[0] = scales[1] = 1.f;
+    if (kind == 0) {
+        OCRVI_CHECK(lin_x2_eligible(OCRVI_F16X2, d1, d0), OCRVI_EINVAL, "test_pack_stream: lin_x2 needs K in {256, 384}, N %% 32 == 0 (N %d, K %d)", d0, d1);
+        pack_lin_x2_stream(w0, d0, d1, bytes);
+    } else if (kind == 1) {
+        OCRVI_CHECK(w1 && mlp_fused_eligible(d1, d0), OCRVI_EINVAL, "test_pack_stream: no fused MLP for D %d, dtype %d", d0, d1);
+        pack_mlp_stream(w0, w1, d0, d1, bytes);
+    } else if (kind == 2) {
+        PackedBneckTail pt = pack_bneck_tail(w0, nullptr, w1, nullptr);
+        bytes.swap(pt.stream);
+        scales[0] = pt.ws3;
+        scales[1] = pt.ws1;
+    } else if (kind == 3 || kind == 4) {
+        OCRVI_CHECK(d0 > 0 && d1 > 0, OCRVI_EINVAL, "test_pack_stream: bad channel counts");
+        PackedConv pc = pack_conv(w0, nullptr, d1, d0, 3, 3, 1, kind == 3 ? AM_CONV3 : AM_DCN, OCRVI_F16X2, kind == 3);
+        OCRVI_CHECK(kind == 3 ? pc.quartets : dcn_pipe_packing(OCRVI_F16X2, d0), OCRVI_EINVAL, "test_pack_stream: %d -> %d is not packed as quartets", d0, d1);
+        bytes.swap(pc.bytes);
+        scales[0] = pc.wscale;
+    } else {
+        set_error("test_pack_stream: unknown kind %d", kind);
+        return OCRVI_EINVAL;
+    }
+    *size = bytes.size();
+    if (!out) return OCRVI_OK;
+    OCRVI_CHECK(cap >= bytes.size(), OCRVI_EINVAL, "test_pack_stream: %zu bytes needed, %zu given", bytes.size(), cap);
+    memcpy(out, bytes.data(), bytes.size());
+    return OCRVI_OK;
+}
+
+// Host only: the two row swizzles as the packers call them (rows 0 .. 63), and the launchers' grid rule (common.h)
+extern "C" int ocrvi_test_swizzles(int32_t swz128_rows[64], int32_t swz_halo_rows[64]) {
+    OCRVI_CHECK(swz128_rows && swz_halo_rows, OCRVI_EINVAL, "test_swizzles: null out");
+    for (int r = 0; r < 64; ++r) {
+        swz128_rows[r] = swz128(r);
+        swz_halo_rows[r] = swz_halo(r);
+    }
+    return OCRVI_OK;
+}
+extern "C" int ocrvi_test_persistent_grid(int ntile, int slots, int32_t* grid) {
+    OCRVI_CHECK(grid && ntile > 0, OCRVI_EINVAL, "test_persistent_grid: bad argument");
+    *grid = persistent_grid(ntile, slots);
+    return OCRVI_OK;
+}
+
 // ---- the memory-bound kernels of kernels.hip, one hook each (no timing arguments: nothing benchmarks these)
 namespace {
 // [n] T -> float32 (same order): a C = 1 "NHWC -> NCHW" copy is a plain cast

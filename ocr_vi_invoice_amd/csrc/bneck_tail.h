@@ -410,8 +410,7 @@ static int launch_bneck_tail_t(const BneckTailParams& p_in, hipStream_t stream) 
     OCRVI_TRY(device_cus(&n_cu));
     const int tiles_x = cdiv(p.W, C::TW), tiles_y = cdiv(p.H, C::TH);
     const int ntile = p.n_img * tiles_y * tiles_x;
-    int gm = std::min(ntile, std::max(1, n_cu));
-    gm = cdiv(ntile, cdiv(ntile, gm));   // equal tile counts
+    const int gm = persistent_grid(ntile, n_cu);
     auto kern = bneck_tail_kernel<PHC>;
     OCRVI_TRY(ensure_max_smem((const void*)kern, B::SMEM));
     hipLaunchKernelGGL(kern, dim3(gm), dim3(512), B::SMEM, stream, p, tiles_x, tiles_y);

@@ -319,8 +319,11 @@ template <> struct Mma<f16x2_t> {   // operands are chunks [4 hi | 4 lo]: hh + l
 };
 
 // Swizzle for [rows][128 B] LDS tiles read as (row = base + lane&15, chunks 2g, 2g+1) with ds_read_b128:
-// conflict-free under the gfx950 lane-group / 64-bank rule (checked by simulation).
-__device__ __forceinline__ int swz128(int row) { return ((row >> 1) & 1) | (((row >> 3) & 1) << 2); }
+// conflict-free under the gfx950 lane-group / 64-bank rule (checked by simulation).  (Host too: the packers of weight_pack.h
+// store LDS images under the function the kernel reads with.)
+__host__ __device__ __forceinline__ int swz128(int row) { return ((row >> 1) & 1) | (((row >> 3) & 1) << 2); }
+// The same for fragment reads that start at ANY pixel of a patch (conv3_halo.h, bneck_tail.h): row bits 1 and 2.
+__host__ __device__ __forceinline__ int swz_halo(int row) { return ((row >> 1) & 1) | (((row >> 2) & 1) << 2); }
 
 // Exact (erf) GELU = x * Phi(x) with erfc by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7, i.e. fp32 round-off level):
 //   z = |x| / sqrt(2),  t = 1 / (1 + p z),  erfc(z) = t (a1 + t (a2 + t (a3 + t (a4 + t a5)))) exp(-z^2),
@@ -349,6 +352,12 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 }
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// Grid of a persistent kernel whose workgroups walk `ntile` tiles: at most one workgroup per slot (a CU, or a share of the CUs), and then
+// no more workgroups than the longest walk needs -- equal tile counts, e.g. 300 tiles on 256 slots run as 150 workgroups of 2.
+static inline int persistent_grid(int ntile, int slots) {
+    const int s = slots > 1 ? slots : 1;
+    return cdiv(ntile, cdiv(ntile, ntile < s ? ntile : s));
+}
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // ---------------------------------------------------------------- workspace arena

@@ -49,8 +49,6 @@
 
 namespace ocrvi {
 
-__device__ __forceinline__ int swz_halo(int row) { return ((row >> 1) & 1) | (((row >> 2) & 1) << 2); }
-
 template <int NC> struct HaloCfg {
     static constexpr int TH = 16, TW = 16, PH = TH + 2, PW = TW + 2, NPIX = PH * PW;   // 18 x 18 patch
     static constexpr int NI_P = (NPIX + 7) / 8;                    // 41 1-KiB patch pieces per stage (8 pixels x 128 B)
@@ -296,8 +294,7 @@ static int launch_conv3_halo_t(const ConvParams& p_in, int n_cu, hipStream_t str
     OCRVI_TRY(ring_pages(&p.zero_page, &p.dump_page));
     const int tiles_x = cdiv(p.OW, C::TW), tiles_y = cdiv(p.OH, C::TH);
     const int ntile = p.n_img * tiles_y * tiles_x, nct = p.Np / NC;
-    int gm = std::min(ntile, std::max(1, n_cu / nct));
-    gm = cdiv(ntile, cdiv(ntile, gm));   // equal tile counts
+    const int gm = persistent_grid(ntile, n_cu / nct);
     const int grid = gm * nct;
     auto kern = conv3_halo_kernel<T, NC, ACT>;
     OCRVI_TRY(ensure_max_smem((const void*)kern, C::SMEM));

@@ -427,7 +427,7 @@ inline DcnPipePlan dcn_pipe_plan(int esz, int n_img, int OH, int OW, int Np, int
     }
     r.patch_lw = best_lw;
     r.total = n_img * cdiv(OH, 128 >> best_lw) * cdiv(OW, 1 << best_lw) * (Np / r.bn);
-    r.grid = cdiv(r.total, cdiv(r.total, std::min(r.total, n_cu)));   // one persistent workgroup per CU, equal tile counts
+    r.grid = persistent_grid(r.total, n_cu);   // one persistent workgroup per CU
     r.nk = 9 * (Cin_g / (128 / esz));
     return r;
 }

@@ -225,8 +225,7 @@ inline Gconv32Plan gconv32_plan(int n_img, int H, int W, int groups, int n_cu) {
     r.smem = (r.th + 2) * (16 * r.nbx + 2) * GC_PS + 9 * 32 * GC_PS;
     r.hw_magic = gc_hw_magic(16 * r.nbx + 2);  // pix / HW == (pix * magic) >> 16 for every pix of the halo tile (gc_hw_magic_exact)
     r.ntile = n_img * r.bands_y * r.bands_x;
-    const int per_group = std::max(1, 2 * n_cu / groups);        // two persistent workgroups per CU over all groups
-    r.grid_x = cdiv(r.ntile, cdiv(r.ntile, per_group));          // equal tile counts
+    r.grid_x = persistent_grid(r.ntile, 2 * n_cu / groups);      // two persistent workgroups per CU over all groups
     r.tiles_min = r.ntile / r.grid_x;
     r.tiles_max = cdiv(r.ntile, r.grid_x);
     return r;

@@ -12,6 +12,7 @@
 #include "conv_gemm.h"
 #include "gemm_ring.h"
 #include "dcn_pipe.h"
+#include "weight_pack.h"
 
 namespace ocrvi {
 
@@ -92,11 +93,8 @@ void convert_to_dtype(const float* src, size_t n, int dtype, void* dst, float sc
     } else if (dtype == OCRVI_F16X2) {   // chunks of 4 elements: [4 hi | 4 lo], x * scale = hi + lo (n % 4 == 0: rows are padded to 32)
         _Float16* d = (_Float16*)dst;
         for (size_t i = 0; i < n; ++i) {
-            const float x = src[i] * scale;
-            const _Float16 hi = (_Float16)x;
             const size_t c = i >> 2, j = i & 3;
-            d[8 * c + j] = hi;
-            d[8 * c + 4 + j] = (_Float16)(x - (float)hi);
+            f16x2_split(src[i] * scale, d[8 * c + j], d[8 * c + 4 + j]);
         }
     } else if (dtype == OCRVI_BF16) {
         uint16_t* d = (uint16_t*)dst;
@@ -113,24 +111,12 @@ static PackedConv finish_pack(const std::vector<float>& wt, int groups, int Np, 
     pc.bytes.resize(wt.size() * dtype_size(dtype));
     float scale = 1.f;
     if (dtype == OCRVI_F16X2) {
-        // one power of two per layer that puts the largest |w| into [2^13, 2^14): far from fp16's 65504, and every weight within 2^-17
-        // of the largest keeps a NORMAL lo half (full 2^-23 relative accuracy; smaller ones are off by at most 2^-39 of the largest).
-        // The kernels' epilogues multiply the accumulator by the inverse, which is exact.
-        float mx = 0.f;
-        for (float v : wt) mx = std::max(mx, fabsf(v));
-        if (mx > 0.f && std::isfinite(mx)) {
-            int e = 0;
-            (void)frexpf(mx, &e);                       // mx in [2^(e-1), 2^e)
-            scale = ldexpf(1.0f, std::min(std::max(14 - e, -100), 100));
-        }
+        scale = f16x2_weight_scale(wt.data(), wt.size());
         pc.wscale = 1.0f / scale;
     }
     convert_to_dtype(wt.data(), wt.size(), dtype, pc.bytes.data(), scale);
-    if (quartets && dtype == OCRVI_F16X2) {
-        // (hi, lo) quartet form for kernels that read a lane's 8 k-slots as two 16-byte operands without regrouping them in registers
-        // (dcn_pipe.h, conv3_halo.h): every 32-byte group of 8 consecutive k-slots [hi4 lo4 | hi4' lo4'] becomes [hi4 hi4' | lo4 lo4']
-        uint64_t* q = (uint64_t*)pc.bytes.data();
-        for (size_t i = 0; i + 3 < pc.bytes.size() / 8; i += 4) std::swap(q[i + 1], q[i + 2]);
+    if (quartets && dtype == OCRVI_F16X2) {   // dcn_pipe.h, conv3_halo.h: every 8 consecutive k-slots as a (hi, lo) quartet pair (weight_pack.h)
+        for (size_t i = 0; i + 32 <= pc.bytes.size(); i += 32) f16x2_quartets(pc.bytes.data() + i);
     }
     pc.Np = Np;
     pc.Kp = Kp;
@@ -196,41 +182,21 @@ PackedConv pack_deconv2(const float* const* w, const float* const* bias, int gro
 // The tail stream of bneck_tail.h.  Per group q of 32 conv3 channels: a B unit = conv3's slice K 64 x N 32 as 64 rows R = 32 j + n
 // (K-step j, channel 32 q + n), then (with w1) a C unit = the next conv1's slice K 32 x N 64 as 64 rows m.  A row is 128 bytes = eight
 // 16-byte positions; positions 2 g and 2 g + 1 hold the hi and the lo halves of lane group g's eight k-slots, which are the channels the
-// kernel's accumulator lanes hand over: base + 4 g + e and base + 16 + 4 g + e (e = 0..3; base = 32 j for B, 32 q for C).  Position P of row R
-// is stored at byte R * 128 + ((P ^ swz_halo(R)) << 4): the unit is the LDS image, copied linearly.  One power-of-two scale per layer, as
-// finish_pack chooses it.
+// kernel's accumulator lanes hand over: base + 4 g + e and base + 16 + 4 g + e (e = 0..3; base = 32 j for B, 32 q for C).  Rows are stored
+// under swz_halo(R): the unit is the LDS image, copied linearly.  Scale, halves and row form: weight_pack.h.
 PackedBneckTail pack_bneck_tail(const float* w3, const float* b3, const float* w1, const float* b1) {
     PackedBneckTail pk;
-    auto scale_of = [](const float* w, size_t n) {
-        float mx = 0.f, scale = 1.f;
-        for (size_t i = 0; i < n; ++i) mx = std::max(mx, fabsf(w[i]));
-        if (mx > 0.f && std::isfinite(mx)) {
-            int e = 0;
-            (void)frexpf(mx, &e);
-            scale = ldexpf(1.0f, std::min(std::max(14 - e, -100), 100));
-        }
-        return scale;
-    };
-    const float s3 = scale_of(w3, 256 * 64), s1 = w1 ? scale_of(w1, 64 * 256) : 1.f;
+    const float s3 = f16x2_weight_scale(w3, 256 * 64), s1 = w1 ? f16x2_weight_scale(w1, 64 * 256) : 1.f;
     pk.ws3 = 1.0f / s3;
     pk.ws1 = 1.0f / s1;
     const int nu = w1 ? 16 : 8;
     pk.stream.assign((size_t)nu * 8192, 0);
-    auto swz = [](int row) { return ((row >> 1) & 1) | (((row >> 2) & 1) << 2); };   // swz_halo
-    // row R of unit u: the weights of output channel `n` of matrix w (row stride ld) at input channels base + ...
+    // row R of unit u: the weights wrow of one output channel at input channels base + ...
     auto put_row = [&](int u, int R, const float* wrow, int base, float scale) {
-        char* unit = pk.stream.data() + (size_t)u * 8192;
-        for (int g = 0; g < 4; ++g) {
-            _Float16 hi[8], lo[8];
-            for (int e = 0; e < 8; ++e) {
-                const int k = base + (e < 4 ? 4 * g + e : 16 + 4 * g + (e - 4));
-                const float x = wrow[k] * scale;
-                hi[e] = (_Float16)x;
-                lo[e] = (_Float16)(x - (float)hi[e]);
-            }
-            memcpy(unit + R * 128 + (((2 * g) ^ swz(R)) << 4), hi, 16);
-            memcpy(unit + R * 128 + (((2 * g + 1) ^ swz(R)) << 4), lo, 16);
-        }
+        float v[32];
+        for (int g = 0; g < 4; ++g)
+            for (int e = 0; e < 8; ++e) v[8 * g + e] = wrow[base + (e < 4 ? 4 * g + e : 16 + 4 * g + (e - 4))];
+        f16x2_put_row(v, scale, swz_halo(R), pk.stream.data() + (size_t)u * 8192 + R * 128);
     };
     for (int q = 0; q < 8; ++q) {
         const int ub = w1 ? 2 * q : q;

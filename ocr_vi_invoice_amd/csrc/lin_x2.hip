@@ -22,6 +22,7 @@
 
 #include "gemm_ring.h"
 #include "kernels.h"
+#include "weight_pack.h"
 
 namespace ocrvi {
 OCRVI_RANGE_FLAG_TU()
@@ -185,48 +186,19 @@ bool lin_x2_eligible(int dtype, int K, int N) {
 }
 
 // N / 32 units in output-column order, each the LDS image [K / 32][32 weight rows][128 B] (the fc1-slice layout of pack_mlp_x2_stream): row
-// r of unit u is output column 32 u + r.  Every 128-byte row: (hi, lo) quartets (chunk 2 q = hi halves of k-slots
-// 8 q .. 8 q + 7, chunk 2 q + 1 their lo halves), chunk ch stored at ch ^ swz128(row).  One power-of-two scale per layer (finish_pack's rule,
-// host_util.hip).  Tail: the weight scale's inverse (fp32).
+// r of unit u is output column 32 u + r, its K-step ks the 32 weights w[32 u + r][32 ks ..] in order.  Rows are stored under
+// swz128(32 ks + r); scale, halves and row form: weight_pack.h.  Tail: the weight scale's inverse (fp32).
 void pack_lin_x2_stream(const float* w, int N, int K, std::vector<char>& out) {
     const int KS = K / 32, NU = N / 32;
-    float scale = 1.f;
-    {
-        float mx = 0.f;
-        for (size_t i = 0; i < (size_t)N * K; ++i) mx = std::max(mx, fabsf(w[i]));
-        if (mx > 0.f && std::isfinite(mx)) {
-            int e = 0;
-            (void)frexpf(mx, &e);
-            scale = ldexpf(1.0f, std::min(std::max(14 - e, -100), 100));
-        }
-    }
-    const size_t nrows = (size_t)NU * KS * 32;
-    std::vector<float> buf(nrows * 32);
-    size_t o = 0;
+    const float scale = f16x2_weight_scale(w, (size_t)N * K);
+    const size_t units = (size_t)NU * KS * 32 * 128;
+    out.assign(units + 4, 0);
+    char* dst = out.data();
     for (int u = 0; u < NU; ++u)
         for (int ks = 0; ks < KS; ++ks)
-            for (int row = 0; row < 32; ++row) {
-                const float* src = w + (size_t)(32 * u + row) * K + 32 * ks;
-                for (int e = 0; e < 32; ++e, ++o) buf[o] = src[e];
-            }
-    std::vector<char> chunks(buf.size() * 4);
-    convert_to_dtype(buf.data(), buf.size(), OCRVI_F16X2, chunks.data(), scale);     // [4 hi | 4 lo] per 4 consecutive elements
-    out.assign(chunks.size() + 4, 0);
-    for (size_t r = 0; r < nrows; ++r) {
-        const uint64_t* src = (const uint64_t*)(chunks.data() + r * 128);      // 16 pieces of 8 bytes: (hi4, lo4) x 8 chunks
-        uint64_t q[16];
-        for (int k = 0; k < 4; ++k) {   // 32-byte group k: [hi4 lo4 | hi4' lo4'] -> [hi4 hi4' | lo4 lo4']
-            q[4 * k] = src[4 * k]; q[4 * k + 1] = src[4 * k + 2]; q[4 * k + 2] = src[4 * k + 1]; q[4 * k + 3] = src[4 * k + 3];
-        }
-        const int row = (int)(r & 31), sw = ((row >> 1) & 1) | (((row >> 3) & 1) << 2);   // swz128
-        uint64_t* dst = (uint64_t*)(out.data() + r * 128);
-        for (int ch = 0; ch < 8; ++ch) {
-            dst[2 * (ch ^ sw)] = q[2 * ch];
-            dst[2 * (ch ^ sw) + 1] = q[2 * ch + 1];
-        }
-    }
+            for (int r = 0; r < 32; ++r, dst += 128) f16x2_put_row(w + (size_t)(32 * u + r) * K + 32 * ks, scale, swz128(32 * ks + r), dst);
     const float tail = 1.0f / scale;
-    memcpy(out.data() + chunks.size(), &tail, 4);
+    memcpy(out.data() + units, &tail, 4);
 }
 
 template <int K, int R>
@@ -237,9 +209,7 @@ static int launch_lin_x2(const LinX2Params& p, int max_workgroups, hipStream_t s
     int n_cu = 0;
     OCRVI_TRY(device_cus(&n_cu));
     const int ntiles = (p.M + 127) / 128;
-    int grid = std::min(ntiles, n_cu);
-    if (max_workgroups > 0) grid = std::min(grid, max_workgroups);
-    grid = cdiv(ntiles, cdiv(ntiles, grid));  // equal tile counts
+    const int grid = persistent_grid(ntiles, max_workgroups > 0 ? std::min(n_cu, max_workgroups) : n_cu);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem, s, p);
     OCRVI_HIP(hipGetLastError());
     return OCRVI_OK;

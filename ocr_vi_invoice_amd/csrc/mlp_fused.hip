@@ -387,8 +387,7 @@ static int launch_mlp(const MlpParams& p, hipStream_t s) {
     int n_cu = 0;
     OCRVI_TRY(device_cus(&n_cu));
     const int ntiles = (p.M + 127) / 128;
-    int grid = std::min(ntiles, n_cu * WPS);
-    grid = cdiv(ntiles, cdiv(ntiles, grid));  // equal tile counts
+    const int grid = persistent_grid(ntiles, n_cu * WPS);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512 / TB), smem, s, p);
     OCRVI_HIP(hipGetLastError());
     return OCRVI_OK;

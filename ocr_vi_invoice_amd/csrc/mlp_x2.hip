@@ -21,6 +21,7 @@
 
 #include "gemm_ring.h"
 #include "kernels.h"
+#include "weight_pack.h"
 
 namespace ocrvi {
 OCRVI_RANGE_FLAG_TU()
@@ -362,61 +363,33 @@ bool mlp_x2_eligible(int dtype, int D) {
     return !off && dtype == OCRVI_F16X2 && (D == 128 || D == 256 || D == 384);
 }
 
-// power of two that puts the largest |w| into [2^13, 2^14) (finish_pack's rule, host_util.hip)
-static float x2_scale(const float* w, size_t n) {
-    float mx = 0.f;
-    for (size_t i = 0; i < n; ++i) mx = std::max(mx, fabsf(w[i]));
-    if (!(mx > 0.f) || !std::isfinite(mx)) return 1.f;
-    int e = 0;
-    (void)frexpf(mx, &e);
-    return ldexpf(1.0f, std::min(std::max(14 - e, -100), 100));
-}
-
 // Units in consumption order (unit k = fc1 slice of chunk k + fc2 slice of chunk k - 1, k = 0 .. 4 D / 32: the kernel's software pipeline),
 // each in LDS image order: [KS][32 hidden rows][128 B] of fc1, then [D output rows][128 B] of fc2 with the 32
 // hidden units of the chunk in the k-slot order the accumulator lanes produce (position 8 g + j <-> hidden 16 (j >> 2) + 4 g + (j & 3)).
-// Every 128-byte row: (hi, lo) quartets (chunk 2 q = hi halves of k-slots 8 q .. 8 q + 7, chunk 2 q + 1 their lo halves), chunk ch stored at
-// ch ^ swz128(row).  Tail: the two weight scales (fp32).
+// Rows are stored under swz128(row in its part); scale, halves and row form: weight_pack.h.  Tail: the two weight scales (fp32).
 void pack_mlp_x2_stream(const float* w1, const float* w2, int D, std::vector<char>& out) {
     const int H4 = 4 * D, NCH = H4 / 32, KS = D / 32;
-    const float s1 = x2_scale(w1, (size_t)H4 * D), s2 = x2_scale(w2, (size_t)D * H4);
-    const size_t rows_per_unit = (size_t)KS * 32 + D, nrows = (size_t)(NCH + 1) * rows_per_unit;
-    std::vector<float> buf(nrows * 32, 0.f);
-    std::vector<int> rowidx(nrows);
-    size_t o = 0, ri = 0;
+    const float s1 = f16x2_weight_scale(w1, (size_t)H4 * D), s2 = f16x2_weight_scale(w2, (size_t)D * H4);
+    const size_t units = (size_t)(NCH + 1) * (KS * 32 + D) * 128;
+    out.assign(units + 8, 0);
+    char* dst = out.data();
+    float v[32];
     for (int k = 0; k <= NCH; ++k) {    // unit k: fc1 slice of chunk k (zeros for k = NCH), fc2 slice of chunk k - 1 (zeros for k = 0)
         for (int ks = 0; ks < KS; ++ks)
-            for (int r = 0; r < 32; ++r) {
-                rowidx[ri++] = ks * 32 + r;
-                for (int e = 0; e < 32; ++e, ++o)
-                    if (k < NCH) buf[o] = w1[(size_t)(32 * k + r) * D + 32 * ks + e] * s1;
+            for (int r = 0; r < 32; ++r, dst += 128) {
+                for (int e = 0; e < 32; ++e) v[e] = k < NCH ? w1[(size_t)(32 * k + r) * D + 32 * ks + e] : 0.f;
+                f16x2_put_row(v, s1, swz128(ks * 32 + r), dst);
             }
-        for (int n = 0; n < D; ++n) {
-            rowidx[ri++] = n;
-            for (int pos = 0; pos < 32; ++pos, ++o) {
+        for (int n = 0; n < D; ++n, dst += 128) {
+            for (int pos = 0; pos < 32; ++pos) {
                 const int g = pos >> 3, j = pos & 7;
-                if (k >= 1) buf[o] = w2[(size_t)n * H4 + 32 * (k - 1) + 16 * (j >> 2) + 4 * g + (j & 3)] * s2;
+                v[pos] = k >= 1 ? w2[(size_t)n * H4 + 32 * (k - 1) + 16 * (j >> 2) + 4 * g + (j & 3)] : 0.f;
             }
-        }
-    }
-    std::vector<char> chunks(buf.size() * 4);
-    convert_to_dtype(buf.data(), buf.size(), OCRVI_F16X2, chunks.data());     // [4 hi | 4 lo] per 4 consecutive elements
-    out.assign(chunks.size() + 8, 0);
-    for (size_t r = 0; r < nrows; ++r) {
-        const uint64_t* src = (const uint64_t*)(chunks.data() + r * 128);      // 16 pieces of 8 bytes: (hi4, lo4) x 8 chunks
-        uint64_t q[16];
-        for (int k = 0; k < 4; ++k) {   // 32-byte group k: [hi4 lo4 | hi4' lo4'] -> [hi4 hi4' | lo4 lo4']
-            q[4 * k] = src[4 * k]; q[4 * k + 1] = src[4 * k + 2]; q[4 * k + 2] = src[4 * k + 1]; q[4 * k + 3] = src[4 * k + 3];
-        }
-        const int row = rowidx[r], sw = ((row >> 1) & 1) | (((row >> 3) & 1) << 2);   // swz128
-        uint64_t* dst = (uint64_t*)(out.data() + r * 128);
-        for (int ch = 0; ch < 8; ++ch) {
-            dst[2 * (ch ^ sw)] = q[2 * ch];
-            dst[2 * (ch ^ sw) + 1] = q[2 * ch + 1];
+            f16x2_put_row(v, s2, swz128(n), dst);
         }
     }
     const float tail[2] = {1.0f / s1, 1.0f / s2};
-    memcpy(out.data() + chunks.size(), tail, 8);
+    memcpy(out.data() + units, tail, 8);
 }
 
 template <int D, int R, int TB, bool SPLIT>
@@ -427,8 +400,7 @@ static int launch_mlp_x2(const MlpX2Params& p, hipStream_t s) {
     int n_cu = 0;
     OCRVI_TRY(device_cus(&n_cu));
     const int ntiles = (p.M + 127) / 128;
-    int grid = std::min(ntiles, n_cu);
-    grid = cdiv(ntiles, cdiv(ntiles, grid));  // equal tile counts
+    const int grid = persistent_grid(ntiles, n_cu);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512 / TB), smem, s, p);
     OCRVI_HIP(hipGetLastError());
     return OCRVI_OK;

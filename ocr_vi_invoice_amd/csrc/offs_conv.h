@@ -193,8 +193,7 @@ static int launch_offs_conv_t(const ConvParams& p_in, int n_cu, hipStream_t stre
     OCRVI_TRY(ring_pages(&p.zero_page, &dump));
     const int tiles_x = cdiv(p.OW, C::TW), tiles_y = cdiv(p.OH, C::TH);
     const int ntile = p.n_img * tiles_y * tiles_x;
-    int grid = std::min(ntile, n_cu);
-    grid = cdiv(ntile, cdiv(ntile, grid));   // equal tile counts
+    const int grid = persistent_grid(ntile, n_cu);
     auto kern = offs_conv_kernel<T, S, TH>;
     OCRVI_TRY(ensure_max_smem((const void*)kern, C::SMEM));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), C::SMEM, stream, p, tiles_x, tiles_y);

@@ -252,7 +252,7 @@ int k_stem_pool(int dtype, const void* xpad, const void* w, const float* bias, f
     int n_cu = 0;
     OCRVI_TRY(device_cus(&n_cu));
     const int total = N * tyN * txN;
-    const int grid = cdiv(total, cdiv(total, std::min(total, n_cu)));   // one persistent workgroup per CU, equal tile counts
+    const int grid = persistent_grid(total, n_cu);   // one persistent workgroup per CU
     OCRVI_TRY(ensure_max_smem((const void*)stem_pool_kernel, SP_SMEM));
     hipLaunchKernelGGL(stem_pool_kernel, dim3(grid), dim3(512), SP_SMEM, s, (const char*)xpad, (const char*)w, bias, wscale, (char*)y, N, CH, CW, OH,
                        OW, Hp, Wp, tyN, txN);
