@@ -1040,6 +1040,27 @@ int ocrvi_test_conv_raw(int device, int dtype, const float* x, const float* weig
  * workgroup walks; grid.y = groups; 128-byte K-steps of the packed weights}. */
 int ocrvi_test_gconv_plan(int dtype, int N, int C, int H, int W, int Co, int sh, int sw, int groups, int out_f32, int has_res, int n_cu,
                           int32_t plan[12]);
+/* The three halo-tile kernels of the f16x2 detector with the output buffers owned by the caller, as ocrvi_test_conv_raw: each *_raw
+ * buffer is a DEVICE buffer of at least as many NHWC rows of f16x2 elements (`dtype` elements for the stem) as the output has pixels; the
+ * kernel writes it directly, the caller pre-fills it, and any rows past the output, and reads the bytes back; only the output's rows are
+ * converted to the float32 NCHW DEVICE tensors.  Each returns OCRVI_EINVAL when the call would not take the kernel named.
+ * ocrvi_test_conv3_halo_raw: the dense 3x3 (stride 1, pad 1, bias, act 0 none / 1 ReLU) of ocrvi_test_conv in OCRVI_F16X2 on
+ * conv3_halo_kernel: C a multiple of 32, Co a multiple of 4 up to 256, weights packed as (hi, lo) quartets; out_raw [>= N H W][Co].
+ * ocrvi_test_bneck_tail_raw: ocrvi_test_bneck_tail into y_raw [>= N H W][256] and t1n_raw [>= N H W][64] (unused with no_phase_c = 1).
+ * ocrvi_test_stem_pool_raw: ocrvi_test_stem_pool into out_raw [>= N H/4 W/4][64]; fused != 0 needs stem_pool_eligible. */
+int ocrvi_test_conv3_halo_raw(int device, const float* x, const float* weight_host, const float* bias_host, int N, int C, int H, int W, int Co,
+                              int act, void* out_raw, float* out);
+int ocrvi_test_bneck_tail_raw(int device, const float* t1, const float* identity, const float* w2_host, const float* b2_host,
+                              const float* w3_host, const float* b3_host, const float* w1_host, const float* b1_host, int N, int H, int W,
+                              int no_phase_c, void* y_raw, void* t1n_raw, float* y_out, float* t1n_out);
+int ocrvi_test_stem_pool_raw(int device, int dtype, const float* x, const float* weight_host, const float* bias_host, int N, int H, int W,
+                             int fused, void* out_raw, float* out);
+/* Host-only (no GPU): the launch of those kernels on a device of n_cu compute units, from the functions their launchers launch on.
+ * kind 0: conv3_halo for the C -> Co layer of ocrvi_test_conv3_halo_raw; 1: bneck_tail (either form; C, Co ignored); 2: the fused stem
+ * (H, W the image's; C, Co ignored).  plan = {takes the kernel (0 / 1), columns of a column tile NC, column tiles, pixel tiles across an
+ * image tiles_x, down it tiles_y (16 x 16 output pixels; the stem: 8 x 7 pooled pixels), workgroups, fewest and most pixel tiles one
+ * workgroup walks}. */
+int ocrvi_test_halo_plan(int kind, int N, int C, int H, int W, int Co, int n_cu, int32_t plan[8]);
 /* Multi-head self-attention on a packed qkv tensor [B, N, 3*heads*32] float32 (layout of
  * qkv.reshape(B,N,3,heads,32), svtrv2.py:80) -> out [B, N, heads*32] float32 (svtrv2.py:82-85). */
 /* The detector's stem: conv 7x7 stride 2 pad 3 (3 -> 64 channels) + bias + ReLU + max-pool 3x3 stride 2 pad 1 (torchvision resnet50's

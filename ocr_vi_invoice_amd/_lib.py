@@ -50,6 +50,7 @@ EXPORTS = [
     "ocrvi_document_contour", "ocrvi_document_contour_bits", "ocrvi_doc_working_size", "ocrvi_doc_mask_sizes", "ocrvi_doc_mask_pages",
     "ocrvi_doc_grey_u8", "ocrvi_doc_smooth_u8", "ocrvi_doc_histogram", "ocrvi_doc_otsu", "ocrvi_doc_mask_bits",
     "ocrvi_rec_forward_conf", "ocrvi_ctc_greedy_conf", "ocrvi_test_ctc_logsoftmax_conf",
+    "ocrvi_test_conv3_halo_raw", "ocrvi_test_bneck_tail_raw", "ocrvi_test_stem_pool_raw", "ocrvi_test_halo_plan",
 ]
 PAGE_ENTRY = 4          # int64 fields of one page-table entry: (device address, height, width, 0) -- OCRVI_PAGE_ENTRY
 # ocrvi_det_eval's record: 13 slots of 8 bytes (OCRVI_DET_EVAL_*), the first six int64, the rest float64
@@ -178,6 +179,10 @@ def load() -> C.CDLL:
     lib.ocrvi_test_conv_raw.argtypes = [i32, i32, f32p, vp, vp, f32p] + [i32] * 13 + [vp, f32p]
     lib.ocrvi_test_gconv_plan.argtypes = [i32] * 12 + [C.POINTER(C.c_int32)]
     lib.ocrvi_test_stem_pool.argtypes = [i32, i32, f32p, vp, vp, i32, i32, i32, i32, f32p, i32, C.POINTER(C.c_float)]
+    lib.ocrvi_test_conv3_halo_raw.argtypes = [i32, f32p, vp, vp, i32, i32, i32, i32, i32, i32, vp, f32p]
+    lib.ocrvi_test_bneck_tail_raw.argtypes = [i32, f32p, f32p, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, f32p, f32p]
+    lib.ocrvi_test_stem_pool_raw.argtypes = [i32, i32, f32p, vp, vp, i32, i32, i32, i32, vp, f32p]
+    lib.ocrvi_test_halo_plan.argtypes = [i32] * 7 + [C.POINTER(C.c_int32)]
     lib.ocrvi_test_attention.argtypes = [i32, i32, f32p, i32, i32, i32, f32p, i32, C.POINTER(C.c_float)]
     lib.ocrvi_test_mlp.argtypes = [i32, i32, f32p, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32p, i32, C.POINTER(C.c_float)]
     lib.ocrvi_test_lin_x2.argtypes = [i32, f32p, vp, vp, i32, i32, i32, i32, vp, f32p, i32, C.POINTER(C.c_float)]

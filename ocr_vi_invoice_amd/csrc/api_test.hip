@@ -182,8 +182,10 @@ extern "C" int ocrvi_test_dcn_plan(int dtype, int N, int C, int H, int W, int Co
     return OCRVI_OK;
 }
 
-extern "C" int ocrvi_test_stem_pool(int device, int dtype, const float* x, const float* weight_host, const float* bias_host, int N, int H, int W,
-                                    int fused, float* out, int iters, float* avg_ms) {
+// out_raw: the caller's own device output buffer (NHWC [>= N H/4 W/4][64] of `dtype` elements, ocrvi_test_stem_pool_raw), or null for one of
+// exactly that many rows allocated here
+static int test_stem_pool(int device, int dtype, const float* x, const float* weight_host, const float* bias_host, int N, int H, int W, int fused,
+                          void* out_raw, float* out, int iters, float* avg_ms) {
     OCRVI_CHECK(x && weight_host && bias_host && out && N > 0 && H >= 8 && W >= 8 && H % 4 == 0 && W % 4 == 0, OCRVI_EINVAL, "test_stem_pool: bad argument");
     OCRVI_CHECK(!fused || dtype == OCRVI_F16X2, OCRVI_EINVAL, "test_stem_pool: the fused kernel is the f16x2 form");
     OCRVI_HIP(hipSetDevice(device));
@@ -194,10 +196,13 @@ extern "C" int ocrvi_test_stem_pool(int device, int dtype, const float* x, const
     PackedConv pc = pack_conv(weight_host, bias_host, 64, 3, 7, 7, 1, AM_ROWS, dtype);
     OCRVI_TRY(upload_packed(st, pc, AM_ROWS, &L));
     const int Hp = H + 6, Wp = W + 8;
-    void *xp = nullptr, *sn = nullptr, *yn = nullptr;
+    // (the raw form names its kernel: the fused one must be what the detector would take for this stem)
+    OCRVI_CHECK(!out_raw || !fused || stem_pool_eligible(dtype, pc.N_g, pc.Kp, pc.KH, H, W), OCRVI_EINVAL,
+                "test_stem_pool_raw: this call does not take the fused kernel (OCRVI_STEM_FUSED=0?)");
+    void *xp = nullptr, *sn = nullptr, *yn = out_raw;
     OCRVI_TRY(sc.alloc((size_t)N * Hp * Wp * 4 * dtype_size(dtype), &xp));
     OCRVI_TRY(sc.alloc((size_t)N * (H / 2) * (W / 2) * 64 * dtype_size(dtype), &sn));
-    OCRVI_TRY(sc.alloc((size_t)N * (H / 4) * (W / 4) * 64 * dtype_size(dtype), &yn));
+    if (!yn) OCRVI_TRY(sc.alloc((size_t)N * (H / 4) * (W / 4) * 64 * dtype_size(dtype), &yn));
     OCRVI_TRY(k_nchw3_to_nhwc4_pad(dtype, x, xp, N, H, W, 3, 3, Hp, Wp, sc.s));
     Runner r(dtype, sc.s, (void*)256, 0);
     Tensor tx; tx.p = xp; tx.n = N; tx.h = Hp; tx.w = Wp; tx.c = 4;
@@ -212,6 +217,17 @@ extern "C" int ocrvi_test_stem_pool(int device, int dtype, const float* x, const
     OCRVI_TRY(k_nhwc_to_nchw_f32(dtype, yn, out, N, H / 4, W / 4, 64, 64, 0, sc.s));
     OCRVI_HIP(hipStreamSynchronize(sc.s));
     return OCRVI_OK;
+}
+
+extern "C" int ocrvi_test_stem_pool(int device, int dtype, const float* x, const float* weight_host, const float* bias_host, int N, int H, int W,
+                                    int fused, float* out, int iters, float* avg_ms) {
+    return test_stem_pool(device, dtype, x, weight_host, bias_host, N, H, W, fused, nullptr, out, iters, avg_ms);
+}
+
+extern "C" int ocrvi_test_stem_pool_raw(int device, int dtype, const float* x, const float* weight_host, const float* bias_host, int N, int H, int W,
+                                        int fused, void* out_raw, float* out) {
+    OCRVI_CHECK(out_raw, OCRVI_EINVAL, "test_stem_pool_raw: out_raw is null");
+    return test_stem_pool(device, dtype, x, weight_host, bias_host, N, H, W, fused, out_raw, out, 0, nullptr);
 }
 
 extern "C" int ocrvi_test_conv(int device, int dtype, const float* x, const float* weight_host, const float* bias_host, int N, int C,
@@ -373,11 +389,89 @@ extern "C" int ocrvi_test_gconv_plan(int dtype, int N, int C, int H, int W, int 
     return OCRVI_OK;
 }
 
+namespace {
+// The ConvParams of a dense stride-1 3x3 (pad 1) f16x2 layer with a bias and ReLU / none, as conv() fills them for a layer whose loader
+// asked pack_conv for conv3_halo's weight form (`quartets`: whether the packer gave it)
+ConvParams halo_conv_params(const void* x, const void* w, void* out, int N, int C, int H, int W, int Co, int Np, int act, bool quartets) {
+    ConvParams p;
+    p.x = x; p.w = w; p.out = out; p.bias = (const float*)256;
+    p.n_img = N; p.H = p.OH = H; p.W = p.OW = W; p.M = N * H * W;
+    p.KH = 3; p.SH = p.SW = 1; p.PH = p.PW = 1;
+    p.Cin = p.Cin_g = C;
+    p.N_g = Co; p.Np = Np; p.Kp = 9 * C;
+    p.ldo = Co; p.act = act;
+    p.w_quartets = quartets ? 1 : 0;
+    return p;
+}
+}  // namespace
+
+// conv3_halo_kernel alone (conv3_halo.h), f16x2, straight into the caller's buffer: OCRVI_EINVAL unless the packer gives the quartet form
+// and launch_conv sends this call to conv3_halo.
+extern "C" int ocrvi_test_conv3_halo_raw(int device, const float* x, const float* weight_host, const float* bias_host, int N, int C, int H, int W,
+                                         int Co, int act, void* out_raw, float* out) {
+    OCRVI_CHECK(x && weight_host && out && out_raw && N > 0 && C > 0 && H > 0 && W > 0 && Co > 0, OCRVI_EINVAL, "test_conv3_halo_raw: bad argument");
+    OCRVI_CHECK(act == ACT_NONE || act == ACT_RELU, OCRVI_EINVAL, "test_conv3_halo_raw: activation %d (none or ReLU)", act);
+    OCRVI_HIP(hipSetDevice(device));
+    Scratch sc;
+    OCRVI_TRY(sc.init());
+    const int dt = OCRVI_F16X2;
+    DeviceStore st;
+    ConvLayer L;
+    PackedConv pc = pack_conv(weight_host, bias_host, Co, C, 3, 3, 1, AM_CONV3, dt, true);
+    OCRVI_CHECK(pc.quartets, OCRVI_EINVAL, "test_conv3_halo_raw: %d -> %d is not packed as quartets (OCRVI_CONV3_HALO=0?)", C, Co);
+    OCRVI_TRY(upload_packed(st, pc, AM_CONV3, &L));
+    void* xn = nullptr;
+    OCRVI_TRY(sc.alloc((size_t)N * H * W * C * 4, &xn));
+    OCRVI_CHECK(conv3_halo_eligible(halo_conv_params(xn, L.w, out_raw, N, C, H, W, Co, pc.Np, act, true), AM_CONV3, dt), OCRVI_EINVAL,
+                "test_conv3_halo_raw: this call does not take conv3_halo");
+    OCRVI_TRY(to_nhwc(dt, x, xn, N, C, H * W, sc.s));
+    Runner r(dt, sc.s, (void*)256, 0);
+    Tensor tx; tx.p = xn; tx.n = N; tx.h = H; tx.w = W; tx.c = C;
+    Tensor ty; ty.p = out_raw; ty.n = N; ty.h = H; ty.w = W; ty.c = Co;
+    ConvOpts o;
+    o.pad = 1; o.act = act;
+    OCRVI_TRY(conv(r, L, tx, ty, o));
+    OCRVI_TRY(k_nhwc_to_nchw_f32(dt, out_raw, out, N, H, W, Co, Co, 0, sc.s));
+    OCRVI_HIP(hipStreamSynchronize(sc.s));
+    return OCRVI_OK;
+}
+
+// Host only: the launch of the three halo-tile kernels of the f16x2 detector on a device of n_cu compute units, from the functions their
+// launchers launch on (conv3_halo_plan, stem_pool_plan) and the predicates their callers dispatch on.  No device is touched.
+extern "C" int ocrvi_test_halo_plan(int kind, int N, int C, int H, int W, int Co, int n_cu, int32_t plan[8]) {
+    OCRVI_CHECK(plan && kind >= 0 && kind <= 2 && N > 0 && H > 0 && W > 0 && n_cu > 0, OCRVI_EINVAL, "test_halo_plan: bad argument");
+    for (int i = 0; i < 8; ++i) plan[i] = 0;
+    if (kind == 2) {   // k_stem_pool (C, Co: the stem's 3 -> 64)
+        OCRVI_CHECK(H % 4 == 0 && W % 4 == 0 && H >= 8 && W >= 8, OCRVI_EINVAL, "test_halo_plan: the stem takes H, W = multiples of 4 from 8 up");
+        const StemPoolPlan pl = stem_pool_plan(N, H, W, n_cu);
+        plan[0] = (stem_pool_eligible(OCRVI_F16X2, 64, 7 * 32, 7, H, W) && pl.total > 0) ? 1 : 0;
+        plan[1] = 64; plan[2] = 1; plan[3] = pl.txN; plan[4] = pl.tyN; plan[5] = pl.grid; plan[6] = pl.tiles_min; plan[7] = pl.tiles_max;
+        return OCRVI_OK;
+    }
+    int Np = 64;
+    bool taken = true;
+    if (kind == 0) {
+        OCRVI_CHECK(C > 0 && Co > 0, OCRVI_EINVAL, "test_halo_plan: bad channel counts");
+        const int bn = conv_bn_for(Co);
+        Np = cdiv(Co, bn) * bn;
+        const bool q = conv3_halo_packing(true, OCRVI_F16X2, C, Co, 3, 1, Np);
+        taken = q && conv3_halo_eligible(halo_conv_params((const void*)256, (const void*)256, (void*)256, N, C, H, W, Co, Np, ACT_RELU, q), AM_CONV3,
+                                         OCRVI_F16X2);
+        if (!(Np == 64 || Np == 128 || Np == 256)) return OCRVI_OK;   // (not taken, and no tiling to describe)
+    }   // kind 1: launch_bneck_tail (64 -> 64 -> 256 (-> 64) whatever C and Co say); every shape takes it
+    const HaloPlan pl = conv3_halo_plan(N, H, W, Np, n_cu);
+    plan[0] = taken ? 1 : 0;
+    plan[1] = pl.nc; plan[2] = pl.nct; plan[3] = pl.tiles_x; plan[4] = pl.tiles_y; plan[5] = pl.grid; plan[6] = pl.tiles_min; plan[7] = pl.tiles_max;
+    return OCRVI_OK;
+}
+
 // The fused ResNet-50 layer1 chain (bneck_tail.h), f16x2: t1 [N,64,H,W] -> conv2 3x3 + ReLU -> conv3 1x1 + identity [N,256,H,W] + ReLU = y
 // -> (unless no_phase_c) the next block's conv1 1x1 + ReLU = t1n [N,64,H,W].  Weights as the detector's loader packs them.
-extern "C" int ocrvi_test_bneck_tail(int device, const float* t1, const float* identity, const float* w2_host, const float* b2_host,
-                                     const float* w3_host, const float* b3_host, const float* w1_host, const float* b1_host, int N, int H, int W,
-                                     int no_phase_c, float* y_out, float* t1n_out, int iters, float* avg_ms) {
+// y_raw, t1n_raw: the caller's own device output buffers (NHWC f16x2 [>= N H W][256] / [64], ocrvi_test_bneck_tail_raw), or null for ones of
+// exactly N H W rows allocated here
+static int test_bneck_tail(int device, const float* t1, const float* identity, const float* w2_host, const float* b2_host, const float* w3_host,
+                           const float* b3_host, const float* w1_host, const float* b1_host, int N, int H, int W, int no_phase_c, void* y_raw,
+                           void* t1n_raw, float* y_out, float* t1n_out, int iters, float* avg_ms) {
     OCRVI_CHECK(t1 && identity && w2_host && w3_host && y_out && N > 0 && H > 0 && W > 0, OCRVI_EINVAL, "test_bneck_tail: bad argument");
     OCRVI_CHECK(no_phase_c || (w1_host && t1n_out), OCRVI_EINVAL, "test_bneck_tail: phase C needs the next conv1's weights and an output");
     OCRVI_HIP(hipSetDevice(device));
@@ -395,11 +489,11 @@ extern "C" int ocrvi_test_bneck_tail(int device, const float* t1, const float* i
     OCRVI_TRY(st.upload(pt.stream.data(), pt.stream.size(), &wt));
     OCRVI_TRY(st.upload_f32(pt.bias, &bt));
     const size_t P = (size_t)N * H * W;
-    void *xn = nullptr, *in = nullptr, *yn = nullptr, *tn = nullptr;
+    void *xn = nullptr, *in = nullptr, *yn = y_raw, *tn = no_phase_c ? nullptr : t1n_raw;
     OCRVI_TRY(sc.alloc(P * 64 * 4, &xn));
     OCRVI_TRY(sc.alloc(P * 256 * 4, &in));
-    OCRVI_TRY(sc.alloc(P * 256 * 4, &yn));
-    if (!no_phase_c) OCRVI_TRY(sc.alloc(P * 64 * 4, &tn));
+    if (!yn) OCRVI_TRY(sc.alloc(P * 256 * 4, &yn));
+    if (!no_phase_c && !tn) OCRVI_TRY(sc.alloc(P * 64 * 4, &tn));
     OCRVI_TRY(to_nhwc(dt, t1, xn, N, 64, H * W, sc.s));
     OCRVI_TRY(to_nhwc(dt, identity, in, N, 256, H * W, sc.s));
     BneckTailParams p;
@@ -411,6 +505,21 @@ extern "C" int ocrvi_test_bneck_tail(int device, const float* t1, const float* i
     if (!no_phase_c) OCRVI_TRY(k_nhwc_to_nchw_f32(dt, tn, t1n_out, N, H, W, 64, 64, 0, sc.s));
     OCRVI_HIP(hipStreamSynchronize(sc.s));
     return OCRVI_OK;
+}
+
+extern "C" int ocrvi_test_bneck_tail(int device, const float* t1, const float* identity, const float* w2_host, const float* b2_host,
+                                     const float* w3_host, const float* b3_host, const float* w1_host, const float* b1_host, int N, int H, int W,
+                                     int no_phase_c, float* y_out, float* t1n_out, int iters, float* avg_ms) {
+    return test_bneck_tail(device, t1, identity, w2_host, b2_host, w3_host, b3_host, w1_host, b1_host, N, H, W, no_phase_c, nullptr, nullptr, y_out,
+                           t1n_out, iters, avg_ms);
+}
+
+extern "C" int ocrvi_test_bneck_tail_raw(int device, const float* t1, const float* identity, const float* w2_host, const float* b2_host,
+                                         const float* w3_host, const float* b3_host, const float* w1_host, const float* b1_host, int N, int H,
+                                         int W, int no_phase_c, void* y_raw, void* t1n_raw, float* y_out, float* t1n_out) {
+    OCRVI_CHECK(y_raw && (no_phase_c || t1n_raw), OCRVI_EINVAL, "test_bneck_tail_raw: an output buffer is null");
+    return test_bneck_tail(device, t1, identity, w2_host, b2_host, w3_host, b3_host, w1_host, b1_host, N, H, W, no_phase_c, y_raw, t1n_raw, y_out,
+                           t1n_out, 0, nullptr);
 }
 
 // The DB head's tail (head.py:13-16 per branch: ConvTranspose2d(64,64,2,2) + BN + ReLU, ConvTranspose2d(64,1,2,2)) as det_model.hip builds and

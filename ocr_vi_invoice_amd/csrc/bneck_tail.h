@@ -403,17 +403,14 @@ __global__ __launch_bounds__(512, 2) void bneck_tail_kernel(const BneckTailParam
 template <bool PHC>
 static int launch_bneck_tail_t(const BneckTailParams& p_in, hipStream_t stream) {
     using B = BtCfg<PHC>;
-    using C = HaloCfg<64>;
     BneckTailParams p = p_in;
     OCRVI_TRY(ring_pages(&p.zero_page, &p.dump_page));
     int n_cu = 0;
     OCRVI_TRY(device_cus(&n_cu));
-    const int tiles_x = cdiv(p.W, C::TW), tiles_y = cdiv(p.H, C::TH);
-    const int ntile = p.n_img * tiles_y * tiles_x;
-    const int gm = persistent_grid(ntile, n_cu);
+    const HaloPlan pl = conv3_halo_plan(p.n_img, p.H, p.W, 64, n_cu);   // (phase A's tile: one column tile of 64)
     auto kern = bneck_tail_kernel<PHC>;
     OCRVI_TRY(ensure_max_smem((const void*)kern, B::SMEM));
-    hipLaunchKernelGGL(kern, dim3(gm), dim3(512), B::SMEM, stream, p, tiles_x, tiles_y);
+    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(512), B::SMEM, stream, p, pl.tiles_x, pl.tiles_y);
     OCRVI_HIP(hipGetLastError());
     return OCRVI_OK;
 }

@@ -287,36 +287,57 @@ __global__ __launch_bounds__(512, 2) void conv3_halo_kernel(const ConvParams p, 
 
 bool conv3_halo_eligible(const ConvParams& p, int amode, int dtype);   // host_util.hip
 
+// The launch of conv3_halo_kernel (and of bneck_tail_kernel, whose phase A is the NC = 64 tile: Np = 64) as a pure function of the shape and
+// the CU count: launch_conv3_halo / launch_bneck_tail_t launch on it and ocrvi_test_halo_plan reports it.
+struct HaloPlan {
+    int nc, nct;                 // columns of a column tile (256-column layers: two column tiles of 128), column tiles
+    int tiles_x, tiles_y, ntile; // 16 x 16 pixel tiles across / down an image, in all
+    int gm, grid;                // row lanes, workgroups = gm * nct
+    int tiles_min, tiles_max;    // pixel tiles the workgroups walk
+};
+inline HaloPlan conv3_halo_plan(int n_img, int OH, int OW, int Np, int n_cu) {
+    HaloPlan r;
+    // (256 columns: two column tiles of 128.  A 256-column tile -- 128 accumulator registers per wave -- spills at two waves per SIMD)
+    r.nc = Np == 64 ? 64 : 128;
+    r.nct = Np / r.nc;
+    r.tiles_x = cdiv(OW, HaloCfg<64>::TW); r.tiles_y = cdiv(OH, HaloCfg<64>::TH);
+    r.ntile = n_img * r.tiles_y * r.tiles_x;
+    r.gm = persistent_grid(r.ntile, n_cu / r.nct);
+    r.grid = r.gm * r.nct;
+    r.tiles_min = r.ntile / r.gm;
+    r.tiles_max = cdiv(r.ntile, r.gm);
+    return r;
+}
+
 template <typename T, int NC, int ACT>
-static int launch_conv3_halo_t(const ConvParams& p_in, int n_cu, hipStream_t stream) {
+static int launch_conv3_halo_t(const ConvParams& p_in, const HaloPlan& pl, hipStream_t stream) {
     using C = HaloCfg<NC>;
+    static_assert(C::TW == HaloCfg<64>::TW && C::TH == HaloCfg<64>::TH, "one pixel tile for every column width");
     ConvParams p = p_in;
     OCRVI_TRY(ring_pages(&p.zero_page, &p.dump_page));
-    const int tiles_x = cdiv(p.OW, C::TW), tiles_y = cdiv(p.OH, C::TH);
-    const int ntile = p.n_img * tiles_y * tiles_x, nct = p.Np / NC;
-    const int gm = persistent_grid(ntile, n_cu / nct);
-    const int grid = gm * nct;
     auto kern = conv3_halo_kernel<T, NC, ACT>;
     OCRVI_TRY(ensure_max_smem((const void*)kern, C::SMEM));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), C::SMEM, stream, p, tiles_x, tiles_y);
+    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(512), C::SMEM, stream, p, pl.tiles_x, pl.tiles_y);
     OCRVI_HIP(hipGetLastError());
     return OCRVI_OK;
 }
 
 template <typename T, int NC>
-static int launch_conv3_halo_n(const ConvParams& p, int n_cu, hipStream_t stream) {
-    if (p.act == ACT_RELU) return launch_conv3_halo_t<T, NC, ACT_RELU>(p, n_cu, stream);
-    return launch_conv3_halo_t<T, NC, ACT_NONE>(p, n_cu, stream);
+static int launch_conv3_halo_n(const ConvParams& p, const HaloPlan& pl, hipStream_t stream) {
+    if (p.act == ACT_RELU) return launch_conv3_halo_t<T, NC, ACT_RELU>(p, pl, stream);
+    return launch_conv3_halo_t<T, NC, ACT_NONE>(p, pl, stream);
 }
 
 template <typename T>
 static int launch_conv3_halo(const ConvParams& p, hipStream_t stream) {
     if constexpr (IsSplit<T>::value) {
-        int n_cu = 0;
-        OCRVI_TRY(device_cus(&n_cu));
-        // (256 columns: two column tiles of 128.  A 256-column tile -- 128 accumulator registers per wave -- spills at two waves per SIMD)
-        if (p.Np == 256 || p.Np == 128) return launch_conv3_halo_n<T, 128>(p, n_cu, stream);
-        if (p.Np == 64) return launch_conv3_halo_n<T, 64>(p, n_cu, stream);
+        if (p.Np == 256 || p.Np == 128 || p.Np == 64) {
+            int n_cu = 0;
+            OCRVI_TRY(device_cus(&n_cu));
+            const HaloPlan pl = conv3_halo_plan(p.n_img, p.OH, p.OW, p.Np, n_cu);
+            if (pl.nc == 128) return launch_conv3_halo_n<T, 128>(p, pl, stream);
+            return launch_conv3_halo_n<T, 64>(p, pl, stream);
+        }
     }
     set_error("conv3_halo: unsupported call (Np=%d)", p.Np);
     return OCRVI_EINVAL;

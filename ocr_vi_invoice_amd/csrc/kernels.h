@@ -14,6 +14,13 @@ int k_maxpool3x3s2(int dtype, const void* x, void* y, int N, int H, int W, int C
 bool stem_pool_eligible(int dtype, int cout, int Kp, int KH, int H, int W);
 int k_stem_pool(int dtype, const void* xpad, const void* w, const float* bias, float wscale, void* y, int N, int H, int W, int Hp, int Wp,
                 hipStream_t s);
+// k_stem_pool's launch as a pure function of the shape and the CU count (k_stem_pool launches on it, ocrvi_test_halo_plan reports it)
+struct StemPoolPlan {
+    int tyN, txN, total;        // 8 x 7 pooled-pixel tiles down / across an image, in all
+    int grid;                   // workgroups
+    int tiles_min, tiles_max;   // tiles the workgroups walk
+};
+StemPoolPlan stem_pool_plan(int N, int H, int W, int n_cu);
 // LayerNorm over the last dim (eps 1e-5, svtrv2.py:93,95,446).  x is f32 or T, out is f32 or T.
 int k_layernorm(int dtype, const void* x, int x_f32, void* out, int out_f32, const float* gamma, const float* beta, int rows, int D,
                 hipStream_t s);

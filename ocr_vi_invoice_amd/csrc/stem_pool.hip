@@ -240,22 +240,32 @@ bool stem_pool_eligible(int dtype, int cout, int Kp, int KH, int H, int W) {
     return !off && dtype == OCRVI_F16X2 && cout == 64 && Kp == SP_KS * 32 && KH == 7 && H % 4 == 0 && W % 4 == 0;
 }
 
+// (total = 0: more than 2^30 tiles, which k_stem_pool refuses)
+StemPoolPlan stem_pool_plan(int N, int H, int W, int n_cu) {
+    StemPoolPlan r;
+    r.tyN = cdiv(H / 4, SP_PH); r.txN = cdiv(W / 4, SP_PW);
+    const long long total = (long long)N * r.tyN * r.txN;
+    r.total = total < (1ll << 30) ? (int)total : 0;
+    r.grid = r.total > 0 ? persistent_grid(r.total, n_cu) : 0;   // one persistent workgroup per CU
+    r.tiles_min = r.grid > 0 ? r.total / r.grid : 0;
+    r.tiles_max = r.grid > 0 ? cdiv(r.total, r.grid) : 0;
+    return r;
+}
+
 // xpad: the padded NHWC4 input of the stem conv (Hp >= H + 6, Wp >= W + 8); y: [N][H / 4][W / 4][64]
 int k_stem_pool(int dtype, const void* xpad, const void* w, const float* bias, float wscale, void* y, int N, int H, int W, int Hp, int Wp,
                 hipStream_t s) {
     OCRVI_CHECK(dtype == OCRVI_F16X2 && xpad && w && bias && y && N > 0 && H % 4 == 0 && W % 4 == 0 && Hp >= H + 6 && Wp >= W + 8, OCRVI_EINVAL,
                 "stem_pool: bad arguments (N=%d, %dx%d, padded %dx%d)", N, H, W, Hp, Wp);
     const int CH = H / 2, CW = W / 2, OH = H / 4, OW = W / 4;
-    const int tyN = cdiv(OH, SP_PH), txN = cdiv(OW, SP_PW);
-    OCRVI_CHECK((size_t)N * tyN * txN < ((size_t)1 << 30), OCRVI_EINVAL, "stem_pool: too many tiles");
     ProfScope ps_("stem_pool_f16x2", 2.0 * N * CH * CW * 64 * 147, (double)N * (H * (double)W * 16 + OH * (double)OW * 256), s);
     int n_cu = 0;
     OCRVI_TRY(device_cus(&n_cu));
-    const int total = N * tyN * txN;
-    const int grid = persistent_grid(total, n_cu);   // one persistent workgroup per CU
+    const StemPoolPlan pl = stem_pool_plan(N, H, W, n_cu);
+    OCRVI_CHECK(pl.total > 0, OCRVI_EINVAL, "stem_pool: too many tiles");
     OCRVI_TRY(ensure_max_smem((const void*)stem_pool_kernel, SP_SMEM));
-    hipLaunchKernelGGL(stem_pool_kernel, dim3(grid), dim3(512), SP_SMEM, s, (const char*)xpad, (const char*)w, bias, wscale, (char*)y, N, CH, CW, OH,
-                       OW, Hp, Wp, tyN, txN);
+    hipLaunchKernelGGL(stem_pool_kernel, dim3(pl.grid), dim3(512), SP_SMEM, s, (const char*)xpad, (const char*)w, bias, wscale, (char*)y, N, CH, CW, OH,
+                       OW, Hp, Wp, pl.tyN, pl.txN);
     OCRVI_HIP(hipGetLastError());
     return OCRVI_OK;
 }
