@@ -167,6 +167,43 @@ int ocrvi_ctc_greedy_conf(int device, const float* log_probs, int T, int B, int 
                           int32_t* argmax_ids, int32_t* ids, int32_t* lens, float* best_lp, float* char_lp, int32_t* char_span, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * CTC prefix beam search: the nbest most probable labellings of every row, each with its log-probability.  No counterpart in the
+ * reference.  The standard prefix beam search without a language model, made deterministic by a tie rule and exact by string identity.
+ * ------------------------------------------------------------------------------------------------
+ * Row b of log_probs [T,B,C] float32 (device), blank = blank_id, beam width W = beam; all arithmetic in float64.
+ *   Inputs.  v(t,c) = (double) log_probs[t,b,c].  A NaN is taken as -inf (probability 0).  +inf is not supported: the result is
+ *     unspecified, and no address outside the buffers is formed.
+ *   logsumexp.  lse(a,b) = m + log(exp(a-m) + exp(b-m)) with m = max(a,b); -inf when m is (the lse3 of ocrvi_ctc_loss with a third term
+ *     of -inf).  a + b is -inf when either term is.
+ *   Entry.  A beam entry is (prefix l, pb, pnb): pb the log-probability of all alignments of l so far that end in blank, pnb of those that
+ *     end in a non-blank; s = lse(pb, pnb).  Start: one entry ((), 0, -inf).  Entries are kept in rank order i = 0..n-1.
+ *   Step t, for entry i:
+ *     stay (candidate index i*C + blank, prefix l_i): pb' = s_i + v(t,blank); pnb' = pnb_i + v(t,last(l_i)), -inf for the empty prefix.
+ *     extend by c, c != blank (candidate index i*C + c, prefix l_i + c): pb' = -inf; pnb' = (c == last(l_i) ? pb_i : s_i) + v(t,c).
+ *     merge: if l_i + c is, as a string of ids, the prefix l_j of another entry j of the beam, the extension is no candidate of its own:
+ *       its pnb' is added with lse into the pnb' of j's stay candidate.  At most one i extends into a given j.  Identity is the id string
+ *       itself (a hash filters, equality of the ids decides).
+ *     Every class is extended: there is no top-k pruning of classes.
+ *   Select.  A candidate's total is lse(pb', pnb').  Candidates with total -inf are dropped.  The W largest totals survive, larger first;
+ *     equal totals are ordered by smaller candidate index.  That order is the next step's rank order.
+ *   Output after step T-1, the first nbest entries in rank order: ids [B,nbest,T] int32 (the prefix, -1 beyond it), lens [B,nbest] int32,
+ *     score [B,nbest] float64 = s.  A missing hypothesis (fewer than nbest finite ones) has lens = -1, score = -inf, ids = -1.  Pad id 1 is
+ *     an ordinary label here, as it is for ocrvi_ctc_greedy.
+ * score is a lower bound of the labelling's full probability: score[n] <= -ocrvi_ctc_loss(ids[n]), with equality when nothing that leads
+ * to that labelling was ever pruned.  beam = 1 is not the greedy decode in general.
+ * Limits: 1 <= nbest <= beam <= OCRVI_CTC_BEAM_MAX, 2 <= C <= 1024, 0 <= blank_id < C, 1 <= T <= OCRVI_CTC_BEAM_MAX_T, B >= 1; anything
+ * else (or a null pointer, a workspace not 256-byte aligned) is OCRVI_EINVAL before any launch.  workspace: ocrvi_ctc_beam_workspace_bytes
+ * (the prefixes of both beam tables, [B][2][beam][T rounded up to even] int16, rounded up to 256 bytes); OCRVI_ENOMEM when it is short.
+ * Enqueue-only: one launch, no allocation, no synchronisation, capturable; the same input gives the same bytes.
+ * One workgroup of 256 threads per row; the beam tables and two rows of v live in LDS, the prefixes too when both tables fit in 32 KiB
+ * (in the workspace otherwise); selection is up to W rounds of a workgroup arg-max over candidates that are recomputed, never stored. */
+#define OCRVI_CTC_BEAM_MAX 64
+#define OCRVI_CTC_BEAM_MAX_T 1024
+int ocrvi_ctc_beam_workspace_bytes(int T, int B, int C, int beam, size_t* bytes);
+int ocrvi_ctc_beam(int device, const float* log_probs, int T, int B, int C, int blank_id, int beam, int nbest,
+                   int32_t* ids, int32_t* lens, double* score, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Pre-processing on the device (the callers either side of the two models on the e2e path).
  * ------------------------------------------------------------------------------------------------ */
 /* Replaces the detection input normalisation of src/pipeline/pipeline2.py:312-314: images uint8 HWC

@@ -51,6 +51,7 @@ EXPORTS = [
     "ocrvi_doc_grey_u8", "ocrvi_doc_smooth_u8", "ocrvi_doc_histogram", "ocrvi_doc_otsu", "ocrvi_doc_mask_bits",
     "ocrvi_rec_forward_conf", "ocrvi_ctc_greedy_conf", "ocrvi_test_ctc_logsoftmax_conf",
     "ocrvi_test_conv3_halo_raw", "ocrvi_test_bneck_tail_raw", "ocrvi_test_stem_pool_raw", "ocrvi_test_halo_plan",
+    "ocrvi_ctc_beam_workspace_bytes", "ocrvi_ctc_beam",
 ]
 PAGE_ENTRY = 4          # int64 fields of one page-table entry: (device address, height, width, 0) -- OCRVI_PAGE_ENTRY
 # ocrvi_det_eval's record: 13 slots of 8 bytes (OCRVI_DET_EVAL_*), the first six int64, the rest float64
@@ -59,6 +60,8 @@ DET_EVAL_INT_SLOTS = ("tp", "fp", "fn", "positive_count", "negatives", "negative
 DET_EVAL_F64_SLOTS = ("pos_bce", "topk_bce", "dice_inter", "pred_mask", "gt_mask", "l1_num", "thresh_mask")
 CTC_LOSS_MAX_TARGET = 1024      # OCRVI_CTC_LOSS_MAX_TARGET
 EDIT_DISTANCE_MAX_LEN = 2048    # OCRVI_EDIT_DISTANCE_MAX_LEN
+CTC_BEAM_MAX = 64               # OCRVI_CTC_BEAM_MAX
+CTC_BEAM_MAX_T = 1024           # OCRVI_CTC_BEAM_MAX_T
 CLAHE_WORKSPACE_BYTES = 16384   # OCRVI_CLAHE_WORKSPACE_BYTES
 ENHANCE_MIN_SIDE = 16           # the smallest page side the enhance entries take
 DB_TARGET_GT, DB_TARGET_MASK, DB_TARGET_THRESH = 0, 1, 2   # OCRVI_DB_TARGET_*: the map a fill job writes
@@ -201,6 +204,8 @@ def load() -> C.CDLL:
     lib.ocrvi_det_eval.argtypes = [i32, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, i32, i32, i32, C.c_double, vp, vp, sz, vp]
     lib.ocrvi_ctc_loss.argtypes = [i32, f32p, i32, i32, i32, i32p, i32, i32p, i32p, i32, vp, vp]
     lib.ocrvi_edit_distance.argtypes = [i32, i32p, i32, i32p, i32p, i32, i32p, i32, i32p, vp]
+    lib.ocrvi_ctc_beam_workspace_bytes.argtypes = [i32, i32, i32, i32, C.POINTER(sz)]
+    lib.ocrvi_ctc_beam.argtypes = [i32, f32p, i32, i32, i32, i32, i32, i32, i32p, i32p, vp, vp, sz, vp]
     lib.ocrvi_enhance_init.argtypes = [i32]
     lib.ocrvi_enhance_tables.argtypes = [vp, sz, C.POINTER(sz)]
     lib.ocrvi_enhance_workspace_bytes.argtypes = [i32, i32, C.POINTER(sz)]

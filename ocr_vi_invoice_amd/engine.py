@@ -32,7 +32,7 @@ from . import _lib
 from .codec import IMAGE_BYTES, JPEG, PNG, format_of_info, imdecode, info_struct, parse_into, stream_buffer, table_entry
 from .pipeline import (DBPostProcessor, _check_crop, db_boxes_pages, enhance_init, enhance_workspace_bytes, find_document_quads,
                        four_point_geometry, overlay_paint_, overlay_segments, quad_crops)
-from .rec import make_recognitions
+from .rec import check_beam, make_hypotheses, make_recognitions
 
 _ARENA_ALIGN = 256
 _STREAMS: Dict[int, Tuple[torch.cuda.Stream, torch.cuda.Stream]] = {}
@@ -134,17 +134,23 @@ class Engine:
     element ``recs``, one ``rec.Recognition`` per box with ``recs[i].text == texts[i]`` (after ``annotated`` when both are on).  The
     recogniser graph then calls ``enqueue_forward_conf`` (``ocrvi_rec_forward_conf``) and ``char_lp`` / ``char_span`` come back beside the
     ids; no log-probabilities are stored, so ``log_prob`` is ``None``.  With ``False`` the engine enqueues exactly what it always has.
+    ``beam=W, nbest=n`` (the constructor's arguments only, like ``confidence``; 1 <= n <= W <= 64): ``texts`` stay the greedy strings and
+    each page's result gains a last element (after ``recs`` when both are on), one list of ``rec.Hypothesis`` per box, best first, at most
+    ``n`` long.  The recogniser graph then keeps the forward's log-probabilities in a device buffer [T, rec_batch, C] and launches
+    ``ocrvi_ctc_beam`` on them after the forward, on the same stream (a sequential node); ids / lens / score of the hypotheses come back
+    through pinned slots beside the greedy ones.  With ``beam=None`` the engine enqueues exactly what it always has.
     The captured graphs hold the models' weights as they were: after reloading a model's weights, build a new Engine."""
 
     def __init__(self, det_model, rec_model, post_processor: DBPostProcessor, det_size: int = 960, rec_size: Tuple[int, int] = (32, 256),
                  det_chunk: int = 16, rec_batch: int = 256, max_pages: int = 256, graphs: bool = True, graph_cache: int = 16,
                  post_threads: int = 0, prob_hook=None, binary_head: bool = False, crop: str = "rect", annotate: bool = False,
-                 confidence: bool = False):
+                 confidence: bool = False, beam: int = None, nbest: int = 1):
         rh, rw = int(rec_size[0]), int(rec_size[1])
         if rh <= 0 or rw <= 0 or rh % 16 or rw % 4:
             raise ValueError(f"rec_size {rec_size}: the height must be a multiple of 16 and the width of 4")
         if det_size <= 0 or det_chunk <= 0 or rec_batch <= 0 or max_pages <= 0 or graph_cache <= 0:
             raise ValueError("det_size, det_chunk, rec_batch, max_pages and graph_cache must be positive")
+        check_beam(beam, nbest, rw // 4)
         self.det, self.rec, self.pp = det_model, rec_model, post_processor
         self.dev = det_model.device if det_model.device.index is not None else torch.device("cuda", det_model._dev_index())
         self.devi = det_model._dev_index()
@@ -197,6 +203,15 @@ class Engine:
             self.d_char_span = torch.empty((self.rec_batch, T, 2), dtype=torch.int32, **d)
             self.h_char_lp = [torch.empty((self.rec_batch, T), dtype=torch.float32).pin_memory() for _ in range(nslots)]
             self.h_char_span = [torch.empty((self.rec_batch, T, 2), dtype=torch.int32).pin_memory() for _ in range(nslots)]
+        self.beam, self.nbest = beam, int(nbest)
+        if beam is not None:                       # the forward's log-probabilities stay on the device; the hypotheses come back
+            C = rec_model.tokenizer.num_classes
+            self.d_lp = torch.empty((T, self.rec_batch, C), dtype=torch.float32, **d)
+            self.d_beam_ws = torch.empty(max(rec_model.beam_workspace_bytes(T, self.rec_batch, beam), 1), dtype=torch.uint8, **d)
+            shapes = (((self.rec_batch, self.nbest, T), torch.int32), ((self.rec_batch, self.nbest), torch.int32),
+                      ((self.rec_batch, self.nbest), torch.float64))
+            self.d_hyp = [torch.empty(sh, dtype=dt, **d) for sh, dt in shapes]         # ids, lens, score
+            self.h_hyp = [[torch.empty(sh, dtype=dt).pin_memory() for sh, dt in shapes] for _ in range(nslots)]
         if self.crop == "quad":                    # oriented crops: a descriptor row (page, w, h, 0) and a matrix per crop instead of a rectangle
             self.d_qcrops = torch.zeros((self.rec_batch, 4), dtype=torch.int32, **d)
             self.d_qmat = torch.zeros((self.rec_batch, 9), dtype=torch.float64, **d)
@@ -260,13 +275,18 @@ class Engine:
         else:
             _lib.check(self.lib.ocrvi_crop_resize_normalize_pages(self.devi, self.d_rec_table.data_ptr(), self.max_pages, self.d_rects.data_ptr(),
                                                                   self.rec_batch, rh, rw, self.d_crops.data_ptr(), st))
+        lp = self.d_lp.data_ptr() if self.beam is not None else None
         if self.confidence:
-            self.rec.enqueue_forward_conf(self.d_crops.data_ptr(), self.rec_batch, rh, rw, None, self.d_am.data_ptr(), self.d_ids.data_ptr(),
+            self.rec.enqueue_forward_conf(self.d_crops.data_ptr(), self.rec_batch, rh, rw, lp, self.d_am.data_ptr(), self.d_ids.data_ptr(),
                                           self.d_lens.data_ptr(), None, self.d_char_lp.data_ptr(), self.d_char_span.data_ptr(),
                                           self.rec_ws.data_ptr(), self.rec_ws.numel(), st)
-            return
-        self.rec.enqueue_forward(self.d_crops.data_ptr(), self.rec_batch, rh, rw, None, self.d_am.data_ptr(), self.d_ids.data_ptr(),
-                                 self.d_lens.data_ptr(), self.rec_ws.data_ptr(), self.rec_ws.numel(), st)
+        else:
+            self.rec.enqueue_forward(self.d_crops.data_ptr(), self.rec_batch, rh, rw, lp, self.d_am.data_ptr(), self.d_ids.data_ptr(),
+                                     self.d_lens.data_ptr(), self.rec_ws.data_ptr(), self.rec_ws.numel(), st)
+        if self.beam is not None:
+            ids, lens, score = self.d_hyp
+            self.rec.enqueue_beam(lp, rw // 4, self.rec_batch, self.beam, self.nbest, ids.data_ptr(), lens.data_ptr(), score.data_ptr(),
+                                  self.d_beam_ws.data_ptr(), self.d_beam_ws.numel(), st)
 
     def _run_det(self, n, H, W):
         """Steps 2 and 3 of a chunk on the detector stream: the cached graph of (H, W, n), or an eager launch that is captured after it."""
@@ -473,6 +493,9 @@ class Engine:
             if self.confidence:
                 self.h_char_lp[k].copy_(self.d_char_lp, non_blocking=True)
                 self.h_char_span[k].copy_(self.d_char_span, non_blocking=True)
+            if self.beam is not None:
+                for h, dv in zip(self.h_hyp[k], self.d_hyp):
+                    h.copy_(dv, non_blocking=True)
             self.ev_rec[k].record(self.s_rec)
         self._rec_inflight.append((k, tags))
         self.stats["rec_batches"] += 1
@@ -483,6 +506,9 @@ class Engine:
         self.ev_rec[k].synchronize()
         self.stats["rec_wait_s"] += time.perf_counter() - t0
         n = len(tags)
+        if self.beam is not None:
+            for (pg, b), h in zip(tags, make_hypotheses(self.rec.tokenizer, *[h[:n].numpy() for h in self.h_hyp[k]])):
+                self._hyps[pg][b] = h
         if self.confidence:
             recs = make_recognitions(self.rec.tokenizer, self.h_ids[k][:n].numpy(), self.h_lens[k][:n].numpy(), self.h_char_lp[k][:n].numpy(),
                                      self.h_char_span[k][:n].numpy())
@@ -520,6 +546,7 @@ class Engine:
             self._boxes[i], self._scores[i] = polys, [float(v) for v in sc]
             self._texts[i] = [None] * len(polys)
             self._recs[i] = [None] * len(polys)
+            self._hyps[i] = [None] * len(polys)
             if self.crop == "quad":                # the page's polygons -> quads -> descriptors, one batch call each
                 tq = time.perf_counter()
                 qc, qm = quad_crops(polys, self._sizes[i], page_id=slot)
@@ -683,6 +710,7 @@ class Engine:
                 self.d_enh_out = torch.empty(enh_out, dtype=torch.uint8, device=self.dev)
         self._boxes, self._scores, self._texts = [None] * len(pages), [None] * len(pages), [None] * len(pages)
         self._recs = [None] * len(pages)
+        self._hyps = [None] * len(pages)
         self._pend_rects, self._pend_tags = [], []
         self._rec_inflight, self._rec_slot = collections.deque(), 0
         order = [i for v in buckets.values() for i in v]
@@ -714,4 +742,6 @@ class Engine:
             out = [r + (annotated[i],) for i, r in enumerate(out)]
         if self.confidence:
             out = [r + (self._recs[i],) for i, r in enumerate(out)]
+        if self.beam is not None:
+            out = [r + (self._hyps[i],) for i, r in enumerate(out)]
         return out

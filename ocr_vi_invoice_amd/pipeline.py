@@ -17,7 +17,7 @@ those libraries is unpinned; it is checked bit-for-bit aga
 """
 from __future__ import annotations
 
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import ctypes
 
@@ -31,7 +31,7 @@ from .codec import (IMAGE_BYTES, IMWRITE_FORMATS, JPEG_BYTES, JPEG_SUBSAMPLINGS,
                     jpeg_quant_tables, jpeg_table_entry, png_encode_sizes, png_info, png_info_struct, png_parse, png_parse_into, png_plan,
                     png_table_entry)
 from .det import DBNetPP
-from .rec import Recognition, SVTRv2
+from .rec import Hypothesis, Recognition, SVTRv2, check_beam
 
 
 def _numpy_data_globals():
@@ -452,12 +452,18 @@ def recognize_text(model: SVTRv2, crop: np.ndarray, device: str = "cuda:0", img_
 
 
 def recognize_text_batch(model: SVTRv2, crops: List[np.ndarray], device: str = "cuda:0", img_size: Tuple[int, int] = (32, 256),
-                         batch_size: int = 32, return_confidence: bool = False):
+                         batch_size: int = 32, return_confidence: bool = False, beam: Optional[int] = None, nbest: int = 1):
     """pipeline2.py:144-168: batches of ``batch_size`` crops -> forward -> greedy CTC strings.  Empty crops become the all-zero tensor
-    of :154-156.  ``return_confidence=True``: a list of ``rec.Recognition`` instead, whose ``text`` are those strings."""
+    of :154-156.  ``return_confidence=True``: a list of ``rec.Recognition`` instead, whose ``text`` are those strings.
+    ``beam=W``: one list of ``rec.Hypothesis`` per crop instead (``SVTRv2.decode_greedy(..., beam=W, nbest=nbest)``: best first, at most
+    ``nbest``); ValueError together with ``return_confidence=True``."""
+    check_beam(beam, nbest, img_size[1] // 4, return_confidence)
     texts = []
     for i in range(0, len(crops), batch_size):
         ts = [preprocess_for_recognition(c, img_size, device) for c in crops[i:i + batch_size]]
+        if beam is not None:
+            texts.extend(model.decode_greedy(torch.stack(ts), beam=beam, nbest=nbest))
+            continue
         texts.extend(model.decode_greedy(torch.stack(ts), True) if return_confidence else model.decode_greedy(torch.stack(ts)))
     return texts
 
@@ -903,7 +909,7 @@ def save_result(path: str, image, boxes, texts=None, quality: int = 95, device: 
 
 def detect_and_recognize(original_image, det_model, rec_model, post_processor: DBPostProcessor, device: str = "cuda:0", det_size: int = 640,
                          rec_size: Tuple[int, int] = (32, 256), rec_batch_size: int = 64, binary_head: bool = False, quad=None,
-                         enhance: bool = False, crop: str = "rect", confidence: bool = False):
+                         enhance: bool = False, crop: str = "rect", confidence: bool = False, beam: Optional[int] = None, nbest: int = 1):
     """Steps 2 and 3 of the reference's per-image loop (pipeline2.py:306-352) with every stage on this library: resize + normalise on the
     device -> ``det_model`` -> ``post_processor`` on the host copy of the binary map -> boxes rescaled to the original image -> the
     bounding rectangle of each box cropped, resized and normalised on the device straight from the uploaded page -> ``rec_model`` greedy
@@ -917,8 +923,11 @@ def detect_and_recognize(original_image, det_model, rec_model, post_processor: D
     ``crop``: ``"rect"`` (the reference's crop, the default) or ``"quad"``: each box's minimum-area rectangle is warped upright into the
     recogniser instead of its bounding rectangle (``quad_crops``, ``preprocess_crops_quad``); boxes and scores do not change.
     ``confidence=True``: the result gains a last element ``recs``, one ``rec.Recognition`` per box with ``recs[i].text == texts[i]``.
+    ``beam=W``: ``texts`` stay the greedy strings; the result gains a last element (after ``recs`` when both are on), one list of
+    ``rec.Hypothesis`` per box from the prefix beam search on the same forward's log-probabilities (best first, at most ``nbest``).
     Returns (rescaled_boxes [int32 (n_i, 2)], scores, texts); empty crops decode the all-zero tensor as pipeline2.py:154-156 does."""
     _check_crop(crop)
+    check_beam(beam, nbest, rec_size[1] // 4)
     if isinstance(original_image, IMAGE_BYTES):              # a JPEG or PNG file's bytes: decoded on the device (``imdecode``)
         original_image = imdecode(original_image, device)
     page = original_image if isinstance(original_image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(original_image))
@@ -937,15 +946,21 @@ def detect_and_recognize(original_image, det_model, rec_model, post_processor: D
     rescaled = rescale_boxes(boxes, scale_w, scale_h)
     texts: List[str] = []
     recs: List[Recognition] = []
+    hyps: List[List[Hypothesis]] = []
 
     def decode(batch):
-        if confidence:
+        if beam is not None:
+            greedy, h = rec_model.decode_greedy_and_beam(batch, beam, nbest, confidence)
+            (recs if confidence else texts).extend(greedy)
+            hyps.extend(h)
+        elif confidence:
             recs.extend(rec_model.decode_greedy(batch, True))
         else:
             texts.extend(rec_model.decode_greedy(batch))
 
     def result():
-        return (rescaled, scores, [r.text for r in recs], recs) if confidence else (rescaled, scores, texts)
+        out = (rescaled, scores, [r.text for r in recs], recs) if confidence else (rescaled, scores, texts)
+        return out + (hyps,) if beam is not None else out
 
     if crop == "quad":
         qc, qm = quad_crops(rescaled, (h, w))
@@ -966,14 +981,15 @@ def detect_and_recognize(original_image, det_model, rec_model, post_processor: D
 
 def detect_and_recognize_pages(images, det_model, rec_model, post_processor: DBPostProcessor, device: str = "cuda:0", det_size: int = 640,
                                rec_size: Tuple[int, int] = (32, 256), rec_batch_size: int = 64, binary_head: bool = False, crop: str = "rect",
-                               confidence: bool = False):
+                               confidence: bool = False, beam: Optional[int] = None, nbest: int = 1):
     """``detect_and_recognize`` for a list of pages of any sizes in one call: a one-shot ``engine.Engine`` (pages bucketed by detector
     shape, detector chunks and recogniser batches across pages).  ``det_model`` / ``rec_model`` are the library's DBNetPP / SVTRv2 on
     ``device``.  Returns [(rescaled_boxes, scores, texts) per page, in input order], each what ``detect_and_recognize`` returns for that
-    page alone (``binary_head``, ``crop`` and ``confidence`` as there; the engine keeps no log-probabilities, so ``log_prob`` is ``None``)."""
+    page alone (``binary_head``, ``crop``, ``confidence``, ``beam`` and ``nbest`` as there; without ``beam`` the engine keeps no
+    log-probabilities, so ``log_prob`` is ``None``)."""
     from .engine import Engine
     _check_crop(crop)
     if torch.device(device).type != "cuda" or _dev_index(device) != det_model._dev_index():
         raise ValueError(f"models live on cuda:{det_model._dev_index()}, not {device}")
     return Engine(det_model, rec_model, post_processor, det_size=det_size, rec_size=rec_size, rec_batch=rec_batch_size, binary_head=binary_head,
-                  crop=crop, confidence=confidence).run(images)
+                  crop=crop, confidence=confidence, beam=beam, nbest=nbest).run(images)

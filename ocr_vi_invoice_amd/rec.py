@@ -50,6 +50,56 @@ def make_recognitions(tokenizer: Tokenizer, ids, lens, char_lp, char_span, log_p
     return out
 
 
+class Hypothesis(NamedTuple):
+    """One reading of a line from the CTC prefix beam search (``beam=W``; include/ocrvi.h, ``ocrvi_ctc_beam``).  ``log_prob`` is the device's
+    ``score``: the log-probability of the id string ``ids`` over the alignments the beam kept, a lower bound of its full probability
+    (``-ocrvi_ctc_loss``) and equal to it when nothing that leads to the string was ever pruned.  ``text`` is ``Tokenizer.decode`` of
+    ``ids``."""
+    text: str
+    log_prob: float
+    ids: Tuple[int, ...]
+
+
+def make_hypotheses(tokenizer: Tokenizer, ids, lens, score) -> List[List[Hypothesis]]:
+    """Host half of the beam search: the device's ``ids`` [B,nbest,T] / ``lens`` [B,nbest] / ``score`` [B,nbest] on the host -> one list
+    of ``Hypothesis`` per row, best first.  A missing hypothesis (``lens`` -1) is dropped, so a list may be shorter than nbest or empty.
+    Two id strings that ``Tokenizer.decode`` maps to one text (they differ in pad id 1 only, which decode drops) stay two hypotheses:
+    their probabilities are not added."""
+    ids, lens, score = np.asarray(ids), np.asarray(lens), np.asarray(score)
+    # only the valid ids become Python objects: one flat list, cut by the lengths
+    flat = ids[np.arange(ids.shape[2]) < lens[..., None]].tolist()
+    tokens = tokenizer.id_to_token
+    out, at = [], 0
+    for row_lens, row_score in zip(lens.tolist(), score.tolist()):
+        hyps = []
+        for n, s in zip(row_lens, row_score):
+            if n >= 0:
+                r = flat[at:at + n]
+                at += n
+                hyps.append(Hypothesis("".join([tokens[i] for i in r if i in tokens]), s, tuple(r)))
+        out.append(hyps)
+    return out
+
+
+def first_matching(hyps: Sequence[Hypothesis], accept) -> Optional[Hypothesis]:
+    """The first hypothesis whose text ``accept`` takes (a callable, or a compiled pattern: its ``fullmatch``), else ``hyps[0]``, else
+    ``None``.  The invoice use: ``first_matching(hyps, re.compile(r"\\d{10}(-\\d{3})?"))`` for a tax code, or a checksum function."""
+    ok = accept.fullmatch if hasattr(accept, "fullmatch") else accept
+    return next((h for h in hyps if ok(h.text)), hyps[0] if hyps else None)
+
+
+def check_beam(beam, nbest, T: Optional[int] = None, return_confidence: bool = False) -> None:
+    """The ``ValueError`` cases of ``beam=W`` (a no-op for ``beam=None``), raised before any device work."""
+    if beam is None:
+        return
+    if return_confidence:
+        raise ValueError("beam together with return_confidence=True: the confidences are defined on the greedy path")
+    if not (isinstance(beam, int) and isinstance(nbest, int)) or not 1 <= beam <= _lib.CTC_BEAM_MAX or not 1 <= nbest <= beam:
+        raise ValueError(f"beam {beam!r}, nbest {nbest!r}: need integers with 1 <= nbest <= beam <= {_lib.CTC_BEAM_MAX}")
+    if T is not None and T > _lib.CTC_BEAM_MAX_T:
+        raise ValueError(f"beam search takes at most T = {_lib.CTC_BEAM_MAX_T} steps, got {T}")
+
+
 class SVTRv2(HandleModel):
     _NAME = "SVTRv2"
     _CREATE, _DESTROY, _STATUS = "ocrvi_rec_create", "ocrvi_rec_destroy", "ocrvi_rec_status"
@@ -156,12 +206,42 @@ class SVTRv2(HandleModel):
         self.check_range()      # (the copies above synchronised the stream already)
         return make_recognitions(self.tokenizer, *rows, logp)
 
-    def decode_probs(self, log_probs: torch.Tensor, return_confidence: bool = False):
+    def beam_workspace_bytes(self, T: int, B: int, beam: int, num_classes: Optional[int] = None) -> int:
+        n = _lib.C.c_size_t(0)
+        _lib.check(_lib.load().ocrvi_ctc_beam_workspace_bytes(T, B, num_classes or self.tokenizer.num_classes, beam, _lib.C.byref(n)))
+        return int(n.value)
+
+    def enqueue_beam(self, log_probs, T, B, beam, nbest, ids, lens, score, ws, ws_bytes, stream, num_classes: Optional[int] = None) -> None:
+        """``ocrvi_ctc_beam`` on log_probs [T,B,C], enqueue-only: raw device pointers, sizes and a stream.  C is the model's class count
+        unless ``num_classes`` says otherwise (``decode_probs`` takes it from the tensor, as the greedy decode does)."""
+        _lib.check(_lib.load().ocrvi_ctc_beam(self._dev_index(), log_probs, T, B, num_classes or self.tokenizer.num_classes, self.blank_id,
+                                              beam, nbest, ids, lens, score, ws, ws_bytes, stream))
+
+    def _beam_hypotheses(self, lp: torch.Tensor, beam: int, nbest: int) -> List[List[Hypothesis]]:
+        T, B, Cn = lp.shape
+        d = dict(device=self.device)
+        ids = torch.empty((B, nbest, T), dtype=torch.int32, **d)
+        lens = torch.empty((B, nbest), dtype=torch.int32, **d)
+        score = torch.empty((B, nbest), dtype=torch.float64, **d)
+        ws = torch.empty(self.beam_workspace_bytes(T, B, beam, Cn), dtype=torch.uint8, **d)
+        self.enqueue_beam(lp.data_ptr(), T, B, beam, nbest, ids.data_ptr(), lens.data_ptr(), score.data_ptr(), ws.data_ptr(), ws.numel(),
+                          torch.cuda.current_stream(self.device).cuda_stream, Cn)
+        rows = [t.cpu().numpy() for t in (ids, lens, score)]
+        self.check_range()      # (the copies above synchronised the stream already)
+        return make_hypotheses(self.tokenizer, *rows)
+
+    def decode_probs(self, log_probs: torch.Tensor, return_confidence: bool = False, beam: Optional[int] = None, nbest: int = 1):
         """Greedy CTC decode of (T,B,C) log-probs (svtrv2.py:545-569): argmax, collapse repeats, drop blank on the
         device; id -> text (dropping pad id 1, tokenizer.py:73) on the host.  ``return_confidence=True``: a list of ``Recognition``
-        (``ocrvi_ctc_greedy_conf``) whose ``text`` are the strings returned otherwise."""
+        (``ocrvi_ctc_greedy_conf``) whose ``text`` are the strings returned otherwise.
+        ``beam=W``: the prefix beam search instead (``ocrvi_ctc_beam``): one list of ``Hypothesis`` per row, best first, at most ``nbest``
+        long, possibly empty.  ValueError, before any device work, for ``beam`` outside 1..64, ``nbest`` outside 1..beam, T > 1024 and
+        ``beam`` together with ``return_confidence=True``."""
+        check_beam(beam, nbest, log_probs.shape[0], return_confidence)
         lp = log_probs.to(device=self.device, dtype=torch.float32).contiguous()
         T, B, Cn = lp.shape
+        if beam is not None:
+            return self._beam_hypotheses(lp, beam, nbest)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         if return_confidence:
             am, ids, lens, blp, clp, span = self._conf_buffers(B, T)
@@ -175,21 +255,42 @@ class SVTRv2(HandleModel):
                                                 lens.data_ptr(), stream))
         return self._ids_to_text(ids, lens)
 
-    def decode_greedy(self, images: torch.Tensor, return_confidence: bool = False):
-        """forward + decode in one device pass (svtrv2.py:538-543).  ``return_confidence=True``: a list of ``Recognition``; the pass then
-        also stores the log-probabilities, which ``log_prob`` needs."""
+    def _run_conf(self, images: torch.Tensor):
+        """``ocrvi_rec_forward_conf`` with the log-probabilities stored -> (lp, ids, lens, char_lp, char_span) on the device."""
+        if images.dim() != 4 or images.shape[1] != 3:
+            raise ValueError(f"expected (B,3,H,W) input, got {tuple(images.shape)}")
+        x = images.to(device=self.device, dtype=torch.float32).contiguous()
+        B, _, H, W = x.shape
+        T = W // 4
+        ws = self._workspace(B, H, W)
+        lp = torch.empty((T, B, self.tokenizer.num_classes), dtype=torch.float32, device=self.device)
+        am, ids, lens, blp, clp, span = self._conf_buffers(B, T)
+        self.enqueue_forward_conf(x.data_ptr(), B, H, W, lp.data_ptr(), am.data_ptr(), ids.data_ptr(), lens.data_ptr(), blp.data_ptr(),
+                                  clp.data_ptr(), span.data_ptr(), ws.data_ptr(), ws.numel(),
+                                  torch.cuda.current_stream(self.device).cuda_stream)
+        return lp, ids, lens, clp, span
+
+    def decode_greedy_and_beam(self, images: torch.Tensor, beam: int, nbest: int = 1, return_confidence: bool = False):
+        """One forward, both decodes: (what ``decode_greedy(images, return_confidence)`` returns, what ``decode_greedy(images, beam=beam,
+        nbest=nbest)`` returns).  The greedy half comes from the same entry as without ``beam``; the pass also stores the
+        log-probabilities, which the beam search reads."""
+        check_beam(beam, nbest, images.shape[-1] // 4 if images.dim() == 4 else None)
         if return_confidence:
-            if images.dim() != 4 or images.shape[1] != 3:
-                raise ValueError(f"expected (B,3,H,W) input, got {tuple(images.shape)}")
-            x = images.to(device=self.device, dtype=torch.float32).contiguous()
-            B, _, H, W = x.shape
-            T = W // 4
-            ws = self._workspace(B, H, W)
-            lp = torch.empty((T, B, self.tokenizer.num_classes), dtype=torch.float32, device=self.device)
-            am, ids, lens, blp, clp, span = self._conf_buffers(B, T)
-            self.enqueue_forward_conf(x.data_ptr(), B, H, W, lp.data_ptr(), am.data_ptr(), ids.data_ptr(), lens.data_ptr(), blp.data_ptr(),
-                                      clp.data_ptr(), span.data_ptr(), ws.data_ptr(), ws.numel(),
-                                      torch.cuda.current_stream(self.device).cuda_stream)
-            return self._recognitions(lp, ids, lens, clp, span)
+            lp, ids, lens, clp, span = self._run_conf(images)
+            greedy = self._recognitions(lp, ids, lens, clp, span)
+        else:
+            lp, _, ids, lens = self._run(images, True, True)
+            greedy = self._ids_to_text(ids, lens)
+        return greedy, self._beam_hypotheses(lp, beam, nbest)
+
+    def decode_greedy(self, images: torch.Tensor, return_confidence: bool = False, beam: Optional[int] = None, nbest: int = 1):
+        """forward + decode in one device pass (svtrv2.py:538-543).  ``return_confidence=True``: a list of ``Recognition``; the pass then
+        also stores the log-probabilities, which ``log_prob`` needs.  ``beam=W``: the forward, then the prefix beam search on its
+        log-probabilities: lists of ``Hypothesis`` as ``decode_probs(..., beam=W, nbest=nbest)`` returns them."""
+        check_beam(beam, nbest, images.shape[-1] // 4 if images.dim() == 4 else None, return_confidence)
+        if beam is not None:
+            return self._beam_hypotheses(self._run(images, True, False)[0], beam, nbest)
+        if return_confidence:
+            return self._recognitions(*self._run_conf(images))
         _, _, ids, lens = self._run(images, False, True)
         return self._ids_to_text(ids, lens)
