@@ -204,6 +204,81 @@ int ocrvi_ctc_beam(int device, const float* log_probs, int T, int B, int C, int 
                    int32_t* ids, int32_t* lens, double* score, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Character n-gram language model: a backoff table over the recogniser's class ids, for ocrvi_ctc_beam_lm below.  No counterpart in the
+ * reference.
+ * ------------------------------------------------------------------------------------------------
+ *   Symbols.  Class ids 0..C-1, C = num_classes, 2 <= C <= 1024.  The blank id never occurs in a labelling; in an n-gram it stands for
+ *     begin of line (BOS = bos_id = the blank id) and is legal only as the FIRST symbol of a gram.  The 1-gram (BOS) is a context only: it
+ *     carries a backoff weight and its lp is 0 (a non-zero lp there would predict the blank, which is refused).  There is no end-of-line
+ *     term: a string's score does not depend on the line ending after it (out of scope).
+ *   Order.  N = order, 1 <= N <= OCRVI_LM_MAX_ORDER.  The context of the prediction that follows the labelling l is
+ *     ctx(l) = the last min(N-1, len(l)+1) symbols of BOS + l  (nothing for N = 1; (BOS) for the empty labelling when N >= 2).
+ *   Key.  The n-gram g_1..g_k (g_1 the oldest symbol, 1 <= k <= N) is the 63-bit key (k << 60) | sum_j g_j << (10 (j-1)).  Never zero, never
+ *     shared by two grams: the key is the gram, not a hash of it.
+ *   Slot.  16 bytes {uint64 key; float lp; float bo}: lp = ln p(g_k | g_1..g_k-1), bo = the ln backoff weight of the gram as a context.
+ *     Natural logarithms, finite float32, widened to float64 where they are used.
+ *   Table.  Open addressing over cap = 1 << log2cap slots, cap >= 2 * entries (and >= 2); home slot (key * 0x9e3779b97f4a7c15 mod 2^64)
+ *     >> (64 - log2cap); linear probing with wrap-around; key 0 = empty.  A gram is present iff a probe from its home meets its key before
+ *     an empty slot.
+ *   Blob.  A 48-byte header {uint32 magic 0x4d4c434f; uint32 version 1; int32 order, num_classes, bos_id, log2cap; uint64 entries;
+ *     double unk_lp; uint64 reserved}, then the cap slots.  Little endian.  ocrvi_lm_build inserts the grams in the order given.
+ *   Score.  lm(c | h) for a label c != blank and a context h of |h| symbols:  acc = 0;  for k = |h| down to 0:  if the gram h[-k:] + c
+ *     (the last k symbols of h, then c) is present: return acc + lp of it;  else if k >= 1 and the gram h[-k:] is present: acc = acc + bo
+ *     of it.  When the loop ends (the unigram of c is absent): return acc + unk_lp, unk_lp finite.  All sums float64, in this order.
+ *   String.  g(()) = 0, g(l + c) = g(l) + lm(c | ctx(l)): float64 sums in prefix order, so g is a function of the id string alone, bit
+ *     for bit.
+ * Host entries (no device, no GPU needed):
+ *   ocrvi_lm_build: n_grams grams, gram i = gram_ids[i][0 .. gram_lens[i]) of gram_ids [n_grams][OCRVI_LM_MAX_ORDER] int32 (the rest of a row
+ *     is ignored) with lp[i], bo[i] -> the blob.  blob == NULL: *blob_bytes = its size (after every check).  OCRVI_EINVAL with a message for
+ *     a gram given twice, a length outside 1..order, an id outside [0, num_classes), BOS anywhere but first, the blank as a predicted symbol
+ *     (the 1-gram (BOS) with lp != 0), a non-finite lp / bo / unk_lp, order outside 1..6, num_classes outside 2..1024, bos_id outside
+ *     [0, num_classes); OCRVI_ENOMEM when blob_capacity is short.
+ *   ocrvi_lm_score: ids[0..len) labels (not the blank, < num_classes: OCRVI_EINVAL otherwise) -> *total = g(ids) and, if per_char is not
+ *     NULL, per_char[q] = lm(ids[q] | ctx(ids[0..q))), float64.  Validates the blob as ocrvi_lm_create does.
+ *   ocrvi_lm_create: validates the WHOLE blob on the host (header fields and magic, size == 48 + 16 * cap, entries == occupied slots <=
+ *     cap / 2 -- so an empty slot exists and every probe ends --, every key's length tag in 1..order with no bit set beyond its symbols, ids
+ *     < num_classes, BOS only first, finite lp / bo / unk_lp, every key where a probe from its home finds it) and uploads the slots to
+ *     `device`: OCRVI_EINVAL with a message otherwise.  The kernel then never distrusts the table.  The handle owns the device copy, is
+ *     read-only afterwards and may serve any number of concurrent searches on its device.  ocrvi_lm_destroy(NULL) is a no-op. */
+#define OCRVI_LM_MAX_ORDER 6
+typedef struct ocrvi_lm ocrvi_lm;
+int ocrvi_lm_build(const int32_t* gram_ids, const int32_t* gram_lens, const float* lp, const float* bo, size_t n_grams, int order,
+                   int num_classes, int bos_id, double unk_lp, void* blob, size_t blob_capacity, size_t* blob_bytes);
+int ocrvi_lm_score(const void* blob, size_t blob_bytes, const int32_t* ids, int len, double* total, double* per_char);
+int ocrvi_lm_create(int device, const void* blob, size_t blob_bytes, ocrvi_lm** out);
+void ocrvi_lm_destroy(ocrvi_lm* h);
+
+/* ------------------------------------------------------------------------------------------------
+ * CTC prefix beam search with LM fusion (shallow fusion of the character n-gram model above; Hannun et al. 2014).  The definition is
+ * ocrvi_ctc_beam's, word for word, with three additions:
+ * ------------------------------------------------------------------------------------------------
+ *   Rank total.  An entry also carries g_i = g(l_i) and len_i = len(l_i); the start entry has g = 0, len = 0.  The rank total of (s, g, len)
+ *     is R = (s + alpha * g) + beta * len in float64: each product and each sum rounded on its own, no fused multiply-add.  alpha (LM
+ *     weight) and beta (length bonus per character) are finite, alpha >= 0.
+ *   Candidates.  The stay candidate of entry i keeps g_i and len_i; the extension by c has g_i + lm(c | ctx(l_i)) and len_i + 1.  pb', pnb',
+ *     the repeat rule and the merge by id-string identity with lse are exactly ocrvi_ctc_beam's; a merged extension adds only its acoustic
+ *     pnb' (the string is j's, so g and len already agree).  A candidate whose ACOUSTIC total lse(pb', pnb') is -inf is dropped.  Select
+ *     takes the W largest R, equal R by the smaller candidate index i*C + c; that order is the next step's rank order.
+ *   Outputs.  ids, lens as ocrvi_ctc_beam; score [B,nbest] float64 = R; ctc_score [B,nbest] float64 = s; lm_score [B,nbest] float64 = g.
+ *     A missing hypothesis has lens = -1, ids = -1 and -inf in all three.
+ * With alpha = beta = 0 and any valid model, ids, lens and score are ocrvi_ctc_beam's byte for byte, and ctc_score == score.
+ * lm_score is g(ids) exactly (the same doubles added in the same order as ocrvi_lm_score adds them).
+ * OCRVI_EINVAL before any launch, outputs untouched: every case of ocrvi_ctc_beam; a NULL handle or one ocrvi_lm_create did not return
+ * (or of another device); handle num_classes != C; handle bos_id != blank_id; alpha or beta not finite, or alpha < 0; a score array not
+ * 8-byte aligned.  workspace: ocrvi_ctc_beam_lm_workspace_bytes = ocrvi_ctc_beam's prefixes, then [B][beam][C] float64 (row `slot` of a
+ * beam row holds lm(c | ctx(l)) for every c, for the one live prefix l that owns the slot), each part rounded up to 256 bytes;
+ * OCRVI_ENOMEM when it is short.  Enqueue-only: one launch for all T steps, no allocation, no synchronisation, capturable; the same input
+ * gives the same bytes.
+ * One workgroup of 256 threads per row.  lm(c | ctx(l)) depends on the prefix alone: its C terms are looked up once, when an extension
+ * creates the prefix (16-byte probes of the read-only table; the unigram level sits in LDS), and a staying entry keeps its slot, so a
+ * candidate is two reads and two adds.  Selection: every class keeps the best candidate over the entries; a round is a workgroup arg-max
+ * over the classes, after which one wave scans the winner's class again, lane i the entry i. */
+int ocrvi_ctc_beam_lm_workspace_bytes(int T, int B, int C, int beam, size_t* bytes);
+int ocrvi_ctc_beam_lm(int device, const float* log_probs, int T, int B, int C, int blank_id, int beam, int nbest, const ocrvi_lm* lm,
+                      double alpha, double beta, int32_t* ids, int32_t* lens, double* score, double* ctc_score, double* lm_score,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Pre-processing on the device (the callers either side of the two models on the e2e path).
  * ------------------------------------------------------------------------------------------------ */
 /* Replaces the detection input normalisation of src/pipeline/pipeline2.py:312-314: images uint8 HWC

@@ -52,6 +52,7 @@ EXPORTS = [
     "ocrvi_rec_forward_conf", "ocrvi_ctc_greedy_conf", "ocrvi_test_ctc_logsoftmax_conf",
     "ocrvi_test_conv3_halo_raw", "ocrvi_test_bneck_tail_raw", "ocrvi_test_stem_pool_raw", "ocrvi_test_halo_plan",
     "ocrvi_ctc_beam_workspace_bytes", "ocrvi_ctc_beam",
+    "ocrvi_lm_build", "ocrvi_lm_score", "ocrvi_lm_create", "ocrvi_lm_destroy", "ocrvi_ctc_beam_lm_workspace_bytes", "ocrvi_ctc_beam_lm",
 ]
 PAGE_ENTRY = 4          # int64 fields of one page-table entry: (device address, height, width, 0) -- OCRVI_PAGE_ENTRY
 # ocrvi_det_eval's record: 13 slots of 8 bytes (OCRVI_DET_EVAL_*), the first six int64, the rest float64
@@ -62,6 +63,7 @@ CTC_LOSS_MAX_TARGET = 1024      # OCRVI_CTC_LOSS_MAX_TARGET
 EDIT_DISTANCE_MAX_LEN = 2048    # OCRVI_EDIT_DISTANCE_MAX_LEN
 CTC_BEAM_MAX = 64               # OCRVI_CTC_BEAM_MAX
 CTC_BEAM_MAX_T = 1024           # OCRVI_CTC_BEAM_MAX_T
+LM_MAX_ORDER = 6                # OCRVI_LM_MAX_ORDER
 CLAHE_WORKSPACE_BYTES = 16384   # OCRVI_CLAHE_WORKSPACE_BYTES
 ENHANCE_MIN_SIDE = 16           # the smallest page side the enhance entries take
 DB_TARGET_GT, DB_TARGET_MASK, DB_TARGET_THRESH = 0, 1, 2   # OCRVI_DB_TARGET_*: the map a fill job writes
@@ -206,6 +208,13 @@ def load() -> C.CDLL:
     lib.ocrvi_edit_distance.argtypes = [i32, i32p, i32, i32p, i32p, i32, i32p, i32, i32p, vp]
     lib.ocrvi_ctc_beam_workspace_bytes.argtypes = [i32, i32, i32, i32, C.POINTER(sz)]
     lib.ocrvi_ctc_beam.argtypes = [i32, f32p, i32, i32, i32, i32, i32, i32, i32p, i32p, vp, vp, sz, vp]
+    lib.ocrvi_lm_build.argtypes = [i32p, i32p, f32p, f32p, sz, i32, i32, i32, C.c_double, vp, sz, C.POINTER(sz)]
+    lib.ocrvi_lm_score.argtypes = [vp, sz, i32p, i32, C.POINTER(C.c_double), vp]
+    lib.ocrvi_lm_create.argtypes = [i32, vp, sz, C.POINTER(vp)]
+    lib.ocrvi_lm_destroy.argtypes = [vp]
+    lib.ocrvi_lm_destroy.restype = None
+    lib.ocrvi_ctc_beam_lm_workspace_bytes.argtypes = [i32, i32, i32, i32, C.POINTER(sz)]
+    lib.ocrvi_ctc_beam_lm.argtypes = [i32, f32p, i32, i32, i32, i32, i32, i32, vp, C.c_double, C.c_double, i32p, i32p, vp, vp, vp, vp, sz, vp]
     lib.ocrvi_enhance_init.argtypes = [i32]
     lib.ocrvi_enhance_tables.argtypes = [vp, sz, C.POINTER(sz)]
     lib.ocrvi_enhance_workspace_bytes.argtypes = [i32, i32, C.POINTER(sz)]
@@ -261,7 +270,7 @@ def load() -> C.CDLL:
     lib.ocrvi_prof_report.argtypes = [C.c_char_p, sz]
     for name in EXPORTS:
         fn = getattr(lib, name)
-        if name not in ("ocrvi_last_error", "ocrvi_det_destroy", "ocrvi_rec_destroy"):
+        if name not in ("ocrvi_last_error", "ocrvi_det_destroy", "ocrvi_rec_destroy", "ocrvi_lm_destroy"):
             fn.restype = i32
     if lib.ocrvi_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libocrvi ABI {lib.ocrvi_abi_version()} != binding {ABI_VERSION}: rebuild")

@@ -32,7 +32,7 @@ from . import _lib
 from .codec import IMAGE_BYTES, JPEG, PNG, format_of_info, imdecode, info_struct, parse_into, stream_buffer, table_entry
 from .pipeline import (DBPostProcessor, _check_crop, db_boxes_pages, enhance_init, enhance_workspace_bytes, find_document_quads,
                        four_point_geometry, overlay_paint_, overlay_segments, quad_crops)
-from .rec import check_beam, make_hypotheses, make_recognitions
+from .rec import check_beam, check_lm, make_hypotheses, make_lm_hypotheses, make_recognitions
 
 _ARENA_ALIGN = 256
 _STREAMS: Dict[int, Tuple[torch.cuda.Stream, torch.cuda.Stream]] = {}
@@ -139,18 +139,23 @@ class Engine:
     ``n`` long.  The recogniser graph then keeps the forward's log-probabilities in a device buffer [T, rec_batch, C] and launches
     ``ocrvi_ctc_beam`` on them after the forward, on the same stream (a sequential node); ids / lens / score of the hypotheses come back
     through pinned slots beside the greedy ones.  With ``beam=None`` the engine enqueues exactly what it always has.
+    ``lm=CharLM, lm_weight=a, len_bonus=b`` (the constructor's arguments only; legal only with ``beam``): ``ocrvi_ctc_beam_lm`` takes the
+    place of the ``ocrvi_ctc_beam`` node, on the same stream, and the lists hold ``rec.LMHypothesis``; the two extra score arrays come
+    back through pinned slots of their own.  The table is uploaded in the constructor, never inside a capture.  With ``lm=None`` the
+    engine enqueues exactly what it enqueues without the argument.
     The captured graphs hold the models' weights as they were: after reloading a model's weights, build a new Engine."""
 
     def __init__(self, det_model, rec_model, post_processor: DBPostProcessor, det_size: int = 960, rec_size: Tuple[int, int] = (32, 256),
                  det_chunk: int = 16, rec_batch: int = 256, max_pages: int = 256, graphs: bool = True, graph_cache: int = 16,
                  post_threads: int = 0, prob_hook=None, binary_head: bool = False, crop: str = "rect", annotate: bool = False,
-                 confidence: bool = False, beam: int = None, nbest: int = 1):
+                 confidence: bool = False, beam: int = None, nbest: int = 1, lm=None, lm_weight: float = 1.0, len_bonus: float = 0.0):
         rh, rw = int(rec_size[0]), int(rec_size[1])
         if rh <= 0 or rw <= 0 or rh % 16 or rw % 4:
             raise ValueError(f"rec_size {rec_size}: the height must be a multiple of 16 and the width of 4")
         if det_size <= 0 or det_chunk <= 0 or rec_batch <= 0 or max_pages <= 0 or graph_cache <= 0:
             raise ValueError("det_size, det_chunk, rec_batch, max_pages and graph_cache must be positive")
         check_beam(beam, nbest, rw // 4)
+        check_lm(lm, lm_weight, len_bonus, beam, rec_model.tokenizer.num_classes, rec_model.blank_id)
         self.det, self.rec, self.pp = det_model, rec_model, post_processor
         self.dev = det_model.device if det_model.device.index is not None else torch.device("cuda", det_model._dev_index())
         self.devi = det_model._dev_index()
@@ -204,13 +209,18 @@ class Engine:
             self.h_char_lp = [torch.empty((self.rec_batch, T), dtype=torch.float32).pin_memory() for _ in range(nslots)]
             self.h_char_span = [torch.empty((self.rec_batch, T, 2), dtype=torch.int32).pin_memory() for _ in range(nslots)]
         self.beam, self.nbest = beam, int(nbest)
+        self.lm, self.lm_weight, self.len_bonus = lm, float(lm_weight), float(len_bonus)
         if beam is not None:                       # the forward's log-probabilities stay on the device; the hypotheses come back
             C = rec_model.tokenizer.num_classes
             self.d_lp = torch.empty((T, self.rec_batch, C), dtype=torch.float32, **d)
-            self.d_beam_ws = torch.empty(max(rec_model.beam_workspace_bytes(T, self.rec_batch, beam), 1), dtype=torch.uint8, **d)
+            ws_bytes = rec_model.beam_workspace_bytes if lm is None else rec_model.beam_lm_workspace_bytes
+            self.d_beam_ws = torch.empty(max(ws_bytes(T, self.rec_batch, beam), 1), dtype=torch.uint8, **d)
             shapes = (((self.rec_batch, self.nbest, T), torch.int32), ((self.rec_batch, self.nbest), torch.int32),
                       ((self.rec_batch, self.nbest), torch.float64))
-            self.d_hyp = [torch.empty(sh, dtype=dt, **d) for sh, dt in shapes]         # ids, lens, score
+            if lm is not None:
+                shapes += (shapes[2], shapes[2])
+                lm.to(self.dev)
+            self.d_hyp = [torch.empty(sh, dtype=dt, **d) for sh, dt in shapes]         # ids, lens, score (with lm: ctc_score, lm_score)
             self.h_hyp = [[torch.empty(sh, dtype=dt).pin_memory() for sh, dt in shapes] for _ in range(nslots)]
         if self.crop == "quad":                    # oriented crops: a descriptor row (page, w, h, 0) and a matrix per crop instead of a rectangle
             self.d_qcrops = torch.zeros((self.rec_batch, 4), dtype=torch.int32, **d)
@@ -283,7 +293,10 @@ class Engine:
         else:
             self.rec.enqueue_forward(self.d_crops.data_ptr(), self.rec_batch, rh, rw, lp, self.d_am.data_ptr(), self.d_ids.data_ptr(),
                                      self.d_lens.data_ptr(), self.rec_ws.data_ptr(), self.rec_ws.numel(), st)
-        if self.beam is not None:
+        if self.lm is not None:
+            self.rec.enqueue_beam_lm(lp, rw // 4, self.rec_batch, self.beam, self.nbest, self.lm, self.lm_weight, self.len_bonus,
+                                     *[t.data_ptr() for t in self.d_hyp], self.d_beam_ws.data_ptr(), self.d_beam_ws.numel(), st)
+        elif self.beam is not None:
             ids, lens, score = self.d_hyp
             self.rec.enqueue_beam(lp, rw // 4, self.rec_batch, self.beam, self.nbest, ids.data_ptr(), lens.data_ptr(), score.data_ptr(),
                                   self.d_beam_ws.data_ptr(), self.d_beam_ws.numel(), st)
@@ -507,7 +520,8 @@ class Engine:
         self.stats["rec_wait_s"] += time.perf_counter() - t0
         n = len(tags)
         if self.beam is not None:
-            for (pg, b), h in zip(tags, make_hypotheses(self.rec.tokenizer, *[h[:n].numpy() for h in self.h_hyp[k]])):
+            make = make_hypotheses if self.lm is None else make_lm_hypotheses
+            for (pg, b), h in zip(tags, make(self.rec.tokenizer, *[h[:n].numpy() for h in self.h_hyp[k]])):
                 self._hyps[pg][b] = h
         if self.confidence:
             recs = make_recognitions(self.rec.tokenizer, self.h_ids[k][:n].numpy(), self.h_lens[k][:n].numpy(), self.h_char_lp[k][:n].numpy(),

@@ -31,7 +31,7 @@ from .codec import (IMAGE_BYTES, IMWRITE_FORMATS, JPEG_BYTES, JPEG_SUBSAMPLINGS,
                     jpeg_quant_tables, jpeg_table_entry, png_encode_sizes, png_info, png_info_struct, png_parse, png_parse_into, png_plan,
                     png_table_entry)
 from .det import DBNetPP
-from .rec import Hypothesis, Recognition, SVTRv2, check_beam
+from .rec import Hypothesis, Recognition, SVTRv2, check_beam, check_lm
 
 
 def _numpy_data_globals():
@@ -452,17 +452,20 @@ def recognize_text(model: SVTRv2, crop: np.ndarray, device: str = "cuda:0", img_
 
 
 def recognize_text_batch(model: SVTRv2, crops: List[np.ndarray], device: str = "cuda:0", img_size: Tuple[int, int] = (32, 256),
-                         batch_size: int = 32, return_confidence: bool = False, beam: Optional[int] = None, nbest: int = 1):
+                         batch_size: int = 32, return_confidence: bool = False, beam: Optional[int] = None, nbest: int = 1,
+                         lm=None, lm_weight: float = 1.0, len_bonus: float = 0.0):
     """pipeline2.py:144-168: batches of ``batch_size`` crops -> forward -> greedy CTC strings.  Empty crops become the all-zero tensor
     of :154-156.  ``return_confidence=True``: a list of ``rec.Recognition`` instead, whose ``text`` are those strings.
     ``beam=W``: one list of ``rec.Hypothesis`` per crop instead (``SVTRv2.decode_greedy(..., beam=W, nbest=nbest)``: best first, at most
-    ``nbest``); ValueError together with ``return_confidence=True``."""
+    ``nbest``); ValueError together with ``return_confidence=True``.  ``lm=CharLM`` (with ``beam``; ``lm_weight``, ``len_bonus``): the search
+    with the language model fused in, lists of ``rec.LMHypothesis``; ValueError as ``SVTRv2.decode_probs`` raises it."""
     check_beam(beam, nbest, img_size[1] // 4, return_confidence)
+    check_lm(lm, lm_weight, len_bonus, beam, model.tokenizer.num_classes, model.blank_id)
     texts = []
     for i in range(0, len(crops), batch_size):
         ts = [preprocess_for_recognition(c, img_size, device) for c in crops[i:i + batch_size]]
         if beam is not None:
-            texts.extend(model.decode_greedy(torch.stack(ts), beam=beam, nbest=nbest))
+            texts.extend(model.decode_greedy(torch.stack(ts), beam=beam, nbest=nbest, lm=lm, lm_weight=lm_weight, len_bonus=len_bonus))
             continue
         texts.extend(model.decode_greedy(torch.stack(ts), True) if return_confidence else model.decode_greedy(torch.stack(ts)))
     return texts
@@ -909,7 +912,8 @@ def save_result(path: str, image, boxes, texts=None, quality: int = 95, device: 
 
 def detect_and_recognize(original_image, det_model, rec_model, post_processor: DBPostProcessor, device: str = "cuda:0", det_size: int = 640,
                          rec_size: Tuple[int, int] = (32, 256), rec_batch_size: int = 64, binary_head: bool = False, quad=None,
-                         enhance: bool = False, crop: str = "rect", confidence: bool = False, beam: Optional[int] = None, nbest: int = 1):
+                         enhance: bool = False, crop: str = "rect", confidence: bool = False, beam: Optional[int] = None, nbest: int = 1,
+                         lm=None, lm_weight: float = 1.0, len_bonus: float = 0.0):
     """Steps 2 and 3 of the reference's per-image loop (pipeline2.py:306-352) with every stage on this library: resize + normalise on the
     device -> ``det_model`` -> ``post_processor`` on the host copy of the binary map -> boxes rescaled to the original image -> the
     bounding rectangle of each box cropped, resized and normalised on the device straight from the uploaded page -> ``rec_model`` greedy
@@ -925,9 +929,15 @@ def detect_and_recognize(original_image, det_model, rec_model, post_processor: D
     ``confidence=True``: the result gains a last element ``recs``, one ``rec.Recognition`` per box with ``recs[i].text == texts[i]``.
     ``beam=W``: ``texts`` stay the greedy strings; the result gains a last element (after ``recs`` when both are on), one list of
     ``rec.Hypothesis`` per box from the prefix beam search on the same forward's log-probabilities (best first, at most ``nbest``).
+    ``lm=CharLM`` (only with ``beam``; ``lm_weight``, ``len_bonus``): that search with the language model fused in (``ocrvi_ctc_beam_lm``);
+    the lists then hold ``rec.LMHypothesis``.
     Returns (rescaled_boxes [int32 (n_i, 2)], scores, texts); empty crops decode the all-zero tensor as pipeline2.py:154-156 does."""
     _check_crop(crop)
     check_beam(beam, nbest, rec_size[1] // 4)
+    lm_kw = {}                                               # (without lm the recogniser is called as it always was)
+    if lm is not None or lm_weight != 1.0 or len_bonus != 0.0:
+        check_lm(lm, lm_weight, len_bonus, beam, rec_model.tokenizer.num_classes, rec_model.blank_id)
+        lm_kw = dict(lm=lm, lm_weight=lm_weight, len_bonus=len_bonus)
     if isinstance(original_image, IMAGE_BYTES):              # a JPEG or PNG file's bytes: decoded on the device (``imdecode``)
         original_image = imdecode(original_image, device)
     page = original_image if isinstance(original_image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(original_image))
@@ -950,7 +960,7 @@ def detect_and_recognize(original_image, det_model, rec_model, post_processor: D
 
     def decode(batch):
         if beam is not None:
-            greedy, h = rec_model.decode_greedy_and_beam(batch, beam, nbest, confidence)
+            greedy, h = rec_model.decode_greedy_and_beam(batch, beam, nbest, confidence, **lm_kw)
             (recs if confidence else texts).extend(greedy)
             hyps.extend(h)
         elif confidence:
@@ -981,15 +991,16 @@ def detect_and_recognize(original_image, det_model, rec_model, post_processor: D
 
 def detect_and_recognize_pages(images, det_model, rec_model, post_processor: DBPostProcessor, device: str = "cuda:0", det_size: int = 640,
                                rec_size: Tuple[int, int] = (32, 256), rec_batch_size: int = 64, binary_head: bool = False, crop: str = "rect",
-                               confidence: bool = False, beam: Optional[int] = None, nbest: int = 1):
+                               confidence: bool = False, beam: Optional[int] = None, nbest: int = 1,
+                               lm=None, lm_weight: float = 1.0, len_bonus: float = 0.0):
     """``detect_and_recognize`` for a list of pages of any sizes in one call: a one-shot ``engine.Engine`` (pages bucketed by detector
     shape, detector chunks and recogniser batches across pages).  ``det_model`` / ``rec_model`` are the library's DBNetPP / SVTRv2 on
     ``device``.  Returns [(rescaled_boxes, scores, texts) per page, in input order], each what ``detect_and_recognize`` returns for that
-    page alone (``binary_head``, ``crop``, ``confidence``, ``beam`` and ``nbest`` as there; without ``beam`` the engine keeps no
-    log-probabilities, so ``log_prob`` is ``None``)."""
+    page alone (``binary_head``, ``crop``, ``confidence``, ``beam``, ``nbest``, ``lm``, ``lm_weight`` and ``len_bonus`` as there; without
+    ``beam`` the engine keeps no log-probabilities, so ``log_prob`` is ``None``)."""
     from .engine import Engine
     _check_crop(crop)
     if torch.device(device).type != "cuda" or _dev_index(device) != det_model._dev_index():
         raise ValueError(f"models live on cuda:{det_model._dev_index()}, not {device}")
     return Engine(det_model, rec_model, post_processor, det_size=det_size, rec_size=rec_size, rec_batch=rec_batch_size, binary_head=binary_head,
-                  crop=crop, confidence=confidence, beam=beam, nbest=nbest).run(images)
+                  crop=crop, confidence=confidence, beam=beam, nbest=nbest, lm=lm, lm_weight=lm_weight, len_bonus=len_bonus).run(images)

@@ -81,6 +81,47 @@ def make_hypotheses(tokenizer: Tokenizer, ids, lens, score) -> List[List[Hypothe
     return out
 
 
+class LMHypothesis(NamedTuple):
+    """One reading of a line from the beam search with a language model fused in (``beam=W, lm=...``; include/ocrvi.h,
+    ``ocrvi_ctc_beam_lm``).  ``score`` is the rank total the search ordered by, ``(log_prob + lm_weight * lm_log_prob) + len_bonus *
+    len(ids)``; ``log_prob`` is the acoustic part, what ``Hypothesis.log_prob`` is (a lower bound of ``-ocrvi_ctc_loss``); ``lm_log_prob``
+    is the model's score of ``ids`` (``CharLM.score``)."""
+    text: str
+    score: float
+    ids: Tuple[int, ...]
+    log_prob: float
+    lm_log_prob: float
+
+
+def make_lm_hypotheses(tokenizer: Tokenizer, ids, lens, score, ctc_score, lm_score) -> List[List[LMHypothesis]]:
+    """``make_hypotheses`` for the five outputs of ``ocrvi_ctc_beam_lm``."""
+    ctc, lms = np.asarray(ctc_score).tolist(), np.asarray(lm_score).tolist()
+    out = []
+    for b, row in enumerate(make_hypotheses(tokenizer, ids, lens, score)):
+        out.append([LMHypothesis(h.text, h.log_prob, h.ids, ctc[b][k], lms[b][k]) for k, h in enumerate(row)])
+    return out
+
+
+def check_lm(lm, lm_weight, len_bonus, beam, num_classes: Optional[int] = None, blank_id: Optional[int] = None) -> None:
+    """The ``ValueError`` cases of ``lm=...`` (a no-op for ``lm=None`` with the default weights), raised before any device work."""
+    if lm is None:
+        if lm_weight != 1.0 or len_bonus != 0.0:
+            raise ValueError("lm_weight / len_bonus without lm")
+        return
+    if beam is None:
+        raise ValueError("lm without beam: the language model is fused into the beam search (beam=W)")
+    from .lm import CharLM
+    if not isinstance(lm, CharLM):
+        raise ValueError(f"lm must be a CharLM, got {type(lm).__name__}")
+    ok = all(isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v) for v in (lm_weight, len_bonus))
+    if not ok or lm_weight < 0:
+        raise ValueError(f"lm_weight {lm_weight!r}, len_bonus {len_bonus!r}: need finite numbers, lm_weight >= 0")
+    if num_classes is not None and lm.num_classes != num_classes:
+        raise ValueError(f"the language model has {lm.num_classes} classes, the recogniser {num_classes}")
+    if blank_id is not None and lm.blank_id != blank_id:
+        raise ValueError(f"the language model's begin-of-line id {lm.blank_id} is not the recogniser's blank {blank_id}")
+
+
 def first_matching(hyps: Sequence[Hypothesis], accept) -> Optional[Hypothesis]:
     """The first hypothesis whose text ``accept`` takes (a callable, or a compiled pattern: its ``fullmatch``), else ``hyps[0]``, else
     ``None``.  The invoice use: ``first_matching(hyps, re.compile(r"\\d{10}(-\\d{3})?"))`` for a tax code, or a checksum function."""
@@ -217,12 +258,34 @@ class SVTRv2(HandleModel):
         _lib.check(_lib.load().ocrvi_ctc_beam(self._dev_index(), log_probs, T, B, num_classes or self.tokenizer.num_classes, self.blank_id,
                                               beam, nbest, ids, lens, score, ws, ws_bytes, stream))
 
-    def _beam_hypotheses(self, lp: torch.Tensor, beam: int, nbest: int) -> List[List[Hypothesis]]:
+    def beam_lm_workspace_bytes(self, T: int, B: int, beam: int, num_classes: Optional[int] = None) -> int:
+        n = _lib.C.c_size_t(0)
+        _lib.check(_lib.load().ocrvi_ctc_beam_lm_workspace_bytes(T, B, num_classes or self.tokenizer.num_classes, beam, _lib.C.byref(n)))
+        return int(n.value)
+
+    def enqueue_beam_lm(self, log_probs, T, B, beam, nbest, lm, lm_weight, len_bonus, ids, lens, score, ctc_score, lm_score, ws, ws_bytes, stream,
+                        num_classes: Optional[int] = None) -> None:
+        """``ocrvi_ctc_beam_lm``, enqueue-only like ``enqueue_beam``; ``lm`` a ``CharLM`` (its handle on this device is made on first use,
+        which uploads the table: do that before a graph capture with ``lm.to(device)``)."""
+        _lib.check(_lib.load().ocrvi_ctc_beam_lm(self._dev_index(), log_probs, T, B, num_classes or self.tokenizer.num_classes, self.blank_id,
+                                                 beam, nbest, lm.handle(self.device), float(lm_weight), float(len_bonus), ids, lens, score,
+                                                 ctc_score, lm_score, ws, ws_bytes, stream))
+
+    def _beam_hypotheses(self, lp: torch.Tensor, beam: int, nbest: int, lm=None, lm_weight: float = 1.0, len_bonus: float = 0.0):
         T, B, Cn = lp.shape
         d = dict(device=self.device)
         ids = torch.empty((B, nbest, T), dtype=torch.int32, **d)
         lens = torch.empty((B, nbest), dtype=torch.int32, **d)
         score = torch.empty((B, nbest), dtype=torch.float64, **d)
+        if lm is not None:
+            ctc, lms = torch.empty_like(score), torch.empty_like(score)
+            ws = torch.empty(self.beam_lm_workspace_bytes(T, B, beam, Cn), dtype=torch.uint8, **d)
+            self.enqueue_beam_lm(lp.data_ptr(), T, B, beam, nbest, lm, lm_weight, len_bonus, ids.data_ptr(), lens.data_ptr(), score.data_ptr(),
+                                 ctc.data_ptr(), lms.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(self.device).cuda_stream,
+                                 Cn)
+            rows = [t.cpu().numpy() for t in (ids, lens, score, ctc, lms)]
+            self.check_range()
+            return make_lm_hypotheses(self.tokenizer, *rows)
         ws = torch.empty(self.beam_workspace_bytes(T, B, beam, Cn), dtype=torch.uint8, **d)
         self.enqueue_beam(lp.data_ptr(), T, B, beam, nbest, ids.data_ptr(), lens.data_ptr(), score.data_ptr(), ws.data_ptr(), ws.numel(),
                           torch.cuda.current_stream(self.device).cuda_stream, Cn)
@@ -230,18 +293,23 @@ class SVTRv2(HandleModel):
         self.check_range()      # (the copies above synchronised the stream already)
         return make_hypotheses(self.tokenizer, *rows)
 
-    def decode_probs(self, log_probs: torch.Tensor, return_confidence: bool = False, beam: Optional[int] = None, nbest: int = 1):
+    def decode_probs(self, log_probs: torch.Tensor, return_confidence: bool = False, beam: Optional[int] = None, nbest: int = 1,
+                     lm=None, lm_weight: float = 1.0, len_bonus: float = 0.0):
         """Greedy CTC decode of (T,B,C) log-probs (svtrv2.py:545-569): argmax, collapse repeats, drop blank on the
         device; id -> text (dropping pad id 1, tokenizer.py:73) on the host.  ``return_confidence=True``: a list of ``Recognition``
         (``ocrvi_ctc_greedy_conf``) whose ``text`` are the strings returned otherwise.
         ``beam=W``: the prefix beam search instead (``ocrvi_ctc_beam``): one list of ``Hypothesis`` per row, best first, at most ``nbest``
         long, possibly empty.  ValueError, before any device work, for ``beam`` outside 1..64, ``nbest`` outside 1..beam, T > 1024 and
-        ``beam`` together with ``return_confidence=True``."""
+        ``beam`` together with ``return_confidence=True``.
+        ``lm=CharLM`` (with ``beam``): the search ranks by ``(log_prob + lm_weight * lm(ids)) + len_bonus * len(ids)``
+        (``ocrvi_ctc_beam_lm``) and the lists hold ``LMHypothesis``.  ValueError, before any device work, for ``lm`` without ``beam``, a
+        model whose class count or blank is not this tensor's / this recogniser's, and weights that are not finite or ``lm_weight < 0``."""
         check_beam(beam, nbest, log_probs.shape[0], return_confidence)
+        check_lm(lm, lm_weight, len_bonus, beam, log_probs.shape[2], self.blank_id)
         lp = log_probs.to(device=self.device, dtype=torch.float32).contiguous()
         T, B, Cn = lp.shape
         if beam is not None:
-            return self._beam_hypotheses(lp, beam, nbest)
+            return self._beam_hypotheses(lp, beam, nbest, lm, lm_weight, len_bonus)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         if return_confidence:
             am, ids, lens, blp, clp, span = self._conf_buffers(B, T)
@@ -270,26 +338,31 @@ class SVTRv2(HandleModel):
                                   torch.cuda.current_stream(self.device).cuda_stream)
         return lp, ids, lens, clp, span
 
-    def decode_greedy_and_beam(self, images: torch.Tensor, beam: int, nbest: int = 1, return_confidence: bool = False):
+    def decode_greedy_and_beam(self, images: torch.Tensor, beam: int, nbest: int = 1, return_confidence: bool = False,
+                               lm=None, lm_weight: float = 1.0, len_bonus: float = 0.0):
         """One forward, both decodes: (what ``decode_greedy(images, return_confidence)`` returns, what ``decode_greedy(images, beam=beam,
         nbest=nbest)`` returns).  The greedy half comes from the same entry as without ``beam``; the pass also stores the
-        log-probabilities, which the beam search reads."""
+        log-probabilities, which the beam search reads.  ``lm``, ``lm_weight``, ``len_bonus`` as ``decode_probs`` takes them."""
         check_beam(beam, nbest, images.shape[-1] // 4 if images.dim() == 4 else None)
+        check_lm(lm, lm_weight, len_bonus, beam, self.tokenizer.num_classes, self.blank_id)
         if return_confidence:
             lp, ids, lens, clp, span = self._run_conf(images)
             greedy = self._recognitions(lp, ids, lens, clp, span)
         else:
             lp, _, ids, lens = self._run(images, True, True)
             greedy = self._ids_to_text(ids, lens)
-        return greedy, self._beam_hypotheses(lp, beam, nbest)
+        return greedy, self._beam_hypotheses(lp, beam, nbest, lm, lm_weight, len_bonus)
 
-    def decode_greedy(self, images: torch.Tensor, return_confidence: bool = False, beam: Optional[int] = None, nbest: int = 1):
+    def decode_greedy(self, images: torch.Tensor, return_confidence: bool = False, beam: Optional[int] = None, nbest: int = 1,
+                      lm=None, lm_weight: float = 1.0, len_bonus: float = 0.0):
         """forward + decode in one device pass (svtrv2.py:538-543).  ``return_confidence=True``: a list of ``Recognition``; the pass then
         also stores the log-probabilities, which ``log_prob`` needs.  ``beam=W``: the forward, then the prefix beam search on its
-        log-probabilities: lists of ``Hypothesis`` as ``decode_probs(..., beam=W, nbest=nbest)`` returns them."""
+        log-probabilities: lists of ``Hypothesis`` as ``decode_probs(..., beam=W, nbest=nbest)`` returns them (of ``LMHypothesis`` with
+        ``lm``)."""
         check_beam(beam, nbest, images.shape[-1] // 4 if images.dim() == 4 else None, return_confidence)
+        check_lm(lm, lm_weight, len_bonus, beam, self.tokenizer.num_classes, self.blank_id)
         if beam is not None:
-            return self._beam_hypotheses(self._run(images, True, False)[0], beam, nbest)
+            return self._beam_hypotheses(self._run(images, True, False)[0], beam, nbest, lm, lm_weight, len_bonus)
         if return_confidence:
             return self._recognitions(*self._run_conf(images))
         _, _, ids, lens = self._run(images, False, True)
