@@ -32,7 +32,7 @@ from . import _lib
 from .codec import IMAGE_BYTES, JPEG, PNG, format_of_info, imdecode, info_struct, parse_into, stream_buffer, table_entry
 from .pipeline import (DBPostProcessor, _check_crop, db_boxes_pages, enhance_init, enhance_workspace_bytes, find_document_quads,
                        four_point_geometry, overlay_paint_, overlay_segments, quad_crops)
-from .rec import check_beam, check_lm, make_hypotheses, make_lm_hypotheses, make_recognitions
+from .rec import check_beam, check_lm, make_recognitions
 
 _ARENA_ALIGN = 256
 _STREAMS: Dict[int, Tuple[torch.cuda.Stream, torch.cuda.Stream]] = {}
@@ -213,12 +213,10 @@ class Engine:
         if beam is not None:                       # the forward's log-probabilities stay on the device; the hypotheses come back
             C = rec_model.tokenizer.num_classes
             self.d_lp = torch.empty((T, self.rec_batch, C), dtype=torch.float32, **d)
-            ws_bytes = rec_model.beam_workspace_bytes if lm is None else rec_model.beam_lm_workspace_bytes
-            self.d_beam_ws = torch.empty(max(ws_bytes(T, self.rec_batch, beam), 1), dtype=torch.uint8, **d)
-            shapes = (((self.rec_batch, self.nbest, T), torch.int32), ((self.rec_batch, self.nbest), torch.int32),
-                      ((self.rec_batch, self.nbest), torch.float64))
+            ws_bytes, shapes, self._enqueue_beam, self._make_hyps = rec_model._beam_search(T, self.rec_batch, beam, self.nbest, lm,
+                                                                                           self.lm_weight, self.len_bonus)
+            self.d_beam_ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, **d)
             if lm is not None:
-                shapes += (shapes[2], shapes[2])
                 lm.to(self.dev)
             self.d_hyp = [torch.empty(sh, dtype=dt, **d) for sh, dt in shapes]         # ids, lens, score (with lm: ctc_score, lm_score)
             self.h_hyp = [[torch.empty(sh, dtype=dt).pin_memory() for sh, dt in shapes] for _ in range(nslots)]
@@ -293,13 +291,8 @@ class Engine:
         else:
             self.rec.enqueue_forward(self.d_crops.data_ptr(), self.rec_batch, rh, rw, lp, self.d_am.data_ptr(), self.d_ids.data_ptr(),
                                      self.d_lens.data_ptr(), self.rec_ws.data_ptr(), self.rec_ws.numel(), st)
-        if self.lm is not None:
-            self.rec.enqueue_beam_lm(lp, rw // 4, self.rec_batch, self.beam, self.nbest, self.lm, self.lm_weight, self.len_bonus,
-                                     *[t.data_ptr() for t in self.d_hyp], self.d_beam_ws.data_ptr(), self.d_beam_ws.numel(), st)
-        elif self.beam is not None:
-            ids, lens, score = self.d_hyp
-            self.rec.enqueue_beam(lp, rw // 4, self.rec_batch, self.beam, self.nbest, ids.data_ptr(), lens.data_ptr(), score.data_ptr(),
-                                  self.d_beam_ws.data_ptr(), self.d_beam_ws.numel(), st)
+        if self.beam is not None:
+            self._enqueue_beam(lp, [t.data_ptr() for t in self.d_hyp], self.d_beam_ws.data_ptr(), self.d_beam_ws.numel(), st)
 
     def _run_det(self, n, H, W):
         """Steps 2 and 3 of a chunk on the detector stream: the cached graph of (H, W, n), or an eager launch that is captured after it."""
@@ -520,8 +513,7 @@ class Engine:
         self.stats["rec_wait_s"] += time.perf_counter() - t0
         n = len(tags)
         if self.beam is not None:
-            make = make_hypotheses if self.lm is None else make_lm_hypotheses
-            for (pg, b), h in zip(tags, make(self.rec.tokenizer, *[h[:n].numpy() for h in self.h_hyp[k]])):
+            for (pg, b), h in zip(tags, self._make_hyps(self.rec.tokenizer, *[h[:n].numpy() for h in self.h_hyp[k]])):
                 self._hyps[pg][b] = h
         if self.confidence:
             recs = make_recognitions(self.rec.tokenizer, self.h_ids[k][:n].numpy(), self.h_lens[k][:n].numpy(), self.h_char_lp[k][:n].numpy(),

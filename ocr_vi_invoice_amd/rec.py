@@ -271,27 +271,29 @@ class SVTRv2(HandleModel):
                                                  beam, nbest, lm.handle(self.device), float(lm_weight), float(len_bonus), ids, lens, score,
                                                  ctc_score, lm_score, ws, ws_bytes, stream))
 
+    def _beam_search(self, T: int, B: int, beam: int, nbest: int, lm=None, lm_weight: float = 1.0, len_bonus: float = 0.0,
+                     num_classes: Optional[int] = None):
+        """What tells the two searches apart, for ``_beam_hypotheses`` and the engine: (the workspace bytes, the outputs' (shape, dtype),
+        ``enqueue(log_probs, outputs, ws, ws_bytes, stream)``, the ``make_*hypotheses`` that reads the outputs).  ``enqueue`` takes raw
+        device pointers, ``outputs`` a list of them in the order of the shapes: ids, lens, score (with ``lm``: ctc_score, lm_score)."""
+        row = ((B, nbest), torch.float64)
+        outputs = (((B, nbest, T), torch.int32), ((B, nbest), torch.int32), row)                     # ids, lens, score
+        if lm is None:
+            return (self.beam_workspace_bytes(T, B, beam, num_classes), outputs,
+                    lambda lp, outs, *ws: self.enqueue_beam(lp, T, B, beam, nbest, *outs, *ws, num_classes), make_hypotheses)
+        return (self.beam_lm_workspace_bytes(T, B, beam, num_classes), outputs + (row, row),         # ctc_score, lm_score
+                lambda lp, outs, *ws: self.enqueue_beam_lm(lp, T, B, beam, nbest, lm, lm_weight, len_bonus, *outs, *ws, num_classes),
+                make_lm_hypotheses)
+
     def _beam_hypotheses(self, lp: torch.Tensor, beam: int, nbest: int, lm=None, lm_weight: float = 1.0, len_bonus: float = 0.0):
         T, B, Cn = lp.shape
-        d = dict(device=self.device)
-        ids = torch.empty((B, nbest, T), dtype=torch.int32, **d)
-        lens = torch.empty((B, nbest), dtype=torch.int32, **d)
-        score = torch.empty((B, nbest), dtype=torch.float64, **d)
-        if lm is not None:
-            ctc, lms = torch.empty_like(score), torch.empty_like(score)
-            ws = torch.empty(self.beam_lm_workspace_bytes(T, B, beam, Cn), dtype=torch.uint8, **d)
-            self.enqueue_beam_lm(lp.data_ptr(), T, B, beam, nbest, lm, lm_weight, len_bonus, ids.data_ptr(), lens.data_ptr(), score.data_ptr(),
-                                 ctc.data_ptr(), lms.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(self.device).cuda_stream,
-                                 Cn)
-            rows = [t.cpu().numpy() for t in (ids, lens, score, ctc, lms)]
-            self.check_range()
-            return make_lm_hypotheses(self.tokenizer, *rows)
-        ws = torch.empty(self.beam_workspace_bytes(T, B, beam, Cn), dtype=torch.uint8, **d)
-        self.enqueue_beam(lp.data_ptr(), T, B, beam, nbest, ids.data_ptr(), lens.data_ptr(), score.data_ptr(), ws.data_ptr(), ws.numel(),
-                          torch.cuda.current_stream(self.device).cuda_stream, Cn)
-        rows = [t.cpu().numpy() for t in (ids, lens, score)]
+        ws_bytes, outputs, enqueue, make = self._beam_search(T, B, beam, nbest, lm, lm_weight, len_bonus, Cn)
+        outs = [torch.empty(sh, dtype=dt, device=self.device) for sh, dt in outputs]
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+        enqueue(lp.data_ptr(), [t.data_ptr() for t in outs], ws.data_ptr(), ws.numel(), torch.cuda.current_stream(self.device).cuda_stream)
+        rows = [t.cpu().numpy() for t in outs]
         self.check_range()      # (the copies above synchronised the stream already)
-        return make_hypotheses(self.tokenizer, *rows)
+        return make(self.tokenizer, *rows)
 
     def decode_probs(self, log_probs: torch.Tensor, return_confidence: bool = False, beam: Optional[int] = None, nbest: int = 1,
                      lm=None, lm_weight: float = 1.0, len_bonus: float = 0.0):

@@ -22,6 +22,10 @@ def _path_rows(path, C, hit=0.0, miss=NINF):
     return y
 
 
+def rows3_workspace():
+    return np.ascontiguousarray(np.stack([BR.make(s, 140, 6, 2.0) for s in (50, 52, 58)], 1))
+
+
 def _build():
     cases = []
     add = lambda name, y, blank, W, nbest: cases.append((name, y, blank, W, nbest))  # noqa: E731
@@ -64,6 +68,8 @@ def _build():
     add("text_like", _one(BR.text_like(39, 80, 232, 8.0)), 0, 8, 4)
     # both prefix tables of (W = 64, T = 300) are past 32 KiB: they live in the workspace, not in LDS
     add("T300_C8_W64_workspace", _one(BR.make(40, 300, 8, 2.0)), 0, 64, 8)
+    # the same path with three rows: each takes its own part of the workspace (2 * 64 * 140 * 2 = 35 840 bytes a row)
+    add("rows3_T140_C6_W64_workspace", rows3_workspace(), 0, 64, 8)
     # 6. row independence: five different rows in one launch (the GPU test also launches each alone)
     add("rows5", np.ascontiguousarray(np.stack([BR.make(s, 12, 4, 1.5) for s in (6, 35, 308, 7, 8)], 1)), 0, 3, 3)
     return cases

@@ -133,6 +133,7 @@ def _build():
     add("text_like_W8", _one(BR.text_like(39, 80, 232, 8.0)), 0, 8, 4, "trained_o4", 0.5, 1.0)
     add("text_like_W64", _one(BR.text_like(73, 80, 232, 6.0, noise=2.0)), 0, 64, 16, "trained_o4", 0.5, 1.0)
     add("T300_C8_W64_workspace", _one(BR.make(40, 300, 8, 2.0)), 0, 64, 8, "rand8_o4", 0.4, 0.1)
+    add("rows3_T140_C6_W64_workspace", CC.rows3_workspace(), 0, 64, 8, "rand6_o3", 0.4, 0.1)   # three rows' prefix tables and LM rows
     add("C2_T20_W8", _one(BR.make(38, 20, 2, 1.0)), 0, 8, 8, "rand2_o3", 1.0, 0.5)
     add("T64_C40_W16", _one(BR.make(34, 64, 40, 3.0)), 0, 16, 16, "rand40_o3", 0.9, -0.3)
     add("T65_C40_W16_blank39", _one(BR.make(35, 65, 40, 3.0)), 39, 16, 16, "rand40_o3_blank39", 0.9, 0.3)

@@ -127,7 +127,10 @@ def test_exports_header_and_abi():
     src = open(os.path.join(ROOT, "ocr_vi_invoice_amd", "csrc", "ctc_beam.hip")).read()
     for name in NEW_EXPORTS:
         assert re.search(r'extern "C" int %s\(' % name, src), name
-    assert "ctc_beam.hip" in open(os.path.join(ROOT, "ocr_vi_invoice_amd", "csrc", "Makefile")).read()
+    mk = open(os.path.join(ROOT, "ocr_vi_invoice_amd", "csrc", "Makefile")).read()
+    assert "ctc_beam.hip" in mk and "ctc_beam_core.h" in re.search(r"^HDRS\s*=(.*)$", mk, re.M).group(1)   # an edit rebuilds both objects
+    lm_src = open(os.path.join(ROOT, "ocr_vi_invoice_amd", "csrc", "ctc_beam_lm.hip")).read()
+    assert all('#include "ctc_beam_core.h"' in t for t in (src, lm_src))
     lib = _lib.load()                                                   # the built library (there is no other way to have the symbols)
     assert all(hasattr(lib, n) for n in NEW_EXPORTS) and lib.ocrvi_abi_version() == 5
 

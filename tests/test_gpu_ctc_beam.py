@@ -145,12 +145,14 @@ def test_case_equals_the_reference_and_keeps_the_invariants(name):
 
 
 def test_rows_are_independent():
-    """Five different rows in one launch against each launched alone; 300 copies of two rows (more rows than CUs)."""
-    _, y, blank, W, nbest = CC.BY_NAME["rows5"]
-    together = _got("rows5")
-    for b in range(y.shape[1]):
-        alone = run_beam(np.ascontiguousarray(y[:, b:b + 1]), blank, W, nbest)
-        assert all(np.array_equal(a[0], t[b]) for a, t in zip(alone, together)), b
+    """Five different rows in one launch against each launched alone, and three whose prefix tables are in the workspace; 300 copies of
+    two rows (more rows than CUs)."""
+    for name in ("rows5", "rows3_T140_C6_W64_workspace"):
+        _, y, blank, W, nbest = CC.BY_NAME[name]
+        together = _got(name)
+        for b in range(y.shape[1]):
+            alone = run_beam(np.ascontiguousarray(y[:, b:b + 1]), blank, W, nbest)
+            assert all(np.array_equal(a[0], t[b]) and a[0].tobytes() == t[b].tobytes() for a, t in zip(alone, together)), (name, b)
     _, g, gblank, _, _ = CC.BY_NAME["golden_W8"]
     two = run_beam(g, gblank, 8, 4)
     many = run_beam(np.ascontiguousarray(np.tile(g, (1, 150, 1))), gblank, 8, 4)

@@ -184,12 +184,14 @@ def test_alpha_beta_zero_gives_the_bytes_of_ctc_beam(name):
 
 
 def test_rows_are_independent():
-    """Five different rows in one launch against each launched alone; 300 copies of two rows (more rows than CUs)."""
-    _, y, blank, W, nbest, tname, alpha, beta = LC.BY_NAME["rows5"]
-    together = _got("rows5")
-    for b in range(y.shape[1]):
-        alone = run_beam_lm(np.ascontiguousarray(y[:, b:b + 1]), blank, W, nbest, LC.table(tname), alpha, beta)
-        assert all(np.array_equal(a[0], t[b]) for a, t in zip(alone, together)), b
+    """Five different rows in one launch against each launched alone, and three whose prefix tables are in the workspace; 300 copies of
+    two rows (more rows than CUs)."""
+    for name in ("rows5", "rows3_T140_C6_W64_workspace"):
+        _, y, blank, W, nbest, tname, alpha, beta = LC.BY_NAME[name]
+        together = _got(name)
+        for b in range(y.shape[1]):
+            alone = run_beam_lm(np.ascontiguousarray(y[:, b:b + 1]), blank, W, nbest, LC.table(tname), alpha, beta)
+            assert all(np.array_equal(a[0], t[b]) and a[0].tobytes() == t[b].tobytes() for a, t in zip(alone, together)), (name, b)
     _, g, gblank, _, _, gt, ga, gb = LC.BY_NAME["golden_W8"]
     two = run_beam_lm(g, gblank, 8, 4, LC.table(gt), ga, gb)
     many = run_beam_lm(np.ascontiguousarray(np.tile(g, (1, 150, 1))), gblank, 8, 4, LC.table(gt), ga, gb)
