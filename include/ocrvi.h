@@ -1310,6 +1310,47 @@ int ocrvi_doc_histogram(int device, const uint8_t* src, int work_h, int ww, int3
 int ocrvi_doc_otsu(int device, const uint8_t* smooth, const int32_t* hist, int work_h, int ww, int polarity, int32_t* thr, void* stream);
 int ocrvi_doc_mask_bits(int device, const uint8_t* smooth, int work_h, int ww, const int32_t* thr, uint32_t* bits, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Skew estimate: by how much a page is rotated, from the page alone, and the corners that straighten it.  The reference has no such
+ * step; it sits where `--preprocess` sits, for pages whose border the document finder cannot see (a flatbed or feeder scan fills the
+ * frame).  A projection-profile search: text lines binned along the right slope give a profile of sharp peaks, whose sum of squares is
+ * maximal.  Integer arithmetic throughout; tests/skew_ref.py restates every stage and must agree exactly.  work_h (8 .. 512), ww, ratio
+ * and the bounds are those of ocrvi_doc_working_size; G is the document finder's `grey` stage, unchanged.
+ *   edges    d = |G[i][min(j+1, ww-1)] - G[i][max(j-1, 0)]|;  E[i][j] = d >= OCRVI_SKEW_FLOOR ? d : 0  (the horizontal central difference,
+ *            replicated border: horizontal rules contribute nothing, vertical rules the same to every row)
+ *   offset   for the slope index k in -OCRVI_SKEW_K .. OCRVI_SKEW_K and column j:  o(j, k) = ((j - (ww >> 1)) * k + 256) >> OCRVI_SKEW_SHIFT,
+ *            an arithmetic shift (a floor; the product may be negative)
+ *   profile  P_k[r] = the sum of E[i][j] over all (i, j) with i - o(j, k) == r, for every integer r  (an int32: 255 * 8192 < 2^31)
+ *   score    S_k = the sum over r of P_k[r]^2, an exact uint64 (< 2^54), independent of the order;  scores[k + OCRVI_SKEW_K] = S_k
+ *   pick     (host) the k of maximal S_k; among equals the smallest |k|; of -k and +k, +k.  angle_deg = atan(k / 512.0) * 180 / pi and
+ *            gain = double(S_best) / double(S_0) in double; when S_0 == 0 the gain is 1.0 if S_best == 0 and +inf otherwise.  A constant
+ *            page gives k = 0.  A text line of image slope tan(theta), y pointing down, is picked at k ~ 512 tan(theta): the range is
+ *            +-14.04 degrees in steps of 0.112 degrees.
+ *   quad     (host, double, no fused multiply-add, in this order)  t = k / 512.0, c = 1 / sqrt(1 + t t), s = t c;  centre (cx, cy) =
+ *            ((w-1) / 2, (h-1) / 2);  for the page's corners (0,0) (w,0) (w,h) (0,h):  dx = x - cx, dy = y - cy, a = dx c + dy s,
+ *            b = dy c - dx s;  the quad is (cx + a c - b s, cy + a s + b c) for (a, b) = (amin,bmin) (amax,bmin) (amax,bmax) (amin,bmax):
+ *            the upright rectangle of the deskewed frame that encloses the whole page, so no content is lost and the wedges outside the
+ *            page are the warp's 0.  ocrvi_four_point_transform orders these corners as given and decides the output size; k = 0 gives
+ *            the page's own corners and its own size.
+ * The device entries are enqueue-only on `stream` (no allocation, no synchronisation); pointers are DEVICE memory unless stated. */
+#define OCRVI_SKEW_K 128
+#define OCRVI_SKEW_SHIFT 9
+#define OCRVI_SKEW_FLOOR 8
+#define OCRVI_SKEW_ANGLES 257
+/* Host only: the workspace of ocrvi_skew_scores_pages for n pages (1 .. 65535) whose working widths are at most ww_cap. */
+int ocrvi_skew_sizes(int n, int work_h, int ww_cap, size_t* workspace_bytes);
+/* grey -> edges -> scores for n pages of their own sizes: `pages` is a page table (OCRVI_PAGE_ENTRY), read when the kernels run; page i's
+ * scores are scores[i][0 .. 256].  An invalid entry, a side above 16384 or a working width outside [8, ww_cap] leaves the page's 257 scores
+ * zero and touches nothing else.  workspace: 16-byte aligned; scores: 8-byte aligned. */
+int ocrvi_skew_scores_pages(int device, const int64_t* pages, int n, int work_h, int ww_cap, uint64_t* scores /*[n][257]*/, void* workspace,
+                            size_t workspace_bytes, void* stream);
+/* The stages one by one, on row-major arrays: grey uint8 [work_h][ww] -> edges (edges != grey); edges of ANY values -> scores [257]. */
+int ocrvi_skew_edges_u8(int device, const uint8_t* grey, int work_h, int ww, uint8_t* edges /*[work_h][ww]*/, void* stream);
+int ocrvi_skew_scores(int device, const uint8_t* edges /*[work_h][ww]*/, int work_h, int ww, uint64_t* scores /*[257]*/, void* stream);
+/* Host only: pick and quad as defined above.  scores: HOST [257];  quad: float64 [4][2] of (x, y);  1 <= h, w <= 16384, |k| <= 128. */
+int ocrvi_skew_pick(const uint64_t* scores, int32_t* k, double* angle_deg, double* gain);
+int ocrvi_skew_quad(int h, int w, int k, double* quad /*[4][2]*/);
+
 /* Per-launch HIP-event profiler (process-global, off by default).  While enabled every MFMA / bandwidth kernel launch
  * of the graphs above is bracketed by two events recorded on its launch stream.  ocrvi_prof_report synchronises those
  * events and writes a JSON object {tag: {launches, ms, flops, bytes}} (algorithmic FLOPs / bytes per tag) into buf. */

@@ -53,6 +53,7 @@ EXPORTS = [
     "ocrvi_test_conv3_halo_raw", "ocrvi_test_bneck_tail_raw", "ocrvi_test_stem_pool_raw", "ocrvi_test_halo_plan",
     "ocrvi_ctc_beam_workspace_bytes", "ocrvi_ctc_beam",
     "ocrvi_lm_build", "ocrvi_lm_score", "ocrvi_lm_create", "ocrvi_lm_destroy", "ocrvi_ctc_beam_lm_workspace_bytes", "ocrvi_ctc_beam_lm",
+    "ocrvi_skew_sizes", "ocrvi_skew_scores_pages", "ocrvi_skew_edges_u8", "ocrvi_skew_scores", "ocrvi_skew_pick", "ocrvi_skew_quad",
 ]
 PAGE_ENTRY = 4          # int64 fields of one page-table entry: (device address, height, width, 0) -- OCRVI_PAGE_ENTRY
 # ocrvi_det_eval's record: 13 slots of 8 bytes (OCRVI_DET_EVAL_*), the first six int64, the rest float64
@@ -80,6 +81,7 @@ OVERLAY_PRIM = 8                # int32 fields of one overlay primitive -- OCRVI
 OVERLAY_MAX_COORD = 16384       # OCRVI_OVERLAY_MAX_COORD: page sides 1..16384, endpoints within +-16384
 DOC_POLARITIES = {"auto": 0, "bright": 1, "dark": 2}   # OCRVI_DOC_AUTO / _BRIGHT / _DARK
 DOC_WORK_H = 500                # the reference's working height (scanner.py:85)
+SKEW_K, SKEW_ANGLES = 128, 257  # OCRVI_SKEW_K, OCRVI_SKEW_ANGLES
 
 
 class DetCfg(C.Structure):
@@ -254,6 +256,12 @@ def load() -> C.CDLL:
     lib.ocrvi_doc_histogram.argtypes = [i32, vp, i32, i32, vp, vp]
     lib.ocrvi_doc_otsu.argtypes = [i32, vp, vp, i32, i32, i32, vp, vp]
     lib.ocrvi_doc_mask_bits.argtypes = [i32, vp, i32, i32, vp, vp, vp]
+    lib.ocrvi_skew_sizes.argtypes = [i32, i32, i32, C.POINTER(sz)]
+    lib.ocrvi_skew_scores_pages.argtypes = [i32, vp, i32, i32, i32, vp, vp, sz, vp]
+    lib.ocrvi_skew_edges_u8.argtypes = [i32, vp, i32, i32, vp, vp]
+    lib.ocrvi_skew_scores.argtypes = [i32, vp, i32, i32, vp, vp]
+    lib.ocrvi_skew_pick.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.ocrvi_skew_quad.argtypes = [i32, i32, i32, vp]
     lib.ocrvi_overlay_segments.argtypes = [vp, vp, vp, vp, vp, i32, C.c_uint32, C.c_uint32, i32, vp, C.c_int64, vp, C.c_int64, vp,
                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.ocrvi_overlay_pages.argtypes = [i32, vp, i32, vp, vp, vp, i32, i32, vp]

@@ -4,47 +4,15 @@
 // enqueue-only on its stream: no allocation, no synchronisation.  The contour half runs on the host (dbpost.hip, ocrvi_document_contour).
 #include <algorithm>
 
-#include "common.h"
+#include "docfind.h"
 
 namespace ocrvi {
 namespace {
 
-constexpr int MAX_SIDE = 16384;      // page sides: a box of the downscale then sums to less than 2^31
-constexpr int MIN_WW = 8, MAX_WW = 8192, MIN_WORK_H = 8, MAX_WORK_H = 512;
+// (the bounds, the page table and the grey stage's launch are shared with skew.hip: docfind.h)
+constexpr int MAX_SIDE = DOC_MAX_SIDE;
+constexpr int MIN_WW = DOC_MIN_WW, MAX_WW = DOC_MAX_WW, MIN_WORK_H = DOC_MIN_WORK_H, MAX_WORK_H = DOC_MAX_WORK_H;
 constexpr int GREY_COLS = 8192;      // source columns whose sums one LDS pass of grey_kernel holds
-
-// Where a kernel's pages come from: a page table in device memory (read when the kernel runs), or, table == nullptr, one image given
-// directly (the per-stage entries): ptr / h / w its pixels and size, ww its working width.
-struct Pages {
-    const int64_t* table;
-    const uint8_t* ptr;
-    int h, w, ww;
-};
-struct Geom {
-    const uint8_t* ptr;
-    int H, W, ww;
-};
-
-__host__ __device__ inline int working_width(int H, int W, int work_h) {
-    const double ratio = (double)H / (double)work_h;       // scanner.py:85-86: ratio = height / 500.0, int(width / ratio)
-    const double v = (double)W / ratio;
-    return v >= 1e9 ? 1000000000 : (int)v;
-}
-
-// false: the page is not processed (an invalid table entry, a side above MAX_SIDE, a working width outside [8, ww_cap])
-__device__ inline bool page_geom(const Pages& p, int page, int work_h, int ww_cap, Geom& g) {
-    if (!p.table) {
-        g = Geom{p.ptr, p.h, p.w, p.ww};
-        return true;
-    }
-    const int64_t* e = p.table + (size_t)page * OCRVI_PAGE_ENTRY;
-    const int64_t a = e[0], h = e[1], w = e[2];
-    if (a == 0 || h <= 0 || w <= 0 || h > MAX_SIDE || w > MAX_SIDE) return false;
-    const int ww = working_width((int)h, (int)w, work_h);
-    if (ww < MIN_WW || ww > ww_cap) return false;
-    g = Geom{(const uint8_t*)(uintptr_t)a, (int)h, (int)w, ww};
-    return true;
-}
 
 __device__ inline uint32_t luma(uint32_t r, uint32_t g, uint32_t b) { return (77u * r + 150u * g + 29u * b + 128u) >> 8; }
 
@@ -291,6 +259,8 @@ inline Layout layout(int n, int work_h, int ww_cap) {
     return l;
 }
 
+}  // namespace
+
 int check_work(const char* what, int device, int work_h, int ww) {
     OCRVI_CHECK(device >= 0, OCRVI_EINVAL, "%s: device %d", what, device);
     OCRVI_CHECK(work_h >= MIN_WORK_H && work_h <= MAX_WORK_H, OCRVI_EINVAL, "%s: work_h = %d (%d .. %d)", what, work_h, MIN_WORK_H, MAX_WORK_H);
@@ -304,6 +274,8 @@ int launch_grey(const Pages& p, int n, int work_h, int ww_cap, uint8_t* out, siz
     OCRVI_HIP(hipGetLastError());
     return OCRVI_OK;
 }
+
+namespace {
 int launch_smooth(const Pages& p, int n, int work_h, int ww_cap, const uint8_t* in, uint8_t* out, size_t stride, hipStream_t st) {
     ProfScope ps("doc_smooth", 0.0, 0.0, st);
     hipLaunchKernelGGL(smooth_kernel, dim3((ww_cap + SM_TW - 1) / SM_TW, (work_h + SM_TH - 1) / SM_TH, n), dim3(256), 0, st, p, work_h, ww_cap, in, out,

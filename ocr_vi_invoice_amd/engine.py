@@ -30,8 +30,8 @@ import torch
 
 from . import _lib
 from .codec import IMAGE_BYTES, JPEG, PNG, format_of_info, imdecode, info_struct, parse_into, stream_buffer, table_entry
-from .pipeline import (DBPostProcessor, _check_crop, db_boxes_pages, enhance_init, enhance_workspace_bytes, find_document_quads,
-                       four_point_geometry, overlay_paint_, overlay_segments, quad_crops)
+from .pipeline import (DBPostProcessor, _check_crop, db_boxes_pages, enhance_init, enhance_workspace_bytes, estimate_skews, find_document_quads,
+                       four_point_geometry, overlay_paint_, overlay_segments, quad_crops, skew_quad)
 from .rec import check_beam, check_lm, make_recognitions
 
 _ARENA_ALIGN = 256
@@ -109,6 +109,10 @@ class Engine:
     for all pages, on the current stream), then exactly the path above runs: the result equals ``run(pages, find_document_quads(pages),
     enhance)``.  Encoded pages are decoded once, up front (``codec.imdecode``), and host arrays uploaded once; they go on as device
     tensors, so ``stats`` counts no ``jpeg`` / ``png`` page in that mode.
+    ``run(pages, quads="deskew")``: decoded and uploaded in the same way, the pages go through ``pipeline.estimate_skews`` (one page table
+    and one launch per stage); a page whose estimate has ``k != 0`` and ``gain >= deskew_min_gain`` (the constructor's argument; 1.0 takes
+    every non-zero estimate) gets ``pipeline.skew_quad(h, w, k)``, every other page ``None``, and the path above runs: the result equals
+    ``run(pages, those_quads)``.  ``stats["deskewed"]`` counts the pages that were turned.
     ``run(pages, quads, enhance)``: ``enhance`` is a bool for all pages or one bool per page; such a page goes through
     ``ocrvi_enhance_u8`` (``pipeline.enhance_document``, src/preprocess/scanner.py:55-76) in its arena slot, after its rectification and
     ahead of its chunk's detector launch, eagerly on the detector stream, as ``detect_and_recognize(page, ..., enhance=True)`` does.
@@ -148,7 +152,8 @@ class Engine:
     def __init__(self, det_model, rec_model, post_processor: DBPostProcessor, det_size: int = 960, rec_size: Tuple[int, int] = (32, 256),
                  det_chunk: int = 16, rec_batch: int = 256, max_pages: int = 256, graphs: bool = True, graph_cache: int = 16,
                  post_threads: int = 0, prob_hook=None, binary_head: bool = False, crop: str = "rect", annotate: bool = False,
-                 confidence: bool = False, beam: int = None, nbest: int = 1, lm=None, lm_weight: float = 1.0, len_bonus: float = 0.0):
+                 confidence: bool = False, beam: int = None, nbest: int = 1, lm=None, lm_weight: float = 1.0, len_bonus: float = 0.0,
+                 deskew_min_gain: float = 1.0):
         rh, rw = int(rec_size[0]), int(rec_size[1])
         if rh <= 0 or rw <= 0 or rh % 16 or rw % 4:
             raise ValueError(f"rec_size {rec_size}: the height must be a multiple of 16 and the width of 4")
@@ -165,6 +170,7 @@ class Engine:
         self.det_chunk, self.rec_batch, self.max_pages = int(det_chunk), int(rec_batch), int(max_pages)
         self.graphs, self.graph_cache, self.prob_hook = bool(graphs), int(graph_cache), prob_hook
         self.binary_head = bool(binary_head)
+        self.deskew_min_gain = float(deskew_min_gain)
         self.crop = _check_crop(crop)
         self.post_threads = int(post_threads) or _usable_cores()
         self.lib = _lib.load()
@@ -666,9 +672,10 @@ class Engine:
         pages = list(pages)
         self._annotate, self._annotated = bool(self.annotate), [None] * len(pages)
         t_start = time.perf_counter()              # (total_s includes the host entropy decode of JPEG pages and the inflate of PNG pages)
+        deskewed = 0
         if isinstance(quads, str):
-            if quads != "auto":
-                raise ValueError(f"quads: expected None, a list of quads or \"auto\", got {quads!r}")
+            if quads not in ("auto", "deskew"):
+                raise ValueError(f"quads: expected None, a list of quads, \"auto\" or \"deskew\", got {quads!r}")
             for i, p in enumerate(pages):
                 self._check_page(i, p)
             enc = [i for i, p in enumerate(pages) if isinstance(p, IMAGE_BYTES)]
@@ -676,7 +683,13 @@ class Engine:
                 pages[i] = page
             pages = [p if isinstance(p, torch.Tensor) and p.is_cuda else
                      torch.as_tensor(np.ascontiguousarray(p) if isinstance(p, np.ndarray) else p).to(self.dev) for p in pages]
-            quads = find_document_quads(pages, device=self.dev)
+            if quads == "auto":
+                quads = find_document_quads(pages, device=self.dev)
+            else:
+                skews = estimate_skews(pages, device=self.dev)
+                quads = [skew_quad(p.shape[0], p.shape[1], s.k) if s is not None and s.k != 0 and s.gain >= self.deskew_min_gain else None
+                         for p, s in zip(pages, skews)]
+                deskewed = sum(q is not None for q in quads)
         infos = {i: info_struct(p, f"page {i}") for i, p in enumerate(pages) if isinstance(p, IMAGE_BYTES)}
         raw_sizes = [self._check_page(i, p, infos.get(i)) for i, p in enumerate(pages)]
         # (every ValueError -- pages, quads, sizes that round to 0 -- is raised here, before any GPU work)
@@ -697,7 +710,7 @@ class Engine:
             if h > self.L or w > self.L:
                 raise RuntimeError(f"page {i}: bucket {h}x{w} exceeds the {self.L}x{self.L} the workspace was sized for")
         self.stats = {"pages": len(pages), "buckets": {f"{h}x{w}": len(v) for (h, w), v in buckets.items()}, "crops": 0, "rec_batches": 0,
-                      "rectified": 0, "enhanced": 0, "launch_s": 0.0, "det_wait_s": 0.0, "post_s": 0.0, "rec_wait_s": 0.0}
+                      "rectified": 0, "enhanced": 0, "deskewed": deskewed, "launch_s": 0.0, "det_wait_s": 0.0, "post_s": 0.0, "rec_wait_s": 0.0}
         if self.crop == "quad":
             self.stats["quad_s"] = 0.0             # host time of ocrvi_min_area_quads + ocrvi_quad_crops (not part of post_s)
         if not pages:

@@ -17,7 +17,7 @@ those libraries is unpinned; it is checked bit-for-bit aga
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import ctypes
 
@@ -761,6 +761,96 @@ def find_document_quad(image, polarity="auto", device: str = "cuda:0"):
     return find_document_quads([image], polarity, device)[0]
 
 
+# ---------------------------------------------------------------------------------------------------- skew estimate
+class Skew(NamedTuple):
+    """``ocrvi_skew_pick``: the slope index ``k`` (-128 .. 128; the text lines' image slope is k / 512, y pointing down), ``angle`` =
+    atan(k / 512) in degrees, and ``gain`` = S_k / S_0, how much sharper the projection profile is along that slope than along the rows."""
+    k: int
+    angle: float
+    gain: float
+
+
+def skew_scores(pages: Sequence[torch.Tensor], work_h: int = _lib.DOC_WORK_H):
+    """``ocrvi_skew_scores_pages`` on the current stream for device pages (uint8 HxWx3, one device) of any sizes: one page table, one launch
+    per stage (grey, edges, scores).  Returns (scores, valid): an int64 device tensor [n, 257] holding the uint64 scores S_k at column
+    k + 128, and per page whether it lies inside the bounds of ``doc_working_size`` (otherwise its row is zero)."""
+    pages = [p.contiguous() for p in pages]
+    wws = []
+    for p in pages:
+        try:
+            wws.append(doc_working_size(p.shape[0], p.shape[1], work_h)[0])
+        except ValueError:
+            wws.append(None)
+    lib, device, n = _lib.load(), pages[0].device, len(pages)
+    ww_cap = max([w for w in wws if w is not None] + [8])
+    ws_bytes = ctypes.c_size_t(0)
+    _lib.check(lib.ocrvi_skew_sizes(n, int(work_h), ww_cap, ctypes.byref(ws_bytes)))
+    with torch.cuda.device(device):
+        table = torch.tensor([(p.data_ptr(), p.shape[0], p.shape[1], 0) for p in pages], dtype=torch.int64).pin_memory().to(device, non_blocking=True)
+        ws = torch.empty(ws_bytes.value, dtype=torch.uint8, device=device)
+        scores = torch.empty((n, _lib.SKEW_ANGLES), dtype=torch.int64, device=device)
+        _lib.check(lib.ocrvi_skew_scores_pages(_dev_index(device), table.data_ptr(), n, int(work_h), ww_cap, scores.data_ptr(), ws.data_ptr(),
+                                               ws.numel(), torch.cuda.current_stream(device).cuda_stream))
+    return scores, [w is not None for w in wws]
+
+
+def skew_pick(scores) -> Skew:
+    """``ocrvi_skew_pick`` (host only): 257 uint64 scores -> ``Skew``."""
+    s = np.ascontiguousarray(np.asarray(scores).reshape(_lib.SKEW_ANGLES)).view(np.uint64)
+    k, angle, gain = ctypes.c_int32(0), ctypes.c_double(0), ctypes.c_double(0)
+    _lib.check(_lib.load().ocrvi_skew_pick(s.ctypes.data, ctypes.byref(k), ctypes.byref(angle), ctypes.byref(gain)))
+    return Skew(k.value, angle.value, gain.value)
+
+
+def skew_quad(h: int, w: int, k: int) -> np.ndarray:
+    """``ocrvi_skew_quad`` (host only): the corners, float64 [4, 2] of (x, y), of the upright rectangle in the frame turned by slope index
+    ``k`` that encloses the whole h x w page -- what ``four_point_transform`` / ``Engine.run`` take to straighten the page; nothing of the page
+    is lost, the wedges outside it come out 0.  ``k = 0`` gives the page's own corners."""
+    quad = np.zeros((4, 2), np.float64)
+    _lib.check(_lib.load().ocrvi_skew_quad(int(h), int(w), int(k), quad.ctypes.data))
+    return quad
+
+
+def estimate_skews(images, work_h: int = _lib.DOC_WORK_H, device: str = "cuda:0"):
+    """By how much each page is rotated (include/ocrvi.h, "Skew estimate"), for a list of pages of any sizes: host arrays, device tensors,
+    JPEG bytes or PNG bytes, as ``find_document_quads`` takes them.  All pages go through one page table and one launch per stage
+    (``ocrvi_skew_scores_pages``); 2 KB of scores per page come back and the host picks (``ocrvi_skew_pick``).  Returns one ``Skew`` per
+    page, ``None`` for a page outside the bounds of ``doc_working_size``.  The range is +-14 degrees in steps of 0.11; a turn of 90 or 180
+    degrees is not seen."""
+    images = list(images)
+    if not images:
+        return []
+    dev = torch.device(device)
+    enc = [i for i, p in enumerate(images) if isinstance(p, IMAGE_BYTES)]
+    pages = list(images)
+    for i, page in zip(enc, imdecode([images[i] for i in enc], dev) if enc else []):
+        pages[i] = page
+    for i, p in enumerate(pages):
+        _check_rgb(p, f"estimate_skews: page {i}")
+        if not (isinstance(p, torch.Tensor) and p.is_cuda):
+            pages[i] = torch.as_tensor(np.ascontiguousarray(p) if isinstance(p, np.ndarray) else p).to(dev)
+    scores, valid = skew_scores(pages, work_h)
+    host = scores.cpu().numpy()
+    return [skew_pick(host[i]) if ok else None for i, ok in enumerate(valid)]
+
+
+def estimate_skew(image, work_h: int = _lib.DOC_WORK_H, device: str = "cuda:0"):
+    """``estimate_skews`` for one page: a ``Skew`` or ``None``."""
+    return estimate_skews([image], work_h, device)[0]
+
+
+def deskew(image, min_gain: float = 1.0, device: str = "cuda:0"):
+    """-> (image, Skew): the page straightened by ``four_point_transform(image, skew_quad(h, w, k))`` when the estimate has ``k != 0`` and
+    ``gain >= min_gain``; otherwise -- and for a page outside the bounds, whose Skew is ``None`` -- the image comes back untouched.  The
+    straightened page is larger than the original: it encloses all of it."""
+    if isinstance(image, IMAGE_BYTES):
+        image = imdecode(image, device)
+    skew = estimate_skew(image, device=image.device if isinstance(image, torch.Tensor) and image.is_cuda else device)
+    if skew is None or skew.k == 0 or not skew.gain >= min_gain:
+        return image, skew
+    return four_point_transform(image, skew_quad(image.shape[0], image.shape[1], skew.k), device), skew
+
+
 # ---------------------------------------------------------------------------------------------------- result overlay
 def _overlay_rgb(c, what: str) -> int:
     try:
@@ -921,7 +1011,8 @@ def detect_and_recognize(original_image, det_model, rec_model, post_processor: D
     (``bytes`` / ``bytearray`` / ``memoryview``: ``imdecode`` first, the reference's cv2.imread, pipeline2.py:284-288).
     ``binary_head``: call ``det_model.forward_binary`` (the binarise branch alone; same map in f32 / f16x2) instead of ``det_model(...)``.
     ``quad``: the document's four corners in ``original_image`` (step 1, pipeline2.py:291-302): the page is rectified first
-    (``four_point_transform``) and replaces the original, so the boxes are in the rectified page's coordinates (:297).
+    (``four_point_transform``) and replaces the original, so the boxes are in the rectified page's coordinates (:297).  ``quad="deskew"``:
+    the page goes through ``deskew`` first (the skew estimated on the device, the page turned upright when it is tilted).
     ``enhance``: ``enhance_document`` on the (rectified) page before the detector resize (scanner.py:190-191): boxes and crops come from
     the enhanced page.
     ``crop``: ``"rect"`` (the reference's crop, the default) or ``"quad"``: each box's minimum-area rectangle is warped upright into the
@@ -942,6 +1033,10 @@ def detect_and_recognize(original_image, det_model, rec_model, post_processor: D
         original_image = imdecode(original_image, device)
     page = original_image if isinstance(original_image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(original_image))
     page = page.to(device).contiguous()
+    if isinstance(quad, str):
+        if quad != "deskew":
+            raise ValueError(f"quad: expected None, four corners or \"deskew\", got {quad!r}")
+        page, quad = deskew(page)[0], None
     if quad is not None:
         page = four_point_transform(page, quad)
     if enhance:
