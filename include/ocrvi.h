@@ -1203,6 +1203,18 @@ int ocrvi_test_mlp_raw(int device, int dtype, float* x, const float* ln_g_host, 
  * at small M.  iters > 0: avg_ms = mean time of `iters` launches. */
 int ocrvi_test_lin_x2(int device, const float* a, const float* weight_host, const float* bias_host, int M, int K, int N, int max_workgroups,
                       void* out_raw, float* out, int iters, float* avg_ms);
+/* gconv_x2_kernel (LocalMixing's grouped 3x3, stride 1, pad 1, 32 channels per group in and out, OCRVI_F16X2) on its own, arguments as
+ * ocrvi_test_conv_raw with Co = C and groups = C / 32.  Two epilogues: out_f32 = 0 and res NULL: act(conv + bias) as f16x2; out_f32 = 1, res
+ * and res_post = 1: act(conv + bias) + res in float32 (in_place: the residual is copied into out_raw, which is then residual and output).
+ * Anything else, or a shape the kernel does not take, returns OCRVI_EINVAL.  max_workgroups > 0 caps the workgroups per group, so that a
+ * workgroup walks several tiles.  With OCRVI_GCONV32=0 the same call runs where the model then runs it, on conv_gemm (A/B timing).
+ * iters > 0: avg_ms = mean time of `iters` launches (they repeat the call: do not time an in_place one for its values). */
+int ocrvi_test_gconv_x2(int device, const float* x, const float* weight_host, const float* bias_host, const float* res, int N, int C, int H, int W,
+                        int act, int res_post, int out_f32, int in_place, int max_workgroups, void* out_raw, float* out, int iters, float* avg_ms);
+/* Host-only (no GPU): the tiling of that launch on a device of n_cu compute units.  plan = {rows per tile bh, 16-pixel blocks per tile row
+ * nbx, tiles down an image bands_y and across it bands_x, tiles per group, workgroups per group, fewest and most tiles one workgroup walks,
+ * groups, dynamic LDS bytes}. */
+int ocrvi_test_gconv_x2_plan(int N, int C, int H, int W, int n_cu, int max_workgroups, int32_t plan[10]);
 /* Host-only (no GPU): the OCRVI_F16X2 weight format.  src: n fp32 values of one layer (n % 4 == 0) -> dst: n 4-byte elements, per chunk of
  * 4 consecutive elements [hi0 hi1 hi2 hi3 | lo0 lo1 lo2 lo3] (fp16), hi + lo = src * 2^s with one power of two s per layer that puts the
  * largest magnitude into [2^13, 2^14); *wscale = 2^-s.  (What ocrvi_*_create does to every GEMM weight in that mode.) */

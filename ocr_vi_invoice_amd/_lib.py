@@ -54,6 +54,7 @@ EXPORTS = [
     "ocrvi_ctc_beam_workspace_bytes", "ocrvi_ctc_beam",
     "ocrvi_lm_build", "ocrvi_lm_score", "ocrvi_lm_create", "ocrvi_lm_destroy", "ocrvi_ctc_beam_lm_workspace_bytes", "ocrvi_ctc_beam_lm",
     "ocrvi_skew_sizes", "ocrvi_skew_scores_pages", "ocrvi_skew_edges_u8", "ocrvi_skew_scores", "ocrvi_skew_pick", "ocrvi_skew_quad",
+    "ocrvi_test_gconv_x2", "ocrvi_test_gconv_x2_plan",
 ]
 PAGE_ENTRY = 4          # int64 fields of one page-table entry: (device address, height, width, 0) -- OCRVI_PAGE_ENTRY
 # ocrvi_det_eval's record: 13 slots of 8 bytes (OCRVI_DET_EVAL_*), the first six int64, the rest float64
@@ -185,6 +186,8 @@ def load() -> C.CDLL:
     lib.ocrvi_test_dcn_plan.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int32)]
     lib.ocrvi_test_conv_raw.argtypes = [i32, i32, f32p, vp, vp, f32p] + [i32] * 13 + [vp, f32p]
     lib.ocrvi_test_gconv_plan.argtypes = [i32] * 12 + [C.POINTER(C.c_int32)]
+    lib.ocrvi_test_gconv_x2.argtypes = [i32, f32p, vp, vp, f32p] + [i32] * 9 + [vp, f32p, i32, C.POINTER(C.c_float)]
+    lib.ocrvi_test_gconv_x2_plan.argtypes = [i32] * 6 + [C.POINTER(C.c_int32)]
     lib.ocrvi_test_stem_pool.argtypes = [i32, i32, f32p, vp, vp, i32, i32, i32, i32, f32p, i32, C.POINTER(C.c_float)]
     lib.ocrvi_test_conv3_halo_raw.argtypes = [i32, f32p, vp, vp, i32, i32, i32, i32, i32, i32, vp, f32p]
     lib.ocrvi_test_bneck_tail_raw.argtypes = [i32, f32p, f32p, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, f32p, f32p]

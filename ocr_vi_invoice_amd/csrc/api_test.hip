@@ -389,6 +389,57 @@ extern "C" int ocrvi_test_gconv_plan(int dtype, int N, int C, int H, int W, int 
     return OCRVI_OK;
 }
 
+// gconv_x2_kernel alone (gconv_x2.hip): ocrvi_test_conv_raw's call for LocalMixing's f16x2 convolutions, straight to the kernel.  With
+// OCRVI_GCONV32=0 the call goes where the model then sends it, through conv() (A/B timing of the two paths with one hook).
+extern "C" int ocrvi_test_gconv_x2(int device, const float* x, const float* weight_host, const float* bias_host, const float* res, int N, int C, int H,
+                                   int W, int act, int res_post, int out_f32, int in_place, int max_workgroups, void* out_raw, float* out, int iters,
+                                   float* avg_ms) {
+    OCRVI_CHECK(x && weight_host && out && out_raw && N > 0 && H > 0 && W > 0 && C >= 64 && C % 32 == 0, OCRVI_EINVAL, "test_gconv_x2: bad argument");
+    OCRVI_CHECK(act == ACT_NONE || act == ACT_RELU || act == ACT_GELU, OCRVI_EINVAL, "test_gconv_x2: unknown activation %d", act);
+    OCRVI_CHECK(!in_place || (res && out_f32), OCRVI_EINVAL, "test_gconv_x2: in_place needs a residual and an fp32 output");
+    const int dtype = OCRVI_F16X2, groups = C / 32;
+    OCRVI_HIP(hipSetDevice(device));
+    Scratch sc;
+    OCRVI_TRY(sc.init());
+    DeviceStore st;
+    ConvLayer L;
+    PackedConv pc = pack_conv(weight_host, bias_host, C, 32, 3, 3, groups, AM_CONV3, dtype);
+    OCRVI_TRY(upload_packed(st, pc, AM_CONV3, &L));
+    void* xn = nullptr;
+    OCRVI_TRY(sc.alloc((size_t)N * H * W * C * 4, &xn));
+    OCRVI_TRY(to_nhwc(dtype, x, xn, N, C, H * W, sc.s));
+    void* rn = nullptr;
+    if (res) {   // fp32 beside an fp32 output, f16x2 otherwise (which the kernel does not take)
+        rn = out_raw;
+        if (!in_place) OCRVI_TRY(sc.alloc((size_t)N * H * W * C * 4, &rn));
+        OCRVI_TRY(to_nhwc(out_f32 ? OCRVI_F32 : dtype, res, rn, N, C, H * W, sc.s));
+    }
+    Tensor tx = wrap(xn, N, H, W, C, false), ty = wrap(out_raw, N, H, W, C, out_f32 != 0), tr = wrap(rn, N, H, W, C, out_f32 != 0);
+    ConvOpts o;
+    o.pad = 1; o.act = act; o.res_post = res_post;
+    if (res) { o.res = &tr; o.res_mode = RES_SAME; }
+    const ConvParams p = fill_conv_params(L, tx, ty, o);
+    if (gconv32_on()) {
+        OCRVI_CHECK(gconv_x2_eligible(p, dtype), OCRVI_EINVAL, "test_gconv_x2: the kernel does not take this call (out_f32 %d, res %d, res_post %d)",
+                    out_f32, res != nullptr, res_post);
+        OCRVI_TRY(timed(sc, iters, avg_ms, [&]() { return k_gconv_x2(p, sc.s, max_workgroups); }));
+    } else {
+        OCRVI_TRY(timed(sc, iters, avg_ms, [&]() { return launch_conv_dt(dtype, p, AM_CONV3, sc.s); }));
+    }
+    OCRVI_TRY(k_nhwc_to_nchw_f32(out_f32 ? OCRVI_F32 : dtype, out_raw, out, N, H, W, C, C, 0, sc.s));
+    OCRVI_HIP(hipStreamSynchronize(sc.s));
+    return OCRVI_OK;
+}
+
+// Host only: the tiling k_gconv_x2 launches on a device of n_cu compute units.  No device is touched.
+extern "C" int ocrvi_test_gconv_x2_plan(int N, int C, int H, int W, int n_cu, int max_workgroups, int32_t plan[10]) {
+    OCRVI_CHECK(plan && N > 0 && H > 0 && W > 0 && C >= 64 && C % 32 == 0 && n_cu > 0, OCRVI_EINVAL, "test_gconv_x2_plan: bad argument");
+    const GconvX2Plan pl = gconv_x2_plan(N, H, W, C / 32, n_cu, max_workgroups);
+    const int32_t v[10] = {pl.bh, pl.nbx, pl.bands_y, pl.bands_x, pl.ntile, pl.grid_x, pl.tiles_min, pl.tiles_max, C / 32, pl.smem};
+    for (int i = 0; i < 10; ++i) plan[i] = v[i];
+    return OCRVI_OK;
+}
+
 namespace {
 // The ConvParams of a dense stride-1 3x3 (pad 1) f16x2 layer with a bias and ReLU / none, as conv() fills them for a layer whose loader
 // asked pack_conv for conv3_halo's weight form (`quartets`: whether the packer gave it)

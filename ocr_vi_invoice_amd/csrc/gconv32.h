@@ -194,9 +194,15 @@ __global__ __launch_bounds__(256, 2) void gconv32_kernel(const ConvParams p, int
     }
 }
 
+// OCRVI_GCONV32=0 takes the direct grouped kernels out, this one and the f16x2 one (gconv_x2.hip): LocalMixing then runs on conv_gemm
+static inline bool gconv32_on() {
+    static const bool on = !(getenv("OCRVI_GCONV32") && atoi(getenv("OCRVI_GCONV32")) == 0);
+    return on;
+}
+
 // true when (p, amode) is a LocalMixing-shaped grouped convolution this kernel handles
 static inline bool gconv32_eligible(const ConvParams& p, int amode, int esz) {
-    static const bool on = !(getenv("OCRVI_GCONV32") && atoi(getenv("OCRVI_GCONV32")) == 0);
+    const bool on = gconv32_on();
     if (!on || amode != AM_CONV3 || esz != 2 || p.groups < 2 || p.Cin_g != 32 || p.N_g != 32 || p.KH != 3) return false;
     if (p.SH != 1 || p.SW != 1 || p.PH != 1 || p.PW != 1 || p.H != p.OH || p.W != p.OW || p.store_mode != ST_NHWC) return false;
     if (p.Kp < 288 || p.Cin % 8 != 0 || p.cin_off % 8 != 0 || ((uintptr_t)p.x & 15) != 0 || ((uintptr_t)p.w & 15) != 0 || p.Kp % 8 != 0) return false;

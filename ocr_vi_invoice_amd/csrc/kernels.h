@@ -41,6 +41,21 @@ void pack_mlp_stream(const float* w1, const float* w2, int D, int dtype, std::ve
 bool lin_x2_eligible(int dtype, int K, int N);
 void pack_lin_x2_stream(const float* w, int N, int K, std::vector<char>& out);
 int k_lin_x2(const void* a, const void* wstream, const float* bias, void* out, int M, int K, int N, hipStream_t s, int max_workgroups = 0);
+// Direct grouped 3x3 (stride 1, pad 1, 32 channels per group in and out) for f16x2 on a full-height halo tile (gconv_x2.hip): SVTRv2's
+// LocalMixing pair.  p: as conv() fills it for the layer (weights in pack_conv's chunk form [group][32][Kp]).  Two epilogues:
+// act(acc wscale + bias) -> f16x2, and act(acc wscale + bias) + fp32 residual -> fp32 (res_post; the residual may be the output buffer).
+// gconv_x2_eligible: by the call alone, and off together with gconv32 (OCRVI_GCONV32=0).  max_workgroups > 0 caps the workgroups per group.
+struct ConvParams;
+struct GconvX2Plan {
+    int bh, nbx;               // output rows (a band of the image: all of it up to 12 rows) and 16-pixel blocks per tile row
+    int bands_y, bands_x;      // tiles down and across one image
+    int ntile, grid_x;         // tiles per group; workgroups per group (grid = grid_x * groups, a tile's groups side by side)
+    int tiles_min, tiles_max;  // tiles the workgroups walk
+    int smem;
+};
+GconvX2Plan gconv_x2_plan(int n_img, int H, int W, int groups, int n_cu, int max_workgroups = 0);
+bool gconv_x2_eligible(const ConvParams& p, int dtype);
+int k_gconv_x2(const ConvParams& p, hipStream_t s, int max_workgroups = 0);
 int k_mlp_fused(int dtype, float* x, void* xn, const float* ln_g, const float* ln_b, const float* next_g, const float* next_b, const void* wstream,
                 const float* b1, const float* b2, int M, int D, hipStream_t s);
 // f32 -> T cast (n elements).

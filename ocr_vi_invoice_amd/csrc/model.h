@@ -78,6 +78,10 @@ struct ConvOpts {
 };
 // y must be pre-shaped (n,h,w,c, f32) and allocated; x likewise.
 int conv(Runner& r, const ConvLayer& L, const Tensor& x, const Tensor& y, const ConvOpts& o);
+// The two halves of conv() for callers that route a layer to a kernel of their own (rec_model.hip's LocalMixing convolutions, the test
+// hooks): the ConvParams conv() launches with, and its checks of the activation type and the output shape.
+ConvParams fill_conv_params(const ConvLayer& L, const Tensor& x, const Tensor& y, const ConvOpts& o);
+int check_conv_shapes(const Runner& r, const ConvLayer& L, const Tensor& x, const ConvParams& p, const ConvOpts& o);
 
 // ---------------------------------------------------------------- what every model handle's C entries share
 // A handle has `device`, `cfg.dtype` and a RangeWatch `range`.  `check()` validates the handle and the shape; `run(Runner&)` walks the

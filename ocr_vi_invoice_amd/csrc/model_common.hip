@@ -37,7 +37,7 @@ int load_vec(DeviceStore& st, const Blob& blob, const std::string& name, int n, 
     return st.upload(t->data, (size_t)n * 4, (void**)out);
 }
 
-int conv(Runner& r, const ConvLayer& L, const Tensor& x, const Tensor& y, const ConvOpts& o) {
+ConvParams fill_conv_params(const ConvLayer& L, const Tensor& x, const Tensor& y, const ConvOpts& o) {
     ConvParams p;
     p.x = x.p; p.w = L.w; p.bias = L.bias; p.out = y.p;
     p.n_img = x.n; p.H = x.h; p.W = x.w; p.Cin = x.c;
@@ -67,12 +67,22 @@ int conv(Runner& r, const ConvLayer& L, const Tensor& x, const Tensor& y, const 
     }
     p.offs = o.offs;
     p.Hp = o.Hp; p.Wp = o.Wp;
+    return p;
+}
+
+int check_conv_shapes(const Runner& r, const ConvLayer& L, const Tensor& x, const ConvParams& p, const ConvOpts& o) {
     OCRVI_CHECK(!x.f32 || r.dtype == OCRVI_F32, OCRVI_EINVAL, "conv: f32 activations fed to a %d-typed GEMM", r.dtype);
     if (L.amode != AM_ROWS) {
         const int k = L.amode == AM_CONV1 ? 1 : 3;
         const int eh = (x.h + 2 * o.pad - k) / o.sh + 1, ew = (x.w + 2 * o.pad - k) / o.sw + 1;
         OCRVI_CHECK(eh == p.OH && ew == p.OW, OCRVI_EINVAL, "conv: output %dx%d but expected %dx%d", p.OH, p.OW, eh, ew);
     }
+    return OCRVI_OK;
+}
+
+int conv(Runner& r, const ConvLayer& L, const Tensor& x, const Tensor& y, const ConvOpts& o) {
+    const ConvParams p = fill_conv_params(L, x, y, o);
+    OCRVI_TRY(check_conv_shapes(r, L, x, p, o));
     if (r.dry()) return OCRVI_OK;
     return launch_conv_dt(r.dtype, p, L.amode, r.stream);
 }

@@ -177,6 +177,18 @@ static int linear(Runner& r, const ConvLayer& L, void* lin, const Tensor& x, con
     if (r.dry()) return OCRVI_OK;
     return k_lin_x2(x.p, lin, L.bias, y.p, (int)x.pixels(), x.c, y.c, r.stream);
 }
+// One of LocalMixing's grouped 3x3 convolutions (stride 1, pad 1): f16x2 calls that gconv_x2_eligible accepts run on gconv_x2.hip, every
+// other one on the conv family as before (OCRVI_GCONV32=0 sends all of them there)
+static int local_conv(Runner& r, const ConvLayer& L, const Tensor& x, const Tensor& y, const ConvOpts& o) {
+    if (r.dtype == OCRVI_F16X2 && L.amode == AM_CONV3) {
+        const ConvParams p = fill_conv_params(L, x, y, o);
+        if (gconv_x2_eligible(p, r.dtype)) {
+            OCRVI_TRY(check_conv_shapes(r, L, x, p, o));
+            return r.dry() ? OCRVI_OK : k_gconv_x2(p, r.stream);
+        }
+    }
+    return conv(r, L, x, y, o);
+}
 // Multi-head self-attention over `seqs` sequences of `len` tokens, qkv -> out.  Sequences beyond 512 keys in the 4-byte modes go through
 // per-chunk partial rows that are merged: their scratch comes from the arena for the duration of the call.
 static int attention(Runner& r, const Tensor& qkv, const Tensor& out, int seqs, int len, int heads) {
@@ -272,9 +284,9 @@ static int rec_run(ocrvi_rec* h, Runner& r, const float* x, int B, int H, int W,
             if (bw.local) {  // x + gelu(bn(conv(gelu(bn(conv(LN x))))))  (svtrv2.py:57-63,98)
                 ConvOpts o;
                 o.pad = 1; o.act = ACT_GELU;
-                OCRVI_TRY(conv(r, bw.conv1, xn, t1, o));
+                OCRVI_TRY(local_conv(r, bw.conv1, xn, t1, o));
                 o.res = &xs; o.res_mode = RES_SAME; o.res_post = 1;
-                OCRVI_TRY(conv(r, bw.conv2, t1, xs, o));
+                OCRVI_TRY(local_conv(r, bw.conv2, t1, xs, o));
             } else {  // x + proj(MHSA(qkv(LN x)))  (svtrv2.py:77-86,98)
                 ConvOpts o;
                 OCRVI_TRY(linear(r, bw.qkv, bw.qkv_lin, view(xn, rows, 1, 1, d), view(big, rows, 1, 1, 3 * d)));
